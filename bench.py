@@ -26,6 +26,13 @@ imbalance shows in `ranks` (per-rank path-kernel ms and path counts).
 (256^2, 16 spp, 4 bounces): the GPU renders it and the CPU baseline leg runs
 the WHOLE C1 frame on the oracle (the C1 plumbing number).
 
+A plain run sets up, warms up, times the steps and prints the result line.
+--full adds what the headline figure does not need: the counting re-render
+behind `roofline`, `events_per_path`, `mrays_per_s` and the per-rank rows, and
+the CPU-baseline leg (`cpu_baseline`, `gpu_vs_cpu`); those keys are null
+without it. --dump-outputs DIR writes the GridRenderPlane arrays the timed
+steps left (what a caller of the path receives) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -76,12 +83,18 @@ def parse():
     ap.add_argument("--depth-max", type=int, default=None)
     ap.add_argument("--seed", type=int, default=20241223)
     ap.add_argument("--tile-rows", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the counting re-render (roofline, events per path, "
+                         "per-rank rows) and the CPU-baseline leg; a plain run leaves those keys null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image state after the last timed step (pixels, counters, sums, pixel_max) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=30.0,
-                    help="minimum duration of the CPU-baseline sample (0 = skip)")
+                    help="--full: minimum duration of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (0 = this process's CPU share, see cpu_threads())")
     ap.add_argument("--no-counters", action="store_true",
-                    help="skip the (untimed) counting re-render used for the roofline")
+                    help="--full: skip the (untimed) counting re-render used for the roofline")
     ap.add_argument("--sync", action="store_true",
                     help="one synchronous ipt_render_device per step instead of queuing the steps with "
                          "ipt_render_device_async (which lets each step's launch fill the previous one's tail)")
@@ -241,6 +254,29 @@ def cpu_baseline(args, desc):
     return out
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # of the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, state):
+    """The GridRenderPlane arrays [H][W] a caller of the timed path receives,
+    as they stand after the last timed step: pixels, sums, pixel_max (float32)
+    and counters (int32, written as float64). A frame whose arrays exceed the
+    budget (c4) is written as one fixed, seeded sample of its pixels, the same
+    flat indices for every array."""
+    st = state.cpu().numpy()  # [4][H][W] float32; field 1 holds the int32 counters' bits
+    fields = {"pixels": st[0], "counters": st[1].view(np.int32).astype(np.float64),
+              "sums": st[2], "pixel_max": st[3]}
+    npix = st[0].size
+    keep = DUMP_BUDGET_BYTES // (3 * 4 + 8)
+    idx = None
+    if npix > keep:
+        idx = np.sort(np.random.default_rng(20241223).choice(npix, size=keep, replace=False))
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in fields.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a if idx is None else a.reshape(-1)[idx]))
+
+
 def main():
     args = parse()
     import torch
@@ -367,13 +403,15 @@ def main():
         verify = bool(torch.equal(whole.view(torch.int32), state.view(torch.int32)))
         del whole
     mean_pixel = float(pixels.mean().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state)
 
     # algorithmic op count of the timed work: re-render the same passes with
     # the kernel's event counters (untimed; counts are deterministic)
     roof = None
     cnt = None
     ranks = None
-    if not args.no_counters:
+    if args.full and not args.no_counters:
         sv = state.clone()
         ctx.reset_counters()
         acc_alone_ms = 0.0
@@ -520,7 +558,7 @@ def main():
         }
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         try:
             cpu = cpu_baseline(args, desc)
         except Exception as e:  # the GPU number stands on its own

@@ -7,7 +7,7 @@
 #
 #   tests[=K_EXPR]        pytest -m gpu (optionally -k K_EXPR)    -> gpurun_out/pytest_gpu.log
 #   smoke                 __graft_entry__.smoke()
-#   bench=CFG[:STEPS]     bench.py --config CFG (default steps)   -> gpurun_out/bench_CFG.json
+#   bench=CFG[:STEPS]     bench.py --full --config CFG (default steps; with the roofline) -> $OUT/bench_CFG.json
 #   ab=V1,V2,...@CFG[:N]  A/B of library variants (ipt_amd/lib/abl/libipt_V.so, `default` =
 #                         the product library), N rounds of V1..Vk in turn, 2 bench steps each
 #   sq=CFG,CFG            SQ / cache counter passes (TAG env)     -> gpurun_out/sq_TAG_CFG_summary.json
@@ -22,6 +22,9 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-latest}
+# where the steps rewritten for `bench.py --full` put their files (OUT env)
+export OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 
 line() {  # one-line summary of a bench JSON line
   python3 - "$1" <<'PY'
@@ -50,9 +53,9 @@ step() {
     bench)
       local c=${v%%:*} n=
       [ "$c" != "$v" ] && n="--steps ${v#*:}"
-      timeout -k 10 600 python3 bench.py --config "$c" $n --cpu-seconds 0 > "gpurun_out/bench_$c.json" \
-        2> "gpurun_out/bench_$c.err" || { tail -5 "gpurun_out/bench_$c.err"; return 1; }
-      line "gpurun_out/bench_$c.json" ;;
+      timeout -k 10 600 python3 bench.py --full --config "$c" $n --cpu-seconds 0 > "$OUT/bench_$c.json" \
+        2> "$OUT/bench_$c.err" || { tail -5 "$OUT/bench_$c.err"; return 1; }
+      line "$OUT/bench_$c.json" ;;
     ab)
       local vs=${v%%@*} rest=${v#*@} c n
       c=${rest%%:*}; n=1; [ "$c" != "$rest" ] && n=${rest#*:}

@@ -64,6 +64,37 @@ def test_cpu_baseline_reports_threads_and_single_thread_rate():
         assert abs(r["full_host_extrapolated_Mpaths_s"] - r["single_thread_paths_per_s"] * phys / 1e6) < 1e-9
 
 
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the budget is written whole ([H][W],
+    float32; the int32 counters as float64), a larger one as the same seeded
+    sample of flat pixel indices for every array, identical from run to run."""
+    import numpy as np
+    import torch
+
+    H, W = 6, 10
+    st = torch.arange(4 * H * W, dtype=torch.float32).reshape(4, H, W) / 7
+    cnt = np.arange(H * W, dtype=np.int32).reshape(H, W) * 3 + 1
+    st[1] = torch.from_numpy(cnt.view(np.float32).copy())
+    bench.dump_outputs(tmp_path / "a", st)
+    for i, name in ((0, "pixels"), (2, "sums"), (3, "pixel_max")):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, st[i].numpy())
+    c = np.load(tmp_path / "a" / "counters.npy")
+    assert c.dtype == np.float64 and np.array_equal(c, cnt)
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 20 * 17)  # room for 17 of the 60 pixels
+    bench.dump_outputs(tmp_path / "b", st)
+    bench.dump_outputs(tmp_path / "c", st)
+    c = np.load(tmp_path / "b" / "counters.npy")
+    assert c.shape == (17,) and np.all(np.diff(c) > 0)
+    idx = ((c - 1) / 3).astype(np.int64)  # the counters above encode their flat index
+    for i, name in ((0, "pixels"), (2, "sums"), (3, "pixel_max")):
+        a = np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(a, st[i].numpy().reshape(-1)[idx])
+        assert np.array_equal(a, np.load(tmp_path / "c" / f"{name}.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 20 * 17 + 4 * 128
+
+
 def test_oracle_sample_renderer_is_thread_invariant():
     """The CPU baseline's sampled renderer (one path per work item) gives the
     full renderer's values at the sampled pixels, for any thread count."""

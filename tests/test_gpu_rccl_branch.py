@@ -38,7 +38,7 @@ def test_bench_rccl_branch_single_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", str(ROOT / "bench.py"),
            "--gpus", "1", "--config", "c2", "--width", "96", "--height", "80", "--spp-per-step", "2",
-           "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--verify"]
+           "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "0", "--verify"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
