@@ -12,7 +12,8 @@
  * Conventions: plain pointers and sizes, no exceptions, every call returns
  * IPT_OK (0) or a negative IPT_E_* code, the message of the last failure is
  * available from ipt_last_error(). Calls are synchronous unless they take a
- * stream argument. One context per HIP device; contexts are independent, a
+ * stream argument and say otherwise (ipt_render_device_async and
+ * ipt_display_device return once their work is queued). One context per HIP device; contexts are independent, a
  * single context is not reentrant. There is NO CPU fallback: without a usable
  * gfx950 device every rendering call fails with IPT_E_DEVICE.
  */
@@ -25,7 +26,7 @@
 extern "C" {
 #endif
 
-#define IPT_ABI_VERSION 5
+#define IPT_ABI_VERSION 6
 
 enum {
     IPT_OK = 0,
@@ -284,6 +285,62 @@ int ipt_last_kernel_ms(ipt_ctx* ctx, float* path_ms, float* accumulate_ms);
    images up to 4096 x 4096. */
 int ipt_smooth(ipt_ctx* ctx, float* pixels, int width, int height, int side, int in_place, float* max_value);
 int ipt_glare(ipt_ctx* ctx, const float* in, float* out, int width, int height, float cutoff);
+
+/* ---- display pipeline on the GPU (ABI 6), bit-exact -------------------------
+   Gui::updateDisplay / Gui::save (gui.cpp:11-16, 54-70) for a plane that stays
+   on the device: glare(image, cutoff) -> normalize (max, /max, powf(., 1/2.2),
+   cut to [0,1]) -> normalize(0,255) and the 8-bit cast. width*height row-major
+   buffers:
+     processed  glare(pixels, glare_cutoff) exactly as ipt_glare computes it, or
+                a copy of pixels when glare_cutoff == 0
+     tone       processed / mx, powf(., (float)(1.0f/2.2f)), cut to [0,1] (NaN
+                passes); mx is the reference's sequential max fold from element
+                0: NaN if and only if element 0 is NaN, otherwise the first
+                occurrence of the maximum of the non-NaN elements. NaN results
+                are the x86 host's (a NaN operand quieted; 0/0, inf/inf and
+                powf of a negative: 0xffc00000)
+     gray8      m, M = the same folds (min, max) over tone; m == M gives 0;
+                otherwise (uint8_t)((v - m) / (M - m) * 255.0f + 0.0f), NaN
+                gives 0 (the host's cast of NaN is undefined and yields 0 on
+                x86; both sides state 0)
+   Errors: a NULL pointer that is not optional, a non-positive size or a
+   negative / NaN cutoff: IPT_E_INVALID; glare on an image wider or taller
+   than 4096 (ipt_glare's limit), more than 2^31 pixels, an infinite cutoff or
+   flags != 0: IPT_E_UNSUPPORTED. */
+typedef struct ipt_display_params {
+    int32_t width, height;
+    float glare_cutoff; /* > 0: Gui::updateDisplay's glare(image, cutoff) first;
+                           0: no glare (Gui::finalize / Gui::save) */
+    uint32_t flags;     /* 0 */
+} ipt_display_params;
+
+/* Device buffers (hipMalloc'd or torch CUDA tensors), any alignment a float /
+   byte array may have. Stream semantics of ipt_render_device_async: the
+   kernels run on `hip_stream` (NULL = the context's own stream) after the work
+   already queued there, the call returns once they are queued, the outputs
+   are complete when the stream reaches that point, and ipt_render_wait,
+   ipt_upload_scene and ipt_destroy wait for them. No value crosses to the
+   host inside the call: the bright-pixel count, mx, m and M stay in device
+   memory where the next kernel reads them. dev_processed and dev_tone may be
+   NULL (the context's scratch is used). The scratch (bright list of 16 B per
+   pixel when glare is on, block counts, the scalars, 4 B per pixel for each
+   output not passed) belongs to the context, grows to the largest image seen
+   and is freed by ipt_destroy: a second call at the same size allocates,
+   frees and synchronises nothing. The input and output buffers must stay
+   valid until the stream has passed the call; dev_pixels is only read and
+   may not overlap an output. */
+int ipt_display_device(ipt_ctx* ctx, const ipt_display_params* p, const float* dev_pixels, float* dev_processed,
+                       float* dev_tone, uint8_t* dev_gray8, void* hip_stream);
+/* Host buffers: the same kernels, synchronous (uploads pixels, downloads the
+   outputs asked for; processed and tone may be NULL). */
+int ipt_display(ipt_ctx* ctx, const ipt_display_params* p, const float* pixels, float* processed, float* tone,
+                uint8_t* gray8);
+/* Probes of the display chain's powf (ipt_math.h powf_, glibc 2.35's
+   __powf_fma restated): out[i] = powf(x[i], y), host buffers; y finite, > 0
+   and not an integer (IPT_E_UNSUPPORTED otherwise). ipt_powf_host is the
+   library's host build of the code the kernels run. */
+int ipt_powf_host(const float* x, float y, float* out, int64_t n);
+int ipt_powf_device(ipt_ctx* ctx, const float* x, float y, float* out, int64_t n);
 
 /* ---- the path's DDF samplers, exactly as the kernels evaluate them -----------
    For sampler validation (the reference's chi^2 harness, check_ddf.cpp:114-203)

@@ -69,8 +69,13 @@ class Image(C.Structure):
                 ("pixel_max", C.c_void_p)]
 
 
-ABI_VERSION = 5  # include/ipt_capi.h IPT_ABI_VERSION
-ABI_LAYOUT_COMPATIBLE = (3, 4, 5)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
+class DisplayParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("glare_cutoff", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+ABI_VERSION = 6  # include/ipt_capi.h IPT_ABI_VERSION
+ABI_LAYOUT_COMPATIBLE = (3, 4, 5, 6)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
 
 COUNTER_NAMES = ("paths", "traced_rays", "surface_hits", "light_hits", "expanded_nodes",
                  "iterations", "light_samples", "skipped", "sphere_frames", "light_traces",
@@ -91,6 +96,7 @@ EXPORTED_SYMBOLS = (
     "ipt_reset_counters", "ipt_last_kernel_ms", "ipt_math_host", "ipt_math_device",
     "ipt_shard_plan", "ipt_get_profile", "ipt_math_selfcheck", "ipt_smooth", "ipt_glare", "ipt_ddf_sample", "ipt_ddf_value",
     "ipt_philox", "ipt_transfer_bytes",
+    "ipt_display_device", "ipt_display", "ipt_powf_host", "ipt_powf_device",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -158,6 +164,13 @@ def load(path: str | os.PathLike | None = None):
     lib.ipt_math_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
     lib.ipt_shard_plan.argtypes = [C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     lib.ipt_philox.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int64]
+    if hasattr(lib, "ipt_display_device"):  # ABI 6
+        lib.ipt_display_device.argtypes = [C.c_void_p, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ipt_display.argtypes = [C.c_void_p, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]
+        lib.ipt_powf_host.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_int64]
+        lib.ipt_powf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64]
     if path is None:
         _lib = lib
     return lib
@@ -204,6 +217,12 @@ def make_params(width, height, spp, spp_offset=0, n_rays=16, depth_max=8, seed=2
     p.width, p.height, p.spp, p.spp_offset = width, height, spp, spp_offset
     p.n_rays, p.depth_max, p.seed = n_rays, depth_max, seed
     p.tile_rows, p.n_shards, p.shard_id, p.flags = tile_rows, n_shards, shard_id, flags
+    return p
+
+
+def make_display_params(width, height, glare_cutoff=0.0, flags=0) -> DisplayParams:
+    p = DisplayParams()
+    p.width, p.height, p.glare_cutoff, p.flags = width, height, glare_cutoff, flags
     return p
 
 
@@ -330,6 +349,33 @@ class Context:
                                                     C.c_float(cutoff)))
         return out
 
+    def display_device(self, params: DisplayParams, pixels_ptr, gray8_ptr, processed_ptr=None, tone_ptr=None,
+                       stream=None):
+        """Queue the display pipeline on device buffers (ipt_display_device):
+        glare (params.glare_cutoff > 0), tone map, 8-bit. Complete on
+        `stream`'s order or after wait()."""
+        _check(self.lib, self.h, self.lib.ipt_display_device(self.h, C.byref(params), pixels_ptr, processed_ptr,
+                                                             tone_ptr, gray8_ptr, stream))
+
+    def display(self, pixels: np.ndarray, width: int, height: int, glare_cutoff: float = 0.0) -> dict:
+        """Host-buffer display pipeline (ipt_display): {processed, tone, gray8}."""
+        src = np.ascontiguousarray(pixels, dtype=np.float32)
+        out = {"processed": np.empty(src.size, np.float32), "tone": np.empty(src.size, np.float32),
+               "gray8": np.empty(src.size, np.uint8)}
+        _check(self.lib, self.h, self.lib.ipt_display(
+            self.h, C.byref(make_display_params(width, height, glare_cutoff)),
+            src.ctypes.data if src.size else None, out["processed"].ctypes.data, out["tone"].ctypes.data,
+            out["gray8"].ctypes.data))
+        return out
+
+    def powf_device(self, x: np.ndarray, y: float) -> np.ndarray:
+        """powf(x, y) as the display kernels compute it, on the device."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.empty_like(x)
+        _check(self.lib, self.h, self.lib.ipt_powf_device(self.h, x.ctypes.data, C.c_float(y), out.ctypes.data,
+                                                          x.size))
+        return out
+
     def profile(self) -> dict:
         """{phase: (wave executions, active lanes)} from an IPT_PROF build."""
         n = 2 * len(PROFILE_PHASES) + 12
@@ -372,6 +418,17 @@ def math_host(fn: int, x: np.ndarray) -> np.ndarray:
     rc = lib.ipt_math_host(fn, x.ctypes.data, out.ctypes.data, x.size)
     if rc != IPT_OK:
         raise IptError(rc, "ipt_math_host")
+    return out
+
+
+def powf_host(x: np.ndarray, y: float) -> np.ndarray:
+    """powf(x, y) by the library's host build of the display kernels' powf_."""
+    lib = load()
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.empty_like(x)
+    rc = lib.ipt_powf_host(x.ctypes.data, C.c_float(y), out.ctypes.data, x.size)
+    if rc != IPT_OK:
+        raise IptError(rc, "ipt_powf_host")
     return out
 
 

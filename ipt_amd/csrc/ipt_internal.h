@@ -14,6 +14,25 @@ hipStream_t ctx_stream(ipt_ctx* ctx);
 int ctx_device(ipt_ctx* ctx);
 int ctx_cus(ipt_ctx* ctx);
 
+// The display pipeline's scratch (ipt_post.hip), owned by the context: grows to
+// the largest image seen, freed by ipt_destroy. `done` is recorded on the
+// caller's stream after each ipt_display_device; the context's drain waits
+// for it (ipt_render_wait, ipt_upload_scene, ipt_destroy).
+struct PostScratch {
+    void* bright = nullptr;        // bright-pixel records, one per pixel at most
+    unsigned int* blocks = nullptr;  // per-block bright counts, then their exclusive scan
+    void* scalars = nullptr;       // bright count, image max key, tone min / max
+    float* processed = nullptr;    // glare output when the caller passes none
+    float* tone = nullptr;         // tone-mapped image when the caller passes none
+    size_t bright_cap = 0, blocks_cap = 0, processed_cap = 0, tone_cap = 0;
+    hipEvent_t done = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool used = false;
+};
+PostScratch& ctx_post(ipt_ctx* ctx);
+int post_wait(ipt_ctx* ctx);     // waits for the queued display work (0 or IPT_E_DEVICE)
+void post_release(ipt_ctx* ctx);  // frees the scratch (after post_wait)
+
 // Owning device allocation: a call's temporaries are freed on every return
 // path, early error returns included; release() hands the pointer over.
 template <class T>

@@ -3045,6 +3045,7 @@ struct ipt_ctx {
     int blocks_per_cu = 0;      // of the last path-kernel launch
     bool lattice_lds = true;    // IPT_LATTICE_LDS=0: the lattice instances with global records (tests)
     size_t max_lds = 160 * 1024;  // the device's LDS per workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock)
+    ipt_internal::PostScratch post;  // ipt_display_device's scratch and completion event (ipt_post.hip)
 };
 
 namespace {
@@ -3212,6 +3213,7 @@ int drain(ipt_ctx* ctx) {
         if (S.used && S.done && hipEventSynchronize(S.done) != hipSuccess) rc = fail(ctx, IPT_E_DEVICE, "slot readers failed");
         S.idle = true;  // (synchronous calls therefore queue no stream value waits)
     }
+    if (const int r = ipt_internal::post_wait(ctx)) rc = r;  // queued ipt_display_device work
     while (!ctx->pending.empty()) {
         const int r = settle_oldest(ctx);
         if (r && !rc) rc = r;
@@ -3670,6 +3672,7 @@ int ctx_fail(ipt_ctx* ctx, int code, const std::string& msg) { return fail(ctx, 
 hipStream_t ctx_stream(ipt_ctx* ctx) { return ctx->stream; }
 int ctx_device(ipt_ctx* ctx) { return ctx->device; }
 int ctx_cus(ipt_ctx* ctx) { return ctx->n_cu; }
+PostScratch& ctx_post(ipt_ctx* ctx) { return ctx->post; }
 }  // namespace ipt_internal
 
 extern "C" {
@@ -3795,6 +3798,7 @@ void ipt_destroy(ipt_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     (void)drain(ctx);  // nothing queued may still use the buffers
+    ipt_internal::post_release(ctx);
     void* bufs[] = {ctx->d_cdf_lo, ctx->d_lgrid, ctx->d_lax, ctx->d_bvh_nodes, ctx->d_bvh_prims, ctx->d_light_nodes, ctx->d_lights, ctx->d_weights, ctx->d_cdf, ctx->d_wall, ctx->d_spheres,
                     ctx->d_counters, ctx->d_cos_a, ctx->d_cos_b, ctx->d_clk,
                     ctx->d_grid_start, ctx->d_grid_items, ctx->d_grid_c4, ctx->d_grid_cells, ctx->d_frame_sc,

@@ -21,6 +21,8 @@
 //                 only its rounding to float is used by the reference
 //                 (libddf/ddf_detail.h:82) and that rounding is verified equal
 //                 to glibc's for every float input in tests/.
+//      powf  -> ARM optimized-routines powf (__powf_fma), for the display
+//                 chain's gamma only (powf_ below; tests/test_display_cpu.py)
 //    Constants were read from the image's libm.so.6 .rodata and the operation
 //    graphs from its disassembly; tests/test_math_exhaustive.py checks every
 //    float input of each function's reachable domain against the host libm.
@@ -479,6 +481,105 @@ IPT_HD float acos_f64_to_f32(float xf) {
 #else
     return acos_f64_to_f32_exact(xf);
 #endif
+}
+
+// ------------------------------------------------------------------ powf
+// ARM optimized-routines powf as built into glibc 2.35
+// (sysdeps/ieee754/flt-32/e_powf.c, powf_log2_data.c, exp2f_data.c) in its FMA
+// ifunc variant __powf_fma: log2(x) by a 16-entry table and a degree-5
+// polynomial, y*log2(x) in double, 2^that by a 32-entry table and a cubic.
+// Tables read from libm .rodata (__powf_log2_data 0xb2f20: {invc, logc}[16]
+// then poly[5]; __exp2f_data 0xb2b80: tab[32], shift 0x1.8p+47, poly[3]); the
+// disassembly (0x7aef0) contracts EVERY multiply-add of the source into an
+// FMA, r = z*invc - 1 included.
+//
+// Scope (the display chain's gamma, x/max in [0,1] with y = 1/2.2 or 0.6):
+// y must be finite, > 0 and not an integer; ipt_powf_* reject other y. For
+// such y the result equals libm's bit for bit on every x >= 0, +-0, +-inf and
+// NaN (x*x there: 0, +inf, the quieted NaN). The rare path is simplified:
+// glibc's (x-x)/(x-x) for finite x < 0 is stated as the x86 default NaN
+// 0xffc00000 (the device's 0/0 has the other sign), and the over/underflow
+// exits return +inf / +0 without raising exceptions.
+IPT_HD float powf_(float x, float y) {
+    const uint64_t log2_tab[16][2] = {
+        {0x3ff661ec79f8f3beull, 0xbfdefec65b963019ull}, {0x3ff571ed4aaf883dull, 0xbfdb0b6832d4fca4ull},
+        {0x3ff49539f0f010b0ull, 0xbfd7418b0a1fb77bull}, {0x3ff3c995b0b80385ull, 0xbfd39de91a6dcf7bull},
+        {0x3ff30d190c8864a5ull, 0xbfd01d9bf3f2b631ull}, {0x3ff25e227b0b8ea0ull, 0xbfc97c1d1b3b7af0ull},
+        {0x3ff1bb4a4a1a343full, 0xbfc2f9e393af3c9full}, {0x3ff12358f08ae5baull, 0xbfb960cbbf788d5cull},
+        {0x3ff0953f419900a7ull, 0xbfaa6f9db6475fceull}, {0x3ff0000000000000ull, 0x0000000000000000ull},
+        {0x3fee608cfd9a47acull, 0x3fb338ca9f24f53dull}, {0x3feca4b31f026aa0ull, 0x3fc476a9543891baull},
+        {0x3feb2036576afce6ull, 0x3fce840b4ac4e4d2ull}, {0x3fe9c2d163a1aa2dull, 0x3fd40645f0c6651cull},
+        {0x3fe886e6037841edull, 0x3fd88e9c2c1b9ff8ull}, {0x3fe767dcf5534862ull, 0x3fdce0a44eb17bccull}};
+    const uint64_t exp2_tab[32] = {
+        0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
+        0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull,
+        0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull,
+        0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull,
+        0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
+        0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull,
+        0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
+        0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+    const double A0 = u2d(0x3fd27616c9496e0bull), A1 = u2d(0xbfd71969a075c67aull), A2 = u2d(0x3fdec70a6ca7baddull),
+                 A3 = u2d(0xbfe7154748bef6c8ull), A4 = u2d(0x3ff71547652ab82bull);
+    const double C0 = u2d(0x3fac6af84b912394ull), C1 = u2d(0x3fcebfce50fac4f3ull), C2 = u2d(0x3fe62e42ff0c52d6ull);
+    const double shift = u2d(0x42e8000000000000ull);  // 0x1.8p+47 = 0x1.8p52 / 32
+    uint32_t ix = f2u(x);
+    if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {  // x < 2^-126, inf or NaN
+        const uint32_t ax = ix & 0x7fffffffu;
+        if (ax == 0) return 0.0f;                          // x*x
+        if (ax == 0x7f800000u) return inf_();              // x*x
+        if (ax > 0x7f800000u) return u2f(ix | 0x00400000u);  // x*x of a NaN: quieted, sign and payload kept
+        if (ix & 0x80000000u) return u2f(0xffc00000u);     // __math_invalidf
+        ix = f2u(x * 8388608.0f) & 0x7fffffffu;            // subnormal: scale by 2^23
+        ix -= 23u << 23;
+    }
+    // log2_inline
+    const uint32_t tmp = ix - 0x3f330000u;
+    const int i = (int)((tmp >> 19) & 15u);
+    const uint32_t top = tmp & 0xff800000u;
+    const uint32_t iz = ix - top;
+    const int k = (int32_t)top >> 23;
+    const double invc = u2d(log2_tab[i][0]), logc = u2d(log2_tab[i][1]);
+    const double z = (double)u2f(iz);
+    const double r = fma_(z, invc, -1.0);
+    const double y0 = logc + (double)k;
+    const double r2 = r * r;
+    const double py = fma_(A0, r, A1);
+    const double pp = fma_(A2, r, A3);
+    const double r4 = r2 * r2;
+    double q = fma_(A4, r, y0);
+    q = fma_(pp, r2, q);
+    const double logx = fma_(py, r4, q);
+    const double ylogx = (double)y * logx;
+    if (((d2u(ylogx) >> 47) & 0xffffu) >= 0x80bfu) {  // |y log2 x| >= 126
+        if (ylogx > u2d(0x405fffffffd1d571ull)) return inf_();  // __math_oflowf
+        if (ylogx <= -150.0) return 0.0f;                       // __math_uflowf
+    }
+    // exp2_inline
+    double kd = ylogx + shift;
+    const uint64_t ki = d2u(kd);
+    kd = kd - shift;
+    const double rr = ylogx - kd;
+    const uint64_t t = exp2_tab[ki & 31u] + (ki << 47);
+    const double s = u2d(t);
+    const double zz = fma_(C0, rr, C1);
+    const double rr2 = rr * rr;
+    double e = fma_(C2, rr, 1.0);
+    e = fma_(zz, rr2, e);
+    return (float)(e * s);
+}
+
+// a / b with the NaN results of the x86 host the reference runs on stated
+// explicitly (the device's division picks another operand's payload and the
+// other sign for an invalid quotient): a NaN operand comes back quieted, the
+// dividend's first (divss returns its first source); 0/0 and inf/inf give the
+// default NaN 0xffc00000. Every other quotient is the IEEE one.
+IPT_HD float div_x86nan_(float a, float b) {
+    const uint32_t ua = f2u(a) & 0x7fffffffu, ub = f2u(b) & 0x7fffffffu;
+    if (ua > 0x7f800000u) return u2f(f2u(a) | 0x00400000u);
+    if (ub > 0x7f800000u) return u2f(f2u(b) | 0x00400000u);
+    if ((ua == 0 && ub == 0) || (ua == 0x7f800000u && ub == 0x7f800000u)) return u2f(0xffc00000u);
+    return a / b;
 }
 
 // --------------------------------------------------- mixed-precision helpers

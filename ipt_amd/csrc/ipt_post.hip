@@ -24,7 +24,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/ipt_capi.h"
@@ -72,10 +74,13 @@ struct Bright {
 
 constexpr int kGlareChunk = 512;
 
+// nb_dev non-NULL: the bright count is read there (ipt_display_device: it
+// never leaves the device, and the grid does not depend on it)
 __global__ __launch_bounds__(kPostBlock) void glare_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                            int W, int H, const Bright* __restrict__ bright, int nb,
-                                                           float cutoff) {
+                                                           float cutoff, const unsigned int* __restrict__ nb_dev) {
     __shared__ Bright tile[kGlareChunk];
+    if (nb_dev) nb = (int)*nb_dev;
     const int x = blockIdx.x * kPostBlock + threadIdx.x, y = blockIdx.y;
     const bool live = x < W;
     float v = live ? in[(size_t)y * W + x] : 0.0f;
@@ -97,14 +102,272 @@ __global__ __launch_bounds__(kPostBlock) void glare_kernel(const float* __restri
     if (live) out[(size_t)y * W + x] = v < 0.0f ? 0.0f : (v > cutoff ? cutoff : v);  // cimg::cut
 }
 
+// ---------------------------------------------------------------- display
+// ipt_display_device: glare -> tone map -> 8-bit without a value crossing to
+// the host. Kernels in stream order; the launch boundary is the only
+// synchronisation between workgroups, and every cross-workgroup combination
+// is an integer max, so the result does not depend on dispatch order.
+//
+// Bright-pixel compaction (raster order, as the glare sums need): a block owns
+// kCompactSpan consecutive pixels. bright_count_kernel writes each block's
+// count, bright_scan_kernel (one workgroup) turns the counts into exclusive
+// offsets and leaves the total in DisplayScalars::nb, bright_scatter_kernel
+// recomputes the flags and places each record at offset + the pixels before it
+// in the block (wave ballot + the earlier waves' counts through LDS).
+//
+// Folds: the reference's `mx = max(mx, v)` from element 0 keeps the FIRST
+// maximum and skips NaN unless element 0 is one. The image max is therefore
+// an atomicMax over 64-bit keys {value key, ~index}: the value key orders all
+// floats (negative ones reversed, -0 == +0), the index part prefers the
+// earliest element among equals (only +-0 differ in bits), NaN gives key 0;
+// "element 0 is NaN" is read from element 0 itself. tone is >= +0 or NaN, so
+// its min and max are integer folds of the bit patterns (min as max of ~bits,
+// so one memset to 0 initialises every scalar).
+constexpr int kCompactRounds = 4;
+constexpr int kCompactSpan = kPostBlock * kCompactRounds;
+constexpr int kPostWaves = kPostBlock / 64;
+
+struct DisplayScalars {
+    unsigned long long max_key;
+    unsigned int nb;
+    unsigned int tone_max;      // bits of max(tone)
+    unsigned int tone_min_inv;  // ~bits of min(tone)
+    unsigned int pad;
+};
+
+__device__ __forceinline__ bool is_nan_(float v) { return (f2u(v) & 0x7fffffffu) > 0x7f800000u; }
+
+__global__ __launch_bounds__(kPostBlock) void bright_count_kernel(const float* __restrict__ in, long long n,
+                                                                  float cutoff, unsigned int* __restrict__ counts) {
+    __shared__ unsigned int total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * kCompactSpan;
+    unsigned int c = 0;
+    for (int r = 0; r < kCompactRounds; ++r) {
+        const long long i = base + r * kPostBlock + threadIdx.x;
+        const bool b = i < n && !(in[i] <= cutoff);
+        c += (unsigned int)__popcll(__ballot(b));
+    }
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&total, c);
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// one workgroup: counts[0..nblk) -> exclusive offsets in place, total -> sc->nb
+__global__ __launch_bounds__(kPostBlock) void bright_scan_kernel(unsigned int* __restrict__ counts, int nblk,
+                                                                 DisplayScalars* __restrict__ sc) {
+    __shared__ unsigned int part[kPostBlock];
+    const int per = (nblk + kPostBlock - 1) / kPostBlock;
+    const int lo = min((int)threadIdx.x * per, nblk), hi = min(lo + per, nblk);
+    unsigned int s = 0;
+    for (int i = lo; i < hi; ++i) s += counts[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned int acc = 0;
+        for (int t = 0; t < kPostBlock; ++t) {
+            const unsigned int v = part[t];
+            part[t] = acc;
+            acc += v;
+        }
+        sc->nb = acc;
+    }
+    __syncthreads();
+    unsigned int off = part[threadIdx.x];
+    for (int i = lo; i < hi; ++i) {
+        const unsigned int v = counts[i];
+        counts[i] = off;
+        off += v;
+    }
+}
+
+__global__ __launch_bounds__(kPostBlock) void bright_scatter_kernel(const float* __restrict__ in, int W, long long n,
+                                                                    float cutoff,
+                                                                    const unsigned int* __restrict__ offsets,
+                                                                    Bright* __restrict__ bright) {
+    __shared__ unsigned int wave_cnt[kPostWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long base = (long long)blockIdx.x * kCompactSpan;
+    unsigned int run = offsets[blockIdx.x];
+    for (int r = 0; r < kCompactRounds; ++r) {
+        const long long i = base + r * kPostBlock + threadIdx.x;
+        const float val = i < n ? in[i] : 0.0f;
+        const bool b = i < n && !(val <= cutoff);  // gui.cpp:40-47; NaN is bright
+        const unsigned long long mask = __ballot(b);
+        if (lane == 0) wave_cnt[wave] = (unsigned int)__popcll(mask);
+        __syncthreads();
+        unsigned int before = 0, all = 0;
+        for (int w = 0; w < kPostWaves; ++w) {
+            const unsigned int c = wave_cnt[w];
+            before += w < wave ? c : 0u;
+            all += c;
+        }
+        if (b) {
+            const unsigned int dst = run + before + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
+            const float coef = (float)(0.1 * (double)val / (double)cutoff);
+            if ((long long)dst < n) bright[dst] = Bright{(int)(i % W), (int)(i / W), cutoff * coef, 0};
+        }
+        run += all;
+        __syncthreads();  // wave_cnt is rewritten next round
+    }
+}
+
+// value key of a non-NaN float: unsigned order == float order, -0 == +0
+__device__ __forceinline__ unsigned long long max_key_(float v, unsigned int idx) {
+    unsigned int u = f2u(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0ull;
+    if (u == 0x80000000u) u = 0u;
+    const unsigned int k = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)k << 32) | (unsigned long long)(0xffffffffu - idx);
+}
+
+// v[0..3] = p[i..i+3] (0 past n): one 16-byte load where the array's alignment allows
+__device__ __forceinline__ void load4_(const float* __restrict__ p, long long i, long long n, bool vec, float* v) {
+    if (vec && i + 3 < n) {
+        const float4 q = *reinterpret_cast<const float4*>(p + i);
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
+        for (int j = 0; j < 4; ++j) v[j] = i + j < n ? p[i + j] : 0.0f;
+    }
+}
+
+// max over the workgroup, valid in thread 0
+template <class T>
+__device__ __forceinline__ T block_max_(T m, T* red) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const T other = __shfl_xor(m, o);
+        m = other > m ? other : m;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    T b = red[0];
+    for (int w = 1; w < kPostWaves; ++w) b = red[w] > b ? red[w] : b;
+    __syncthreads();
+    return b;
+}
+
+__global__ __launch_bounds__(kPostBlock) void image_max_kernel(const float* __restrict__ in, long long n,
+                                                               DisplayScalars* __restrict__ sc) {
+    __shared__ unsigned long long red[kPostWaves];
+    const long long i = ((long long)blockIdx.x * kPostBlock + threadIdx.x) * 4;
+    float v[4];
+    load4_(in, i, n, ((uintptr_t)in & 15u) == 0, v);
+    unsigned long long m = 0ull;
+    for (int j = 0; j < 4; ++j)
+        if (i + j < n) {
+            const unsigned long long k = max_key_(v[j], (unsigned int)(i + j));
+            m = k > m ? k : m;
+        }
+    m = block_max_(m, red);
+    if (threadIdx.x == 0 && m) atomicMax(&sc->max_key, m);
+}
+
+// tone_map (ipt_host.cpp): v / mx, powf(., p), cut to [0,1] (NaN passes)
+__global__ __launch_bounds__(kPostBlock) void tone_kernel(const float* __restrict__ in, float* __restrict__ tone,
+                                                          long long n, float p, DisplayScalars* __restrict__ sc) {
+    __shared__ unsigned int red[kPostWaves];
+    const unsigned long long key = sc->max_key;
+    const float first = in[0];
+    const float mx = (is_nan_(first) || !key) ? first : in[0xffffffffu - (unsigned int)key];
+    const long long i = ((long long)blockIdx.x * kPostBlock + threadIdx.x) * 4;
+    float v[4];
+    load4_(in, i, n, ((uintptr_t)in & 15u) == 0, v);
+    unsigned int hi = 0u, lo_inv = 0u;
+    for (int j = 0; j < 4; ++j) {
+        const float w = powf_(div_x86nan_(v[j], mx), p);
+        v[j] = w < 0.0f ? 0.0f : (w > 1.0f ? 1.0f : w);
+        if (i + j < n && !is_nan_(v[j])) {
+            hi = max(hi, f2u(v[j]));
+            lo_inv = max(lo_inv, ~f2u(v[j]));
+        }
+    }
+    if (((uintptr_t)tone & 15u) == 0 && i + 3 < n) {
+        *reinterpret_cast<float4*>(tone + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int j = 0; j < 4; ++j)
+            if (i + j < n) tone[i + j] = v[j];
+    }
+    hi = block_max_(hi, red);
+    lo_inv = block_max_(lo_inv, red);
+    if (threadIdx.x == 0) {
+        if (hi) atomicMax(&sc->tone_max, hi);
+        if (lo_inv) atomicMax(&sc->tone_min_inv, lo_inv);
+    }
+}
+
+// to_gray8 (ipt_host.cpp): CImg normalize(0, 255) and the unsigned char cast
+__global__ __launch_bounds__(kPostBlock) void gray8_kernel(const float* __restrict__ tone, uint8_t* __restrict__ out,
+                                                           long long n, const DisplayScalars* __restrict__ sc) {
+    const float t0 = tone[0];
+    const bool nan0 = is_nan_(t0);  // the folds start at element 0: NaN there stays
+    const float m = nan0 ? t0 : u2f(~sc->tone_min_inv), M = nan0 ? t0 : u2f(sc->tone_max);
+    const long long i = ((long long)blockIdx.x * kPostBlock + threadIdx.x) * 4;
+    float v[4];
+    load4_(tone, i, n, ((uintptr_t)tone & 15u) == 0, v);
+    uint8_t b[4];
+    for (int j = 0; j < 4; ++j) {
+        float t = v[j];
+        if (m != M && (m != 0.0f || M != 255.0f))
+            t = (t - m) / (M - m) * 255.0f + 0.0f;
+        else if (m == M)
+            t = 0.0f;
+        b[j] = is_nan_(t) ? (uint8_t)0 : (uint8_t)t;
+    }
+    if (((uintptr_t)out & 3u) == 0 && i + 3 < n) {
+        *reinterpret_cast<uchar4*>(out + i) = make_uchar4(b[0], b[1], b[2], b[3]);
+    } else {
+        for (int j = 0; j < 4; ++j)
+            if (i + j < n) out[i + j] = b[j];
+    }
+}
+
+__global__ __launch_bounds__(kPostBlock) void powf_kernel(const float* __restrict__ x, float y, float* __restrict__ out,
+                                                          long long n) {
+    const long long i = (long long)blockIdx.x * kPostBlock + threadIdx.x;
+    if (i < n) out[i] = powf_(x[i], y);
+}
+
+// powf_'s stated domain for y (ipt_math.h)
+bool powf_y_ok(float y) { return isfinite_(y) && y > 0.0f && y != std::trunc(y); }
+
 using ipt_internal::DevBuf;
 
-#define POSTCHECK(ctx, expr)                                                                             \
+#define POSTCHECK(ctx, expr)                                                                            \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
         if (e_ != hipSuccess)                                                                            \
             return ipt_internal::ctx_fail(ctx, IPT_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+// (Re)allocates one of the context's display scratch buffers: the old one is
+// dropped first, and a failure leaves a null pointer with capacity 0.
+template <class T>
+int post_grow(ipt_ctx* ctx, T*& ptr, size_t& cap, size_t count, size_t elem_bytes) {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, count * elem_bytes);
+    if (e != hipSuccess)
+        return ipt_internal::ctx_fail(ctx, e == hipErrorOutOfMemory ? IPT_E_OOM : IPT_E_DEVICE,
+                                      std::string("display scratch: ") + hipGetErrorString(e));
+    ptr = static_cast<T*>(q);
+    cap = count;
+    return IPT_OK;
+}
+
+// the argument rules of ipt_display / ipt_display_device (ipt_capi.h)
+int display_check(ipt_ctx* ctx, const ipt_display_params* p, const float* pixels, const uint8_t* gray8) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!p || !pixels || !gray8 || p->width <= 0 || p->height <= 0 || !(p->glare_cutoff >= 0.0f))
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_display: bad arguments");
+    if (p->glare_cutoff > 0.0f && (p->width > 4096 || p->height > 4096))  // ipt_glare's limit (the hypot equivalence)
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_display: glare on images up to 4096 x 4096");
+    if ((long long)p->width * p->height > (1ll << 31) || p->flags != 0 || !isfinite_(p->glare_cutoff))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_display: at most 2^31 pixels, finite cutoff, flags 0");
+    return IPT_OK;
+}
 
 }  // namespace
 
@@ -169,7 +432,126 @@ int ipt_glare(ipt_ctx* ctx, const float* in, float* out, int width, int height, 
         POSTCHECK(ctx, hipMemcpyAsync(db.p, b.data(), b.size() * sizeof(Bright), hipMemcpyHostToDevice, st));
     dim3 grid((width + kPostBlock - 1) / kPostBlock, height);
     hipLaunchKernelGGL(glare_kernel, grid, dim3(kPostBlock), 0, st, din.p, dout.p, width, height, db.p, (int)b.size(),
-                       cutoff);
+                       cutoff, (const unsigned int*)nullptr);
+    POSTCHECK(ctx, hipGetLastError());
+    POSTCHECK(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    POSTCHECK(ctx, hipStreamSynchronize(st));
+    return IPT_OK;
+}
+
+int ipt_display_device(ipt_ctx* ctx, const ipt_display_params* p, const float* dev_pixels, float* dev_processed,
+                       float* dev_tone, uint8_t* dev_gray8, void* hip_stream) {
+    if (const int rc = display_check(ctx, p, dev_pixels, dev_gray8)) return rc;
+    const bool glare = p->glare_cutoff > 0.0f;
+    const long long n = (long long)p->width * p->height;
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    const size_t nblk = (size_t)((n + kCompactSpan - 1) / kCompactSpan);
+    const size_t need_bright = glare ? (size_t)n : 0, need_blocks = glare ? nblk : 0;
+    const size_t need_processed = glare && !dev_processed ? (size_t)n : 0, need_tone = dev_tone ? 0 : (size_t)n;
+    if (!S.done || !S.scalars || need_bright > S.bright_cap || need_blocks > S.blocks_cap ||
+        need_processed > S.processed_cap || need_tone > S.tone_cap) {
+        // (first call or a larger image: the only path that allocates or waits)
+        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
+        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+        size_t one = 0;
+        if (!S.scalars)
+            if (const int rc = post_grow(ctx, S.scalars, one, 1, sizeof(DisplayScalars))) return rc;
+        if (need_bright > S.bright_cap)
+            if (const int rc = post_grow(ctx, S.bright, S.bright_cap, need_bright, sizeof(Bright))) return rc;
+        if (need_blocks > S.blocks_cap)
+            if (const int rc = post_grow(ctx, S.blocks, S.blocks_cap, need_blocks, sizeof(unsigned int))) return rc;
+        if (need_processed > S.processed_cap)
+            if (const int rc = post_grow(ctx, S.processed, S.processed_cap, need_processed, sizeof(float))) return rc;
+        if (need_tone > S.tone_cap)
+            if (const int rc = post_grow(ctx, S.tone, S.tone_cap, need_tone, sizeof(float))) return rc;
+    }
+    // the scratch is shared: a call on another stream runs after the previous one
+    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
+    DisplayScalars* sc = static_cast<DisplayScalars*>(S.scalars);
+    POSTCHECK(ctx, hipMemsetAsync(sc, 0, sizeof(DisplayScalars), st));
+    const float* processed = dev_pixels;
+    if (glare) {
+        Bright* bright = static_cast<Bright*>(S.bright);
+        float* out = dev_processed ? dev_processed : S.processed;
+        const float cutoff = p->glare_cutoff;
+        hipLaunchKernelGGL(bright_count_kernel, dim3((unsigned)nblk), dim3(kPostBlock), 0, st, dev_pixels, n, cutoff,
+                           S.blocks);
+        hipLaunchKernelGGL(bright_scan_kernel, dim3(1), dim3(kPostBlock), 0, st, S.blocks, (int)nblk, sc);
+        hipLaunchKernelGGL(bright_scatter_kernel, dim3((unsigned)nblk), dim3(kPostBlock), 0, st, dev_pixels, p->width, n,
+                           cutoff, (const unsigned int*)S.blocks, bright);
+        dim3 grid((p->width + kPostBlock - 1) / kPostBlock, p->height);
+        hipLaunchKernelGGL(glare_kernel, grid, dim3(kPostBlock), 0, st, dev_pixels, out, p->width, p->height,
+                           (const Bright*)bright, 0, cutoff, (const unsigned int*)&sc->nb);
+        processed = out;
+    } else if (dev_processed) {
+        POSTCHECK(ctx, hipMemcpyAsync(dev_processed, dev_pixels, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    float* tone = dev_tone ? dev_tone : S.tone;
+    const unsigned int quads = (unsigned int)((n + 4ll * kPostBlock - 1) / (4ll * kPostBlock));
+    const float inv_gamma = 2.2f;
+    const float gamma = (float)(double)(1.0f / inv_gamma);  // tone_map's exponent (gui.cpp:11-16)
+    hipLaunchKernelGGL(image_max_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, n, sc);
+    hipLaunchKernelGGL(tone_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, tone, n, gamma, sc);
+    hipLaunchKernelGGL(gray8_kernel, dim3(quads), dim3(kPostBlock), 0, st, (const float*)tone, dev_gray8, n,
+                       (const DisplayScalars*)sc);
+    POSTCHECK(ctx, hipGetLastError());
+    POSTCHECK(ctx, hipEventRecord(S.done, st));
+    S.used = true;
+    S.last_stream = st;
+    return IPT_OK;
+}
+
+int ipt_display(ipt_ctx* ctx, const ipt_display_params* p, const float* pixels, float* processed, float* tone,
+                uint8_t* gray8) {
+    if (const int rc = display_check(ctx, p, pixels, gray8)) return rc;
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = ipt_internal::ctx_stream(ctx);
+    const size_t n = (size_t)p->width * p->height;
+    DevBuf<float> din, dproc, dtone;
+    DevBuf<uint8_t> dgray;
+    POSTCHECK(ctx, hipMalloc(&din.p, n * sizeof(float)));
+    POSTCHECK(ctx, hipMalloc(&dgray.p, n));
+    if (processed) POSTCHECK(ctx, hipMalloc(&dproc.p, n * sizeof(float)));
+    if (tone) POSTCHECK(ctx, hipMalloc(&dtone.p, n * sizeof(float)));
+    POSTCHECK(ctx, hipMemcpyAsync(din.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (const int rc = ipt_display_device(ctx, p, din.p, dproc.p, dtone.p, dgray.p, st)) return rc;
+    if (processed) POSTCHECK(ctx, hipMemcpyAsync(processed, dproc.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (tone) POSTCHECK(ctx, hipMemcpyAsync(tone, dtone.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    POSTCHECK(ctx, hipMemcpyAsync(gray8, dgray.p, n, hipMemcpyDeviceToHost, st));
+    POSTCHECK(ctx, hipStreamSynchronize(st));
+    return IPT_OK;
+}
+
+int ipt_powf_host(const float* x, float y, float* out, int64_t n) {
+    if (!x || !out || n < 0) return IPT_E_INVALID;
+    if (!powf_y_ok(y)) return IPT_E_UNSUPPORTED;
+    const int nt = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t)
+        th.emplace_back([=]() {
+            const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
+            for (int64_t i = lo; i < hi; ++i) out[i] = powf_(x[i], y);
+        });
+    for (auto& t : th) t.join();
+    return IPT_OK;
+}
+
+int ipt_powf_device(ipt_ctx* ctx, const float* x, float y, float* out, int64_t n) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!x || !out || n < 0) return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_powf_device: bad arguments");
+    if (!powf_y_ok(y))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_powf_device: y must be finite, > 0 and no integer");
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = ipt_internal::ctx_stream(ctx);
+    DevBuf<float> din, dout;
+    POSTCHECK(ctx, hipMalloc(&din.p, std::max<int64_t>(n, 1) * sizeof(float)));
+    POSTCHECK(ctx, hipMalloc(&dout.p, std::max<int64_t>(n, 1) * sizeof(float)));
+    POSTCHECK(ctx, hipMemcpyAsync(din.p, x, n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (n > 0)
+        hipLaunchKernelGGL(powf_kernel, dim3((unsigned)((n + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0, st,
+                           (const float*)din.p, y, dout.p, (long long)n);
     POSTCHECK(ctx, hipGetLastError());
     POSTCHECK(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
     POSTCHECK(ctx, hipStreamSynchronize(st));
@@ -177,3 +559,22 @@ int ipt_glare(ipt_ctx* ctx, const float* in, float* out, int width, int height, 
 }
 
 }  // extern "C"
+
+namespace ipt_internal {
+int post_wait(ipt_ctx* ctx) {
+    PostScratch& S = ctx_post(ctx);
+    if (!S.used) return IPT_OK;
+    S.used = false;
+    const hipError_t e = hipEventSynchronize(S.done);
+    if (e != hipSuccess) return ctx_fail(ctx, IPT_E_DEVICE, std::string("display work failed: ") + hipGetErrorString(e));
+    return IPT_OK;
+}
+
+void post_release(ipt_ctx* ctx) {
+    PostScratch& S = ctx_post(ctx);
+    for (void* b : {S.bright, (void*)S.blocks, S.scalars, (void*)S.processed, (void*)S.tone})
+        if (b) (void)hipFree(b);
+    if (S.done) (void)hipEventDestroy(S.done);
+    S = PostScratch{};
+}
+}  // namespace ipt_internal

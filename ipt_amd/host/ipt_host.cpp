@@ -454,6 +454,17 @@ std::vector<float> GpuRenderer::glare(const GridRenderPlane& plane, float cutoff
     return out;
 }
 
+std::vector<uint8_t> GpuRenderer::display(const GridRenderPlane& plane, float glare_cutoff) {
+    check_plane(plane);
+    ipt_display_params q{};
+    q.width = (int32_t)plane.width;
+    q.height = (int32_t)plane.height;
+    q.glare_cutoff = glare_cutoff;
+    std::vector<uint8_t> out(plane.pixels.size());
+    check(ctx_, ipt_display(ctx_, &q, plane.pixels.data(), nullptr, nullptr, out.data()));
+    return out;
+}
+
 void render_samples_gpu(const Scene& scene, GridRenderPlane& plane, const RenderParams& p, int device) {
     GpuRenderer r(device);
     r.upload(scene);

@@ -211,6 +211,10 @@ class GpuRenderer {
     void computeSmoothedMax(GridRenderPlane& plane, size_t side);
     // Gui's glare bloom (gui.cpp:28-52) of the plane's pixels
     std::vector<float> glare(const GridRenderPlane& plane, float cutoff);
+    // Gui::updateDisplay / Gui::save on the GPU (ipt_display): glare with
+    // glare_cutoff when it is > 0, tone map, normalize(0, 255), 8-bit cast.
+    // With glare_cutoff 0 the bytes equal to_gray8(plane).
+    std::vector<uint8_t> display(const GridRenderPlane& plane, float glare_cutoff = 0.0f);
     ipt_ctx* handle() const { return ctx_; }
 
    private:

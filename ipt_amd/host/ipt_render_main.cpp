@@ -11,7 +11,12 @@
 //              [--devices 0,1,...,7 [--tile-rows 16]]
 //              [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]
 //              [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out glare.pfm]
+//              [--gpu-display]
 //
+// --gpu-display takes the PNG's bytes from GpuRenderer::display (the display
+// pipeline on the GPU, with the --glare cutoff's bloom when one is given, as
+// Gui::updateDisplay shows it) instead of the host's to_gray8; without
+// --glare the file is the same bytes.
 // --smooth applies GridRenderPlane::smooth(SIDE) on the GPU before output;
 // --glare writes Gui's glare bloom of the plane (gui.cpp:28-52, GPU) as PFM;
 // --pgm writes main.cpp's contrast/gamma PGM (main.cpp:297-309).
@@ -38,7 +43,8 @@ namespace {
                  "                  [--n-rays N] [--depth D] [--seed X] [--device I]\n"
                  "                  [--devices I,J,... [--tile-rows 16]]\n"
                  "                  [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]\n"
-                 "                  [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out F.pfm]\n");
+                 "                  [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out F.pfm]\n"
+                 "                  [--gpu-display]\n");
     std::exit(2);
 }
 }  // namespace
@@ -46,6 +52,7 @@ namespace {
 int main(int argc, char** argv) {
     std::string scene_name = "box", out = "result.png", pfm, counts, pgm, glare_out;
     long smooth = 0;
+    bool gpu_display = false;
     double glare = -1.0;
     long width = 640, height = 640, spp = 16, passes = 1, n_rays = 16, depth = 8, device = 0, tile_rows = 16;
     std::vector<int> devices;
@@ -80,6 +87,7 @@ int main(int argc, char** argv) {
         else if (a == "--smooth") smooth = std::atol(val());
         else if (a == "--glare") glare = std::atof(val());
         else if (a == "--glare-out") glare_out = val();
+        else if (a == "--gpu-display") gpu_display = true;
         else usage(("unknown option " + a).c_str());
     }
     if (width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || n_rays < 0 || depth < 0) usage("bad sizes");
@@ -115,7 +123,10 @@ int main(int argc, char** argv) {
             ipt::write_pfm(glare_out, g);
         }
         if (!pgm.empty()) ipt::write_pgm(pgm, plane);
-        if (!out.empty()) ipt::write_png_gray8(out, plane.width, plane.height, ipt::to_gray8(plane));
+        if (!out.empty())
+            ipt::write_png_gray8(out, plane.width, plane.height,
+                                 gpu_display ? gpu.display(plane, glare > 0.0 ? (float)glare : 0.0f)
+                                             : ipt::to_gray8(plane));
         if (!pfm.empty()) ipt::write_pfm(pfm, plane);
         if (!counts.empty()) {
             std::ofstream f(counts, std::ios::binary);
