@@ -2,7 +2,9 @@
 ipt_powf_host) against the host libm powf bit for bit, and the tests' CPU
 reference of the pipeline (tests/display_ref.py) against the host path the
 project already ships (ipt_host.cpp tone_map / to_gray8 through
-tests/native/host_scene_dump.cpp)."""
+tests/native/host_scene_dump.cpp). Also the conditions under which the
+large-shape and denormal inputs of tests/display_cases.py discriminate, which
+the GPU tests rely on."""
 import os
 import struct
 import subprocess
@@ -13,6 +15,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as ge
+import display_cases as dc
 import display_ref as dr
 from ipt_amd import capi
 
@@ -140,3 +143,56 @@ def test_display_ref_folds():
     assert dr.fold_max(np.array([1, nan, 3], np.float32)) == 3 and dr.fold_min(np.array([1, nan, 3], np.float32)) == 1
     z = dr.fold_max(np.array([-1, -0.0, 0.0], np.float32))
     assert z == 0 and np.signbit(z)
+
+
+# ---- the GPU tests' inputs discriminate (tests/display_cases.py) ------------
+def test_scan_geometry_of_the_shapes():
+    """The four compaction shapes reach the scan's branches they are named for."""
+    geo = {(W, H): dc.scan_geometry(W * H) for W, H in dc.SCAN_SHAPES}
+    assert geo[(512, 512)] == (256, 1, 256)   # every scan thread used, the last case before the loop
+    assert geo[(257, 1024)] == (257, 2, 129)  # thread 128 owns one block, threads >= 129 none
+    assert geo[(4096, 65)] == (260, 2, 130)
+    assert geo[(640, 640)] == (400, 2, 200)
+    assert dc.scan_geometry(dc.FAR_W * dc.FAR_H)[:2] == (2048, 8)
+    for W, H in dc.SCAN_SHAPES:
+        n = W * H
+        nblk, per, used = geo[(W, H)]
+        pos = dc.scan_positions(n)
+        assert pos[0] == 0 and pos[-1] == n - 1 and len(pos) <= 40
+        owners = {p // dc.SPAN // per for p in pos}  # scan threads that own a placed pixel
+        assert {0, 1, used // 2, used // 2 + 1, used - 1} <= owners
+
+
+@pytest.mark.parametrize("W,H", dc.SCAN_SHAPES, ids=[f"{W}x{H}" for W, H in dc.SCAN_SHAPES])
+def test_scan_cases_are_unsaturated(oracle, W, H):
+    """300 distinct bright values at the placed positions, and more than half
+    of the reference's processed image below the cutoff (asserted in scan_ref)."""
+    ref = dc.scan_ref(W, H)
+    img, pos = dc.scan_case(W, H)
+    assert np.array_equal(np.flatnonzero(img > dc.SCAN_CUTOFF), pos)
+    assert ref["gray8"].max() == 255 and len(np.unique(ref["gray8"])) > 100
+
+
+@pytest.mark.parametrize("cx,cy", dc.FAR_CORNERS, ids=["top_left", "bottom_right"])
+def test_far_halo_image_discriminates(oracle, cx, cy):
+    """4096 x 512 zeros with one bright corner: the halo with r = sqrtf((float)s)
+    and with r = (float)sqrt((double)s) differ in at least 500 pixels, all of
+    them at s >= 2^24, and the second is the oracle's (float)hypot."""
+    s, near, far = dc.far_models(cx, cy)
+    diff = dr.bits(near) != dr.bits(far)
+    assert int((s >= 1 << 24).sum()) > 5000
+    assert int(diff.sum()) >= 500 and not diff[s < 1 << 24].any()
+    ref = dr.oracle_glare(dc.far_image(cx, cy), dc.FAR_W, dc.FAR_H, dc.FAR_CUTOFF)
+    assert np.array_equal(dr.bits(far), dr.bits(ref))
+    assert np.array_equal(dr.bits(dc.far_ref(cx, cy)["processed"]), dr.bits(ref))
+
+
+@pytest.mark.parametrize("name,W,H,img", dc.denormal_tone_cases(), ids=[c[0] for c in dc.denormal_tone_cases()])
+def test_denormal_tone_cases_are_non_trivial(name, W, H, img):
+    assert img.size == W * H
+    dc.check_denormal_tone_case(name, img, dr.display_ref(img, W, H))
+
+
+def test_stream_cases_are_unsaturated(oracle):
+    for key in ("L", "S"):
+        assert dc.stream_ref(key)["gray8"].max() == 255

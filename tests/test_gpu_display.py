@@ -4,12 +4,14 @@ reference of tests/display_ref.py (oracle glare pinned to the reference's
 gui.cpp, numpy float32 folds, host libm powf). Device buffers are torch
 tensors; every comparison is on bit patterns."""
 import ctypes as C
+import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import __graft_entry__ as ge
+import display_cases as dc
 import display_ref as dr
 from ipt_amd import capi, scenes
 from test_display_cpu import read_png_gray8
@@ -18,6 +20,7 @@ pytestmark = pytest.mark.gpu
 
 ONE = 0x3f800000
 P = float(dr.GAMMA)
+EXHAUSTIVE = os.environ.get("IPT_EXHAUSTIVE") == "1"
 
 
 def run_device(ctx, px, W, H, cutoff=0.0, stream=None, offset=0, want=("processed", "tone")):
@@ -27,7 +30,7 @@ def run_device(ctx, px, W, H, cutoff=0.0, stream=None, offset=0, want=("processe
 
     n = W * H
     src = torch.zeros(n + offset, dtype=torch.float32, device="cuda")
-    src[offset:] = torch.from_numpy(np.ascontiguousarray(px, np.float32).reshape(-1)).cuda()
+    src[offset:] = torch.from_numpy(np.array(px, np.float32).reshape(-1)).cuda()  # (a copy: px may be read-only)
     bufs = {k: torch.full((n + offset,), -7.0, dtype=torch.float32, device="cuda") for k in want}
     g8 = torch.full((n + offset,), 9, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
@@ -48,6 +51,13 @@ def run_device(ctx, px, W, H, cutoff=0.0, stream=None, offset=0, want=("processe
     return out
 
 
+def queue_device(ctx, src, g8, W, H, cutoff, stream):
+    """ipt_display_device on `stream` with NULL processed / tone (the context's
+    scratch carries them); queues only, no synchronisation of any kind."""
+    ctx.display_device(capi.make_display_params(W, H, cutoff), src.data_ptr(), g8.data_ptr(), None, None,
+                       stream.cuda_stream)
+
+
 def assert_same(got, ref, keys=("processed", "tone", "gray8"), tag=None):
     for k in keys:
         a, b = (got[k], ref[k]) if k == "gray8" else (dr.bits(got[k]), dr.bits(ref[k]))
@@ -56,18 +66,43 @@ def assert_same(got, ref, keys=("processed", "tone", "gray8"), tag=None):
 
 
 # ---- 1. powf ---------------------------------------------------------------
-def test_powf_device_equals_host(gpu_ctx):
-    pats = [np.arange(0, ONE + 1, 4093, dtype=np.uint64)]
+def _assert_powf(gpu_ctx, x, y):
+    a, b = dr.bits(gpu_ctx.powf_device(x, y)), dr.bits(capi.powf_host(x, y))
+    bad = a != b
+    assert not bad.any(), (y, dr.bits(x)[bad][:5], a[bad][:5], b[bad][:5])
+
+
+def _powf_sweep(gpu_ctx, stride):
+    """Every stride-th float of [0, 1] in chunks of 2^24 inputs, then the
+    windows around 0, the smallest normal and 1, for y = 1/2.2 and 0.6."""
+    pats = []
     for c in (0, 0x00800000, ONE):
         pats.append(np.arange(max(c - 64, 0), c + 65, dtype=np.uint64))
     pats.append(np.array([0x80000000, 0x7f800000, 0x7fc00000], np.uint64))
-    x = np.concatenate(pats).astype(np.uint32).view(np.float32)
+    edges = np.concatenate(pats).astype(np.uint32).view(np.float32)
+    chunk = (1 << 24) * stride
     for y in (P, 0.6):
-        a, b = dr.bits(gpu_ctx.powf_device(x, y)), dr.bits(capi.powf_host(x, y))
-        bad = a != b
-        assert not bad.any(), (y, dr.bits(x)[bad][:5], a[bad][:5], b[bad][:5])
+        for s in range(0, ONE + 1, chunk):
+            x = np.arange(s, min(ONE + 1, s + chunk), stride, dtype=np.uint64).astype(np.uint32).view(np.float32)
+            _assert_powf(gpu_ctx, x, y)
+        _assert_powf(gpu_ctx, edges, y)
+    return edges
+
+
+def test_powf_device_equals_host(gpu_ctx):
+    """The device's powf_ against the library's host build of the same source
+    (equal to libm on all of [0, 1], tests/test_display_cpu.py): every 61st
+    float of [0, 1], 17.5 M inputs, the sweep of tests/test_math_exhaustive.py."""
+    edges = _powf_sweep(gpu_ctx, 61)
     with pytest.raises(capi.IptError):
-        gpu_ctx.powf_device(x, 2.0)
+        gpu_ctx.powf_device(edges, 2.0)
+
+
+if EXHAUSTIVE:  # IPT_EXHAUSTIVE=1, as in tests/test_math_exhaustive.py
+    @pytest.mark.slow
+    def test_powf_device_equals_host_exhaustive(gpu_ctx):
+        """All 1 065 353 217 floats of [0, 1], both exponents."""
+        _powf_sweep(gpu_ctx, 1)
 
 
 # ---- 2. glare stage against the reference's own gui.cpp glare() ------------
@@ -129,6 +164,33 @@ def test_compaction_edges(gpu_ctx, oracle, name, W, H, img, cutoff):
     assert_same(run_device(gpu_ctx, img, W, H, cutoff), ref, tag=name)
 
 
+@pytest.mark.parametrize("W,H", dc.SCAN_SHAPES, ids=[f"{W}x{H}" for W, H in dc.SCAN_SHAPES])
+def test_compaction_above_256_blocks(gpu_ctx, oracle, W, H):
+    """bright_scan_kernel at and past one block per scan thread (256, 257, 260
+    and 400 blocks): 300 distinct bright values on either side of the scan
+    threads' boundaries, the image unsaturated so that a reordered, dropped or
+    duplicated record changes the float sums (conditions in dc.scan_ref)."""
+    ref = dc.scan_ref(W, H)
+    img, pos = dc.scan_case(W, H)
+    nblk, per, used = dc.scan_geometry(W * H)
+    assert (per == 1 and used == 256) if (W, H) == (512, 512) else (per == 2 and used < 256 and nblk > 256)
+    assert int((img > dc.SCAN_CUTOFF).sum()) == len(pos) == dc.SCAN_BRIGHT
+    assert_same(run_device(gpu_ctx, img, W, H, dc.SCAN_CUTOFF), ref, tag=(W, H))
+    if (W, H) == (640, 640):  # once more through the context's scratch buffers
+        assert_same(run_device(gpu_ctx, img, W, H, dc.SCAN_CUTOFF, want=()), ref, keys=("gray8",), tag="scratch")
+
+
+@pytest.mark.parametrize("cx,cy", dc.FAR_CORNERS, ids=["top_left", "bottom_right"])
+def test_far_halo_display(gpu_ctx, oracle, cx, cy):
+    """glare_kernel's s >= 2^24 branch (the device's f64 root) through
+    ipt_display_device: 4096 x 512 zeros and one bright corner, so that every
+    output pixel is the halo term itself (601 pixels differ between the two
+    radius formulas, tests/test_display_cpu.py). The scan runs at per = 8."""
+    ref = dc.far_ref(cx, cy)
+    assert int(np.count_nonzero(ref["processed"])) == dc.FAR_W * dc.FAR_H
+    assert_same(run_device(gpu_ctx, dc.far_image(cx, cy), dc.FAR_W, dc.FAR_H, dc.FAR_CUTOFF), ref, tag=(cx, cy))
+
+
 # ---- 4. tone and 8-bit, no glare -------------------------------------------
 def _tone_cases():
     rng = np.random.default_rng(23)
@@ -146,12 +208,17 @@ def _tone_cases():
             ("zeros", 64, 48, np.zeros(64 * 48, np.float32)), ("constant", 64, 48, np.full(64 * 48, 0.3, np.float32)),
             ("negative", 64, 48, (-rnd - np.float32(0.5)).astype(np.float32)), ("one_inf", 64, 48, inf1),
             ("mixed_sign", 64, 48, mixed), ("zero_max_sign", 7, 5, zeros_max),
-            ("1x1", 1, 1, small[:1]), ("5x1", 5, 1, small[:5]), ("3x7", 3, 7, small)]
+            ("1x1", 1, 1, small[:1]), ("5x1", 5, 1, small[:5]), ("3x7", 3, 7, small)] + dc.denormal_tone_cases()
+
+
+_DENORMAL_CASES = {c[0] for c in dc.denormal_tone_cases()}
 
 
 @pytest.mark.parametrize("name,W,H,img", _tone_cases(), ids=[c[0] for c in _tone_cases()])
 def test_tone_and_gray8(gpu_ctx, name, W, H, img):
     ref = dr.display_ref(img, W, H)
+    if name in _DENORMAL_CASES:  # subnormal mx, subnormal quotients, a span of a few ulps: stated there
+        dc.check_denormal_tone_case(name, img, ref)
     got = run_device(gpu_ctx, img, W, H)
     assert_same(got, ref, tag=name)
     if name == "zeros":
@@ -210,6 +277,50 @@ def test_stream_order_after_async_render(gpu_ctx):
     plane = B[0].cpu().numpy().reshape(-1)
     assert plane.max() > 0
     assert np.array_equal(got, dr.display_ref(plane, W, H)["gray8"])
+
+
+def test_two_streams_share_the_scratch(oracle):
+    """Two display calls on two streams with no host wait between them: the
+    second must run behind the first (hipStreamWaitEvent on the context's
+    event), because both use the context's scalars, bright list and
+    processed / tone scratch. L (256 x 256, 2000 bright pixels: a glare kernel
+    of 1.3e8 terms) and S (64 x 48, 40 bright) alternate over four pairs, after
+    a warm-up that grows the scratch so that no call takes the allocating path,
+    which waits on the host.
+
+    An ordering test is probabilistic: it cannot prove that the wait is there,
+    it only fails with good likelihood when it is missing (the long call is then
+    still running when the short one rewrites the shared scalars and list)."""
+    import torch
+
+    cases = dc.stream_cases()
+    refs = {k: dc.stream_ref(k) for k in cases}
+    ctx = capi.Context(0)
+    try:
+        src = {k: torch.from_numpy(np.array(img)).cuda() for k, (W, H, img) in cases.items()}
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        (WL, HL, _), out = cases["L"], []
+        warm = torch.zeros(WL * HL, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        queue_device(ctx, src["L"], warm, WL, HL, dc.STREAM_CUTOFF, s1)
+        ctx.wait()
+        for first, second in (("L", "S"), ("S", "L"), ("L", "S"), ("S", "L")):
+            pair = [(key, torch.full((cases[key][0] * cases[key][1],), 9, dtype=torch.uint8, device="cuda"))
+                    for key in (first, second)]
+            torch.cuda.synchronize()
+            for (key, g8), stream in zip(pair, (s1, s2)):
+                W, H, _ = cases[key]
+                queue_device(ctx, src[key], g8, W, H, dc.STREAM_CUTOFF, stream)
+            ctx.wait()
+            torch.cuda.synchronize()
+            out += pair
+        assert np.array_equal(warm.cpu().numpy(), refs["L"]["gray8"])
+        for i, (key, g8) in enumerate(out):
+            got = g8.cpu().numpy()
+            bad = got != refs[key]["gray8"]
+            assert not bad.any(), (i, key, int(bad.sum()), np.flatnonzero(bad)[:5])
+    finally:
+        ctx.close()
 
 
 # ---- 7. host buffers, argument errors --------------------------------------

@@ -12,6 +12,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import display_cases as dc
 import oracle_binding as ob
 from ipt_amd import capi
 
@@ -151,3 +152,77 @@ def test_gpu_glare_matches_oracle(gpu_ctx, oracle):
         ref = oracle_glare(img, W, H, cutoff)
         got = gpu_ctx.glare(img, W, H, float(cutoff))
         assert np.array_equal(_bits(got), _bits(ref)), int((_bits(got) != _bits(ref)).sum())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cx,cy", dc.FAR_CORNERS, ids=["top_left", "bottom_right"])
+def test_gpu_glare_far_halo(gpu_ctx, oracle, cx, cy):
+    """ipt_glare (host bright list) where dx^2 + dy^2 >= 2^24: 4096 x 512 zeros
+    and one bright corner, so every output pixel is the halo term itself and a
+    one-ulp error of r shows (the two radius formulas differ in 601 pixels,
+    tests/test_display_cpu.py::test_far_halo_image_discriminates)."""
+    img = dc.far_image(cx, cy)
+    ref = dc.far_ref(cx, cy)["processed"]  # oracle_glare, computed once
+    got = gpu_ctx.glare(img, dc.FAR_W, dc.FAR_H, dc.FAR_CUTOFF)
+    bad = _bits(got) != _bits(ref)
+    assert not bad.any(), (int(bad.sum()), np.flatnonzero(bad)[:5], _bits(got)[bad][:5], _bits(ref)[bad][:5])
+    assert got[cy * dc.FAR_W + cx] == np.float32(dc.FAR_CUTOFF) and np.count_nonzero(got) == got.size
+
+
+def _smooth_edge_cases():
+    """[(tag, W, H, side, image, expected max bits or None)]"""
+    rng = np.random.default_rng(53)
+    out = []
+    for W, H in ((37, 23), (300, 7)):
+        n, lo, hi = W * H, min(W, H), max(W, H)
+        rnd = (rng.random(n, dtype=np.float32) * 3).astype(np.float32)
+        rnd[rng.random(n) < 0.05] = 0.0
+        # side 0 and a side beyond a dimension run no window: max_value 0, pixels kept.
+        # side == lo is a single row (or column) of windows; on 300 x 7 they span
+        # x = 6..299, across the boundary of the first 256-thread block
+        for side in (0, lo, lo + 1, hi, hi + 1):
+            out.append(("random", W, H, side, rnd, None if side == lo else 0))
+        neg = (-rng.random(n, dtype=np.float32) - np.float32(0.001)).astype(np.float32)
+        neg[rng.random(n) < 0.1] = -0.0
+        allneg0 = np.full(n, -0.0, np.float32)
+        inf1 = rnd.copy()
+        inf1[(H - 2) * W + W // 2] = np.inf
+        nan_one = rnd.copy()
+        nan_one[3 * W + 0] = np.nan       # column 0: inside the first window of side lo alone
+        nan_all = rnd.copy()
+        nan_all[3 * W + lo - 1] = np.nan  # column lo - 1: inside every window of side lo while W <= 2 lo - 1
+        for side in (2, lo):
+            out.append(("negative_and_minus_zero", W, H, side, neg, 0))
+            out.append(("all_minus_zero", W, H, side, allneg0, 0))
+            out.append(("one_inf", W, H, side, inf1, 0x7f800000))
+        out.append(("nan_in_first_window", W, H, lo, nan_one, None))
+        if H == lo and W <= 2 * lo - 1:
+            out.append(("nan_in_every_window", W, H, lo, nan_all, 0))
+    return out
+
+
+@pytest.mark.gpu
+def test_gpu_smooth_edges(gpu_ctx, oracle):
+    """smooth_kernel at side 0, side equal to and beyond the image's dimensions,
+    images without a positive window mean (max_value stays +0), a +inf window
+    and NaN windows, against the oracle: pixels and max_value bit for bit, in
+    place and as computeSmoothedMax."""
+    seen = set()
+    for tag, W, H, side, px, want_max in _smooth_edge_cases():
+        for in_place in (True, False):
+            ref, rmx = oracle_smooth(px, W, H, side, in_place)
+            got, mx = gpu_ctx.smooth(px, W, H, side, in_place)
+            where = (tag, W, H, side, in_place)
+            assert np.array_equal(_bits(got), _bits(ref)), where
+            assert _bits(mx) == _bits(rmx), (where, mx, rmx)
+            if want_max is not None:
+                assert int(_bits(rmx)) == want_max, (where, rmx)
+            if not in_place or side == 0 or side > min(W, H):
+                assert np.array_equal(_bits(ref), _bits(px)), where
+            elif tag == "random":
+                assert rmx > 0 and not np.array_equal(_bits(ref), _bits(px)), where
+            if tag == "nan_in_first_window":
+                assert np.isnan(ref).sum() == (2 if in_place else 1) and rmx > 0, where
+        seen.add(tag)
+    assert seen == {"random", "negative_and_minus_zero", "all_minus_zero", "one_inf", "nan_in_first_window",
+                    "nan_in_every_window"}
