@@ -142,7 +142,15 @@ enum {
    spp_offset continue the same image bit-for-bit. Zero-initialise before the
    first call. `sums` (sequential per-pixel sum in the same order) and
    `pixel_max` (per-pixel running maximum; GridRenderPlane::max_value is its
-   maximum over the frame) may be NULL. */
+   maximum over the frame) may be NULL.
+   A plane that is not zero may be passed in (a saved render, another
+   renderer's plane): any counters, and pixels, sums and pixel_max of any
+   value, infinities and NaNs included, are continued exactly as addRay would.
+   The one limit: a counter must stay below 0xffffffff after the call's
+   samples (one per pixel and pass, two in row 0, plus those that drift in
+   from its neighbours). The reference counts in size_t where this plane
+   counts in uint32_t, so from 0xffffffff on the next mean divides by
+   (float)0 here and by 2^32 there. */
 typedef struct ipt_image {
     float* pixels;
     uint32_t* counters;
