@@ -184,6 +184,8 @@ __device__ __forceinline__ bool longer_sq(float x, float y) {
 }
 __device__ __forceinline__ bool longer(vec3 a, vec3 b) { return longer_sq(dot(a, a), dot(b, b)); }
 
+// a float in LDS: 32-bit addresses and offsets (the stack's level addressing)
+typedef __attribute__((address_space(3))) float lds_float;
 // A uniform value kept in a VGPR (the asm output counts as divergent), so
 // that its uses read it directly instead of from an SGPR spilled to a VGPR
 // lane (v_readlane + hazard nops per use).
@@ -1332,10 +1334,6 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     const int nl = one_light(LMODE) ? 1 : kp.n_lights;  // a compile-time 1 for one light
     const float w_sdf = kp.weights[nl];
     const unsigned long long per_pass = (unsigned long long)kp.n_cand * (unsigned long long)kp.W;
-    // n at every depth is n_rays >> d; when n_rays is a power of two, res/n ==
-    // res * 2^-e exactly (both round the same exact quotient)
-    const bool n_pow2 = kp.n_rays > 0 && (kp.n_rays & (kp.n_rays - 1)) == 0;
-    const int n_log2 = n_pow2 ? 31 - __clz(kp.n_rays) : 0;
 
     // the setup's vector loads (the single light, weights) complete here, so
     // the step loop's waits never drain them (a conservative vmcnt(0) inside
@@ -1450,60 +1448,92 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         // same operations on the same state, nothing changes it in between but
         // the refill of lanes without a path)
         auto pop_node = [&]() {
-        if (active && has_path && !fresh && !((kRes || kResL) && tracing) && ti >= (kp.n_rays >> tdepth)) {
+        // (a lane with a path is active, and a path is fresh only between the
+        // refill and the new-path phase of one step: at the end-of-step pop
+        // neither flag has to be read)
+        if (has_path && (kFramePf == 3 || !fresh) && !((kRes || kResL) && tracing) && ti >= (kp.n_rays >> tdepth)) {
             // the node is done: unwind every suspended level whose node has run
             // all its iterations too (finm, set at push) in one pass -- only
             // their res/multiplier are read -- then resume the first level
             // with iterations left (or store the path's value)
             IPT_PHASE(1);
-            auto fin_v = [&](float r, int d) {
-                float v = 0.0f;
-                if (isfinite_(r))
-                    v = n_pow2 ? r * __builtin_amdgcn_ldexpf(1.0f, -(n_log2 - d)) : r / (float)(kp.n_rays >> d);
-                return v;
-            };
             const uint32_t m = ~finm & ((1u << tdepth) - 1u);
             const int stop = m ? 31 - (int)__clz(m) : -1;
             // every LDS read of the unwind issued before the first use -- the
             // resumed level's six fields and the res/multiplier of the first
             // two finished levels (addresses clamped to level 0 where a level
             // does not exist; those values are not used) -- so that their
-            // latencies overlap instead of forming a chain; the outcomes as
-            // selects so that the loads have unconditional consumers
-            auto lvl = [&](int l) { return stk + (size_t)(l < 0 ? 0 : l) * kStackFields * kBlock + tid; };
-            const float* bs = lvl(stop);
+            // latencies overlap instead of forming a chain; the finished
+            // levels' outcomes as selects so that their loads have
+            // unconditional consumers
+            // (32-bit level offsets: LDS addresses, one v_mad_u32_u24 each)
+            constexpr int kLevelWords = kStackFields * kBlock;
+            const lds_float* sb = (const lds_float*)(stk + tid);
+            auto lvl = [&](int l) { return sb + __umul24((uint32_t)(l < 0 ? 0 : l), (uint32_t)kLevelWords); };
+            const lds_float* bs = lvl(stop);
             const float s0 = bs[0 * kBlock], s1 = bs[1 * kBlock], s2 = bs[2 * kBlock];
             const float s3 = bs[3 * kBlock], s4 = bs[4 * kBlock], s5 = bs[5 * kBlock];
-            const float* b1 = lvl(tdepth - 1);
+            const lds_float* b1 = lvl(tdepth - 1);
             const float r1 = b1[3 * kBlock], m1 = b1[4 * kBlock];
-            const float* b2 = lvl(tdepth - 2);
+            const lds_float* b2 = lvl(tdepth - 2);
             const float r2 = b2[3 * kBlock], m2 = b2[4 * kBlock];
-            auto fin_s = [&](float r, int d) {
-                const float q = n_pow2 ? r * __builtin_amdgcn_ldexpf(1.0f, -(n_log2 - d))
-                                       : r / (float)(kp.n_rays >> (d < 0 ? 0 : d));
-                return isfinite_(r) ? q : 0.0f;
+            // the finished levels' values, one instance of the code per form of
+            // res/n (a wave-uniform choice made once, not once per level).
+            // n at every depth is n_rays >> d; when n_rays is a power of two,
+            // res/n == res * 2^-(log2 n_rays - d) exactly (both round the same
+            // exact quotient), with the factor's bits built directly: level
+            // d's exponent field is 127 - log2 n_rays + d, the next level up
+            // one less -- the very float ldexpf(1, d - log2 n_rays) returns (a
+            // pushed node has n_rays >> d != 0, i.e. d <= log2 n_rays <= 30,
+            // and d >= -2 here: the field stays within 95 .. 127), hence the
+            // same product. The choice and the exponent come from n_rays
+            // inside the step (scalar instructions): as loop invariants they
+            // sat in spilled scalar registers, a v_readlane per use.
+            uint32_t nr = (uint32_t)kp.n_rays;
+            asm volatile("" : "+s"(nr));
+            const bool n_pow2 = nr != 0u && (nr & (nr - 1u)) == 0u;
+            const uint32_t p2_exp = 96u + (uint32_t)__clz((int)nr);  // 127 - log2 n_rays
+            float v;
+            auto unwind = [&](auto p2) {
+                constexpr bool kP2 = decltype(p2)::value;
+                const uint32_t sc0 = (p2_exp + (uint32_t)tdepth) << 23;
+                auto fin_s = [&](float r, int d, uint32_t sc) {
+                    const float q = kP2 ? r * __uint_as_float(sc) : r / (float)(kp.n_rays >> (d < 0 ? 0 : d));
+                    return isfinite_(r) ? q : 0.0f;
+                };
+                v = fin_s(tres, tdepth, sc0);
+                const float v1 = fin_s(r1 + (m1 * 1.0f) * v, tdepth - 1, sc0 - (1u << 23));
+                v = tdepth - 1 > stop ? v1 : v;
+                const float v2 = fin_s(r2 + (m2 * 1.0f) * v, tdepth - 2, sc0 - (2u << 23));
+                v = tdepth - 2 > stop ? v2 : v;
+                uint32_t sc = sc0 - (3u << 23);
+#pragma unroll 1
+                for (int l = tdepth - 3; l > stop; --l, sc -= 1u << 23) {
+                    const lds_float* b = lvl(l);
+                    const float r = b[3 * kBlock] + (b[4 * kBlock] * 1.0f) * v;
+                    v = 0.0f;
+                    if (isfinite_(r)) v = kP2 ? r * __uint_as_float(sc) : r / (float)(kp.n_rays >> l);
+                }
             };
-            float v = fin_s(tres, tdepth);
-            const float v1 = fin_s(r1 + (m1 * 1.0f) * v, tdepth - 1);
-            v = tdepth - 1 > stop ? v1 : v;
-            const float v2 = fin_s(r2 + (m2 * 1.0f) * v, tdepth - 2);
-            v = tdepth - 2 > stop ? v2 : v;
-            for (int l = tdepth - 3; l > stop; --l) {
-                const float* b = lvl(l);
-                v = fin_v(b[3 * kBlock] + (b[4 * kBlock] * 1.0f) * v, l);
-            }
-            const bool resume = stop >= 0;
-            const int meta = __float_as_int(s5);
-            tpos = resume ? v3(s0, s1, s2) : tpos;
-            tres = resume ? s3 + (s4 * 1.0f) * v : tres;  // res += multiplier*albedo*ray_power
-            // (unsigned: with n_rays > 255 a kind of 6 + sphere index >= 32768
-            // sets bit 31 of the word, which must not sign-extend)
-            const int mkind = (int)((uint32_t)meta >> kp.meta_shift);
-            ti = resume ? meta & ((1 << kp.meta_shift) - 1) : ti;
-            tkind = resume ? mkind : tkind;
-            need_frame = resume ? mkind >= 5 && fdepth != stop : need_frame;
-            tdepth = resume ? stop : tdepth;
-            if (!resume) {
+            if (n_pow2)
+                unwind(std::true_type{});
+            else
+                unwind(std::false_type{});
+            if (stop >= 0) {
+                const int meta = __float_as_int(s5);
+                tpos = v3(s0, s1, s2);
+                tres = s3 + (s4 * 1.0f) * v;  // res += multiplier*albedo*ray_power
+                // (unsigned: with n_rays > 255 a kind of 6 + sphere index >= 32768
+                // sets bit 31 of the word, which must not sign-extend)
+                tkind = (int)((uint32_t)meta >> kp.meta_shift);
+                ti = (int)__builtin_amdgcn_ubfe((uint32_t)meta, 0u, (uint32_t)kp.meta_shift);  // meta_shift <= 31
+                need_frame = tkind >= 5 && fdepth != stop;
+                tdepth = stop;
+                // (the resumed node's position and depth land in the lane's
+                // registers here: no merge moves on the path-end side)
+                vgpr_hold(tpos);
+                vgpr_hold(tdepth);
+            } else {
                 kp.values[unit] = v >= 0.0f ? v : 0.0f;  // main.cpp:214
                 has_path = false;
             }
@@ -1532,7 +1562,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         // iteration prologue: RNG window, UnionDdf pick (ddf.cpp:142-153) and,
         // for a cosine pick, the CosineDdf table gathers (running it one step
         // ahead, right after the direction phase, measured -2.7 %: DESIGN.md 4.3)
-        const bool iter_lane = active && has_path && !fresh && !((kRes || kResL) && tracing);
+        const bool iter_lane = has_path && !fresh && !((kRes || kResL) && tracing);
         if constexpr (kRes) {
             // the iteration's pick, draws and CosineDdf factors live within the
             // step (set by the prologue / gathers, used by the direction phase):
@@ -1550,7 +1580,8 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         bool gcos = false;
         // kPreSkip: the word after the iteration's draws (the next pick) and
         // whether the end of the step may take it (set by the prologue)
-        uint32_t pre_w = 0u;
+        // (pre_w is read only behind pre_ok: left uninitialised, no per-step moves)
+        uint32_t pre_w;
         bool pre_ok = false;
         // IPT_LPF (lattice instances): the picked light's sample fields are
         // gathered with the CosineDdf gathers (whole wave, index 0 for lanes
@@ -1746,14 +1777,30 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             if (c <= nl) {
                 // words jj+1, jj+2 (jj <= 4 in the skip-ahead instances, <= 5
                 // with kPreSkip, else <= 3)
-                const bool hi = kSkipAhead && jj >= 4u;
-                const uint32_t r1 = hi ? (kPreSkip && (jj & 1u) ? w.b2 : w.b1) : sel4(jj & 3u, w.a1, w.a2, w.a3, w.b0);
-                const uint32_t r2 = hi ? (kPreSkip && (jj & 1u) ? w.b3 : w.b2) : sel4(jj & 3u, w.a2, w.a3, w.b0, w.b1);
+                uint32_t r1, r2;
                 if constexpr (kPreSkip) {
-                    // the next pick's word jj+3 (taken only at jj <= 3: the step
-                    // then ends at most 9 words past blk)
-                    pre_w = sel4(jj & 3u, w.a3, w.b0, w.b1, w.b2);
+                    // words jj+1 .. jj+3 (the last: the next pick's word, taken
+                    // only at jj <= 3: the step then ends at most 9 words past
+                    // blk) from one rotation of the window instead of three
+                    // select trees: the four words 2h+1 .. 2h+4 of the pair h =
+                    // jj >> 1 (0 .. 2), then one select each on jj's low bit.
+                    // (Word 8 does not exist: at jj >= 4 the third result is
+                    // another word than before, and as before not read.)
+                    const bool odd = (jj & 1u) != 0u, h0 = jj < 2u, h2 = jj >= 4u;
+                    auto sel3 = [&](uint32_t x0, uint32_t x1, uint32_t x2) {
+                        const uint32_t t = h0 ? x0 : x1;
+                        return h2 ? x2 : t;
+                    };
+                    const uint32_t e1 = sel3(w.a1, w.a3, w.b1), e2 = sel3(w.a2, w.b0, w.b2);
+                    const uint32_t e3 = sel3(w.a3, w.b1, w.b3), e4 = h0 ? w.b0 : w.b2;
+                    r1 = odd ? e2 : e1;
+                    r2 = odd ? e3 : e2;
+                    pre_w = odd ? e4 : e3;
                     pre_ok = jj <= 3u && kp.sa_on;
+                } else {
+                    const bool hi = kSkipAhead && jj >= 4u;
+                    r1 = hi ? w.b1 : sel4(jj & 3u, w.a1, w.a2, w.a3, w.b0);
+                    r2 = hi ? w.b2 : sel4(jj & 3u, w.a2, w.a3, w.b0, w.b1);
                 }
                 u1 = u01(r1);
                 u2 = u01(r2);
@@ -1797,18 +1844,21 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 if (kFramePf == 3) {
                     // `to` and its frame-table entry, prepared at the end of
                     // the previous step (pfok: `to` inside the table's range)
-                    to = pto;
-                    fs = pfs;
-                    fc = pfc;
+                    // (the rare branch writes the prefetch's own variables --
+                    // nothing reads them again before the next prefetch -- so
+                    // the common path copies nothing)
                     if constexpr (!IPT_FRAME_FB_PF) {
                     if (__builtin_expect(__any(!pfok), 0))
                         if (!pfok) {
-                            to = kFrameInrange ? normalize_inrange_(nrm) : normalize(nrm);
-                            frame_sc_lookup(kp.frame_sc, to, fs, fc);
-                            keep_alive(fs);  // its wait stays in this rare branch
-                            keep_alive(fc);
+                            pto = kFrameInrange ? normalize_inrange_(nrm) : normalize(nrm);
+                            frame_sc_lookup(kp.frame_sc, pto, pfs, pfc);
+                            keep_alive(pfs);  // its wait stays in this rare branch
+                            keep_alive(pfc);
                         }
                     }
+                    to = pto;
+                    fs = pfs;
+                    fc = pfc;
                     pfok = false;
                 } else {
                     to = kFrameInrange ? normalize_inrange_(nrm) : normalize(nrm);
@@ -1859,13 +1909,16 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         bool have_ray = false, is_iter = false;
         // (written by the new-path or the direction phase wherever have_ray is
         // set and read only then: left uninitialised, no per-step moves)
-        vec3 ro, rd;
+        // The ray's origin is the lane's node position: an iteration's ray
+        // starts there, and a new path parks the camera position in tpos (no
+        // node of its own yet: nothing reads tpos as a node before the
+        // camera ray's push overwrites it), so no origin is copied per step.
+        vec3 rd;
         int rdepth;
         // ------------- phase 2: new path (render_sample body, main.cpp:192-211), after
         // barrier B so that its camera ray is not live across the worker pass
-        if (active && has_path && fresh) {
+        if (has_path && fresh) {
             IPT_PHASE(2);
-            fresh = false;
             if (IPT_RAYGEN) {
                 // raygen_kernel ran render_sample's per-sample work for this
                 // unit (jitter, drift code and flags, camera ray, Philox block 0)
@@ -1877,7 +1930,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 if (r0.w == 0u) {
                     has_path = false;  // not ours / out of range: already stored
                 } else {
-                    ro = kp.cam_pos;
+                    tpos = kp.cam_pos;
                     rd = v3(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
                     w.a2 = r1.x;
                     w.a3 = r1.y;
@@ -1905,7 +1958,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             if (!g.valid) {
                 has_path = false;
             } else {
-                ro = kp.cam_pos;
+                tpos = kp.cam_pos;
                 rd = g.rd;
                 rdepth = 0;
                 have_ray = true;
@@ -1913,6 +1966,9 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             }
             }
         }
+        // (a fresh lane has a path, so the phase above ran for it: cleared for
+        // every lane, the flag is not carried over the loop's back edge)
+        fresh = false;
 
         // ------------------------- phase 3b: the iteration's direction (main.cpp:149-163)
         // kLightsOne: both candidate directions are computed by every lane and
@@ -1928,9 +1984,20 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             fm.m1 = v3(frc[3 * kFrameStride], frc[4 * kFrameStride], frc[5 * kFrameStride]);
             fm.m2 = v3(frc[6 * kFrameStride], frc[7 * kFrameStride], frc[8 * kFrameStride]);
             const vec3 cdir = frame_apply(fm, v3(tr * cs_c, tr * cs_s, sqrt_inrange_(u1)));
-            const vec3 ldir = lsample(LS.one, tpos, u1, u2);
             const vec3 zero = v3(0, 0, 0);
-            dir_bf = pick < nl ? ldir : (pick == nl ? cdir : zero);
+            if constexpr (LMODE == kLightsOneA10 || LMODE == kLightsOneA01) {
+                // the light sample's own zero vector (cosinus < 1e-5) folded
+                // into the pick's select: two selects per component, not three
+                bool lok;
+                const vec3 ldir = LMODE == kLightsOneA10
+                                      ? light_sample_dir_ax_ok<1, 0, IPT_LIGHT_INR>(LS.one, tpos, u1, u2, &lok)
+                                      : light_sample_dir_ax_ok<0, 1, IPT_LIGHT_INR>(LS.one, tpos, u1, u2, &lok);
+                const vec3 other = pick == nl ? cdir : zero;
+                dir_bf = pick < nl && lok ? ldir : other;
+            } else {
+                const vec3 ldir = lsample(LS.one, tpos, u1, u2);
+                dir_bf = pick < nl ? ldir : (pick == nl ? cdir : zero);
+            }
         }
         if (iter_lane) {
             vec3 dir = v3(0, 0, 0);
@@ -1962,13 +2029,13 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             if (is_zero(dir)) {
                 if (COUNT) ++c_skip;
             } else {
-                ro = tpos;
                 rd = dir;
                 rdepth = tdepth + 1;
                 have_ray = true;
                 is_iter = true;
             }
         }
+        const vec3 ro = tpos;
         IPT_STAMP_AT(8);  // direction
         // --------------------------------------------- phase 4: trace + resolve
         // the child's value (main.cpp:100-143) from its traces, then push it,
@@ -2012,8 +2079,9 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             if (push) {
                 IPT_PHASE(10);
                 if (iter) {
-                    finm = (finm & ~(1u << tdepth)) | ((ti >= (kp.n_rays >> tdepth) ? 1u : 0u) << tdepth);
-                    float* b = stk + (size_t)tdepth * kStackFields * kBlock + tid;
+                    const uint32_t lbit = 1u << tdepth;
+                    finm = (finm & ~lbit) | (ti >= (kp.n_rays >> tdepth) ? lbit : 0u);
+                    lds_float* b = (lds_float*)(stk + tid) + __umul24((uint32_t)tdepth, (uint32_t)(kStackFields * kBlock));  // (32-bit LDS address)
                     b[0 * kBlock] = tpos.x;
                     b[1 * kBlock] = tpos.y;
                     b[2 * kBlock] = tpos.z;
@@ -2157,6 +2225,14 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 }
                 if (COUNT) ++c_ltest;
                 if (is_iter) lmix += wl * lpdf(L, ro, h, hp, hn);
+                if constexpr (LMODE == kLightsOneA10 || LMODE == kLightsOneA01) {
+                    // the only light: a hit is the nearest one, and its point
+                    // (always written by light_trace_ax) and power are read
+                    // only behind has_li (resolve): taken without selects
+                    has_li = h;
+                    li_pos = hp;
+                    li_pow = L.spow;
+                } else
                 if (h && (!has_li || longer(li_pos - ro, hp - ro))) {
                     has_li = true;
                     li_pos = hp;
@@ -2409,7 +2485,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 // the frame the lane builds in the next step (a sphere node
                 // pushed in this step, or popped back to with its column
                 // overwritten): `to` and the table gather now, consumed there
-                if (need_frame && active && has_path) {
+                if (need_frame && has_path) {
                     const vec3 to = normalize_inrange_(tpos);
                     const uint32_t u = f2u(to.z), mz = u & 0x7fffffffu;
                     pfok = mz - kFrameTabLo <= kFrameTabSpan;

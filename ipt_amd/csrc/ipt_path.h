@@ -475,8 +475,10 @@ IPT_HD vec3 light_sample_dir_axf(vec3 P, float xa, float ya, float nn, int type,
     if (cosinus < 1e-5f) return v3(0.0f, 0.0f, 0.0f);
     return dir;
 }
+// (..._ok: the direction before the cosinus test and the test's outcome, for a
+// caller that folds the zero vector into a select of its own)
 template <int XA, int YA, bool INR = false>
-IPT_HD vec3 light_sample_dir_ax(const LightDev& L, vec3 o, float u1, float u2raw) {
+IPT_HD vec3 light_sample_dir_ax_ok(const LightDev& L, vec3 o, float u1, float u2raw, bool* ok) {
     constexpr int NA = 3 - XA - YA;
     const float u2 = u2raw * (L.type == 1 ? 1.0f - u1 : 1.0f);
     float pc[3];
@@ -486,7 +488,14 @@ IPT_HD vec3 light_sample_dir_ax(const LightDev& L, vec3 o, float u1, float u2raw
     // INR: |pos - o| in [dmin, dmax] for every surface point o
     const vec3 dir = INR ? normalize_inrange_(v3(pc[0], pc[1], pc[2]) - o) : normalize(v3(pc[0], pc[1], pc[2]) - o);
     const float cosinus = comp<NA>(L.n) * -comp<NA>(dir);
-    if (cosinus < 1e-5f) return v3(0.0f, 0.0f, 0.0f);
+    *ok = !(cosinus < 1e-5f);
+    return dir;
+}
+template <int XA, int YA, bool INR = false>
+IPT_HD vec3 light_sample_dir_ax(const LightDev& L, vec3 o, float u1, float u2raw) {
+    bool ok;
+    const vec3 dir = light_sample_dir_ax_ok<XA, YA, INR>(L, o, u1, u2raw, &ok);
+    if (!ok) return v3(0.0f, 0.0f, 0.0f);
     return dir;
 }
 // Host check of the conditions above; returns 1 + index of the (XA, YA) pair
