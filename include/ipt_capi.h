@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define IPT_ABI_VERSION 6
+#define IPT_ABI_VERSION 7
 
 enum {
     IPT_OK = 0,
@@ -114,7 +114,7 @@ typedef struct ipt_scene {
 } ipt_scene;
 
 typedef struct ipt_params {
-    int32_t width, height;  /* GridRenderPlane size; render_sample hardcodes 640x640 */
+    int32_t width, height;  /* render plane size; render_sample hardcodes 640x640 */
     int32_t spp;            /* number of render_sample passes in this call */
     int32_t spp_offset;     /* absolute index of the first pass (RNG counter) */
     int32_t n_rays;         /* branching factor of the root node (main.cpp:94), 0..65535
@@ -132,7 +132,26 @@ typedef struct ipt_params {
 } ipt_params;
 
 enum {
-    IPT_FLAG_COUNTERS = 1u /* accumulate ipt_counters during the call */
+    IPT_FLAG_COUNTERS = 1u, /* accumulate ipt_counters during the call */
+    /* ABI 7: the render plane is the Gui's (gui.cpp:165-182), the plane the
+       reference program renders into, displays and saves (main.cpp:250-289),
+       instead of GridRenderPlane. Gui::addRay maps a sample to
+         ix = min(size_t(x*W), W-1)   iy = min(size_t(H - y*H), H-1)
+       (its 640 and 639 generalised to W, H and W-1, H-1): a plain vertical
+       flip, source row s lands in row H-1-s, where GridRenderPlane::addRay's
+       size_t(H - y*H - 1) folds source rows H-2 and H-1 into row 0. The
+       running mean (gui.cpp:174-178) is addRay's, operation for operation.
+       With the flag, ipt_render, ipt_render_device, ipt_render_device_async,
+       ipt_render_values (codes relative to the nominal destination
+       (ix, H-1-iy)), ipt_shard_plan and ipt_counters.drifted use this
+       mapping; everything else of the ipt_image contract holds as written
+       (preloaded planes, optional sums and pixel_max, the uint32 counter
+       limit -- one sample per pixel and pass plus those that drift in --
+       and accumulation across calls with increasing spp_offset). Which kind
+       of plane an image holds is the caller's business: calls with and
+       without the flag into one image mix the two mappings. Without the flag
+       nothing changes. */
+    IPT_FLAG_GUI_PLANE = 2u
 };
 
 /* Caller-owned GridRenderPlane state (GridRenderPlane.h:9-12), width*height
@@ -170,7 +189,7 @@ typedef struct ipt_counters {
     uint64_t skipped;         /* iterations that returned vec3() */
     uint64_t sphere_frames;   /* RotateDdf builds at non-wall normals */
     uint64_t light_traces;    /* AreaLight::traceRay calls */
-    uint64_t drifted;         /* samples GridRenderPlane maps off their nominal pixel */
+    uint64_t drifted;         /* samples the render plane maps off their nominal pixel */
     uint64_t bvh_nodes;       /* sphere-BVH nodes visited (IPT_GEOM_SPHERES_IN_BOX) */
     uint64_t sphere_tests;    /* intersection_with_sphere evaluations on the sphere list */
     uint64_t light_nodes;     /* light-BVH nodes visited (many-light scenes) */
@@ -256,13 +275,15 @@ int ipt_render_wait(ipt_ctx* ctx);
    clamped root ray_power of pass p->spp_offset+s at source pixel (ix,iy)
    (main.cpp:211-214) and codes[s][iy][ix] the GridRenderPlane drift code
    (bits 0-1: dx+1, bits 2-3: dy+1 relative to the nominal destination
-   (ix, max(H-2-iy,0)); 0x05 = nominal). Host buffers of spp*width*height. */
+   (ix, max(H-2-iy,0)), or (ix, H-1-iy) with IPT_FLAG_GUI_PLANE; 0x05 =
+   nominal). Host buffers of spp*width*height. */
 int ipt_render_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t* codes);
 
 /* Host-only (no device needed): the tile plan of a sharded render.
    owned_rows[H] = 1 for destination rows this shard accumulates;
    cand_rows[*n_cand] = source rows whose samples it traces (the nominal
-   sources of its rows +-1 for GridRenderPlane drift). Arrays sized H. */
+   sources of its rows +-1 for drift, under GridRenderPlane's row map or, with
+   IPT_FLAG_GUI_PLANE, the Gui's). Arrays sized H. */
 int ipt_shard_plan(const ipt_params* p, uint8_t* owned_rows, int32_t* cand_rows, int32_t* n_cand);
 
 int ipt_get_counters(ipt_ctx* ctx, ipt_counters* out);

@@ -34,6 +34,7 @@ IPT_LIGHT_AREA_DIAMOND = 0
 IPT_LIGHT_AREA_TRIANGLE = 1
 IPT_LIGHT_SPHERE, IPT_LIGHT_POINT, IPT_LIGHT_OUTER_SPHERE = 2, 3, 4
 IPT_FLAG_COUNTERS = 1
+IPT_FLAG_GUI_PLANE = 2  # Gui::addRay's row map instead of GridRenderPlane::addRay's (ABI 7)
 
 F3 = C.c_float * 3
 
@@ -74,8 +75,8 @@ class DisplayParams(C.Structure):
                 ("flags", C.c_uint32)]
 
 
-ABI_VERSION = 6  # include/ipt_capi.h IPT_ABI_VERSION
-ABI_LAYOUT_COMPATIBLE = (3, 4, 5, 6)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
+ABI_VERSION = 7  # include/ipt_capi.h IPT_ABI_VERSION
+ABI_LAYOUT_COMPATIBLE = (3, 4, 5, 6, 7)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
 
 COUNTER_NAMES = ("paths", "traced_rays", "surface_hits", "light_hits", "expanded_nodes",
                  "iterations", "light_samples", "skipped", "sphere_frames", "light_traces",
@@ -446,7 +447,8 @@ SELFCHECK_DIV_ALL_SIGNIFICANDS, SELFCHECK_RCP_SCALING = 21, 22
 
 
 def shard_plan(p: Params):
-    """(owned_rows bool[H], candidate source rows int[]) of a sharded render."""
+    """(owned_rows bool[H], candidate source rows int[]) of a sharded render;
+    the candidates follow the plane's row map (p.flags & IPT_FLAG_GUI_PLANE)."""
     lib = load()
     owned = np.zeros(p.height, np.uint8)
     cand = np.zeros(p.height, np.int32)

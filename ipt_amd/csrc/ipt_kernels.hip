@@ -13,7 +13,9 @@
 //   accumulate_kernel  one thread per destination pixel: replays
 //                      GridRenderPlane::addRay (GridRenderPlane.cpp:61-75) for
 //                      all passes in render_sample order — coalesced reads of
-//                      the radiance buffer, HBM-bound.
+//                      the radiance buffer, HBM-bound. Its kPlaneGui instance
+//                      replays Gui::addRay's row map instead (gui.cpp:165-182,
+//                      IPT_FLAG_GUI_PLANE).
 // Build: see __graft_entry__.py (hipcc --offload-arch=gfx950 -O3
 //        -ffp-contract=off, no fast-math).
 #include <hip/hip_runtime.h>
@@ -158,7 +160,10 @@ struct KParams {
     const float2* __restrict__ frame_sc;  // frame_table_kernel: RotateDdf angle (sin, cos) by to.z
     const uint4* __restrict__ rg;         // IPT_RAYGEN: [total_units][2] raygen_kernel records
     int count;                            // raygen_kernel: accumulate the drift counter
+    int plane;                            // new_path_setup: kPlaneGrid / kPlaneGui (IPT_FLAG_GUI_PLANE)
 };
+// The render plane's index map: GridRenderPlane::addRay's or Gui::addRay's.
+enum { kPlaneGrid = 0, kPlaneGui = 1 };
 
 // floor(n / d) for 32-bit n, d >= 1 from a double reciprocal: the estimate's
 // error is below (n/d) * 2^-51 < 1/d (n < 2^32), i.e. below the distance of a
@@ -1149,9 +1154,10 @@ __host__ __device__ constexpr int waves_per_simd(int geom, int lmode) {
 // render_sample's per-sample work before ray_power (main.cpp:192-211) for
 // work unit `unit` (pass-major, then candidate row, then column): the absolute
 // pass and source pixel (the Philox counter), the two jitter draws, the
-// GridRenderPlane drift code (and the flags of drifted samples), the camera
-// ray. A unit whose sample lands outside the image or in another shard's row
-// gets its value (0) and code stored here and is not traced.
+// render plane's drift code (GridRenderPlane's or, with kp.plane ==
+// kPlaneGui, the Gui's; and the flags of drifted samples), the camera ray. A
+// unit whose sample lands outside the image or in another shard's row gets
+// its value (0) and code stored here and is not traced.
 struct RayGen {
     vec3 rd;
     uint32_t a0, a1, a2, a3, rpass, rpix;
@@ -1172,9 +1178,14 @@ __device__ __forceinline__ RayGen new_path_setup(const KParams& kp, unsigned lon
     philox_fill(g.a0, g.a1, g.a2, g.a3, 0u, g.rpass, g.rpix, kp.key0, kp.key1);
     const float x = jitter_coord(ix, u01(g.a0), kp.W);
     const float y = jitter_coord(iy, u01(g.a1), kp.H);
-    int xi, yi;
-    grid_index(x, y, kp.W, kp.H, &xi, &yi);
-    const int yn = nominal_row(iy, kp.H);
+    int xi, yi, yn;
+    if (kp.plane == kPlaneGui) {
+        gui_index(x, y, kp.W, kp.H, &xi, &yi);
+        yn = gui_nominal_row(iy, kp.H);
+    } else {
+        grid_index(x, y, kp.W, kp.H, &xi, &yi);
+        yn = nominal_row(iy, kp.H);
+    }
     const int dx = xi - ix, dy = yi - yn;
     uint8_t code = 0xff;
     if (dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1 && xi < kp.W && yi < kp.H)
@@ -2554,16 +2565,22 @@ __device__ __forceinline__ void add_ray(float v, float& p, uint32_t& c, float& s
     if (p > m) m = p;
 }
 
+// PLANE: kPlaneGrid replays GridRenderPlane::addRay's row map (source rows
+// H-2 and H-1 both land in row 0), kPlaneGui Gui::addRay's (source row s lands
+// in row H-1-s); the running mean is the same.
+template <int PLANE>
 __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int yi);
+template <int PLANE>
 __global__ __launch_bounds__(256) void accumulate_kernel(AParams ap) {
     const int xi = blockIdx.x * blockDim.x + threadIdx.x;
     const int yi = blockIdx.y;
     if (threadIdx.x == 0) atomicMin(&ap.clk[0], (unsigned long long)wall_clock64());
     if (xi < ap.W && (ap.n_shards <= 1 || ap.tile_rows <= 0 || ((yi / ap.tile_rows) % ap.n_shards) == ap.shard_id))
-        accumulate_pixel(ap, xi, yi);
+        accumulate_pixel<PLANE>(ap, xi, yi);
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(&ap.clk[1], (unsigned long long)wall_clock64());
 }
+template <int PLANE>
 __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int yi) {
     const size_t d = (size_t)yi * ap.W + xi;
     float p = ap.pixels[d];
@@ -2572,7 +2589,44 @@ __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int 
     float m = ap.pixel_max ? ap.pixel_max[d] : 0.0f;
     const size_t pass_stride = (size_t)ap.n_cand * ap.W;
     const int H = ap.H;
-    if (ap.flags[d] == 0) {
+    if (PLANE == kPlaneGui && ap.flags[d] == 0) {
+        // the one nominal source: row H-1-yi (in [0, H) for every yi). Loads
+        // of 8 passes, then their 8 updates, as below
+        const int c0 = ap.cand_of_row[H - 1 - yi];
+        if (c0 >= 0) {
+            const float* v0p = ap.values + (size_t)c0 * ap.W + xi;
+            int sp = 0;
+            for (; sp + 8 <= ap.spp; sp += 8) {
+                float a0[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) a0[q] = v0p[(size_t)(sp + q) * pass_stride];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) add_ray(a0[q], p, c, s, m);
+            }
+            for (; sp < ap.spp; ++sp) add_ray(v0p[(size_t)sp * pass_stride], p, c, s, m);
+        }
+    } else if (PLANE == kPlaneGui) {
+        // source rows whose nominal row H-1-iy is yi+1, yi, yi-1: ascending
+        // (raster order of render_sample). A sample the min() clamped has
+        // code 0x5 (row H-1 is source row 0's nominal row): no special case
+        for (int sp = 0; sp < ap.spp; ++sp) {
+            const size_t base = (size_t)sp * pass_stride;
+            for (int iy = H - 2 - yi; iy <= H - yi; ++iy) {
+                if (iy < 0 || iy >= H) continue;
+                const int ci = ap.cand_of_row[iy];
+                if (ci < 0) continue;
+                const int yn = H - 1 - iy;
+                for (int ix = xi - 1; ix <= xi + 1; ++ix) {
+                    if (ix < 0 || ix >= ap.W) continue;
+                    const size_t idx = base + (size_t)ci * ap.W + ix;
+                    const uint8_t code = ap.codes[idx];
+                    if (code >= 0x10) continue;
+                    const int dx = (code & 3) - 1, dy = ((code >> 2) & 3) - 1;
+                    if (ix + dx == xi && yn + dy == yi) add_ray(ap.values[idx], p, c, s, m);
+                }
+            }
+        }
+    } else if (ap.flags[d] == 0) {
         // nominal sources only: source row H-2-yi (and H-1 for yi == 0)
         int r0 = H - 2 - yi;
         const int c0 = r0 >= 0 ? ap.cand_of_row[r0] : -1;
@@ -2987,7 +3041,7 @@ struct WorkSlot {
     int* d_cand_rows = nullptr;
     int* d_cand_of_row = nullptr;
     int cand_cap_rows = 0, cand_cap_h = 0;
-    int plan[4] = {-1, -1, -1, -1};  // (H, tile_rows, n_shards, shard_id) whose rows are on the device
+    int plan[5] = {-1, -1, -1, -1, -1};  // (H, tile_rows, n_shards, shard_id, plane) whose rows are on the device
     unsigned long long* d_unit = nullptr;
     // pool-drained flag in signal memory (hipExtMallocWithFlags(hipMallocSignalMemory),
     // the memory hipStreamWaitValue64 is specified for) and the sequence
@@ -3308,14 +3362,18 @@ bool owned_host(const ipt_params* p, int yi) {
     return ((yi / p->tile_rows) % p->n_shards) == p->shard_id;
 }
 
-// Source rows whose samples can land in an owned destination row:
-// nominal row H-2-iy (0 for iy=H-1) within +-1 of an owned row.
+int plane_of(const ipt_params* p) { return (p->flags & IPT_FLAG_GUI_PLANE) ? kPlaneGui : kPlaneGrid; }
+
+// Source rows whose samples can land in an owned destination row: nominal
+// row within +-1 of an owned row, H-2-iy (0 for iy=H-1) under
+// GridRenderPlane's map, H-1-iy under the Gui's.
 void candidate_rows(const ipt_params* p, std::vector<int>& rows, std::vector<int>& of_row) {
     const int H = p->height;
+    const bool gui = plane_of(p) == kPlaneGui;
     rows.clear();
     of_row.assign(H, -1);
     for (int iy = 0; iy < H; ++iy) {
-        const int yn = H - 2 - iy > 0 ? H - 2 - iy : 0;
+        const int yn = gui ? ipt::gui_nominal_row(iy, H) : ipt::nominal_row(iy, H);
         bool c = false;
         for (int dy = -1; dy <= 1; ++dy) {
             const int y = yn + dy;
@@ -3513,8 +3571,8 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         ctx->next_slot ^= 1u;
         const bool grow = (size_t)chunk * per_pass > S.work_cap || (size_t)W * H > S.flags_cap ||
                           n_cand > S.cand_cap_rows || H > S.cand_cap_h;
-        const int plan[4] = {H, p->tile_rows, p->n_shards, p->shard_id};
-        const bool replan = !std::equal(plan, plan + 4, S.plan);
+        const int plan[5] = {H, p->tile_rows, p->n_shards, p->shard_id, plane_of(p)};
+        const bool replan = !std::equal(plan, plan + 5, S.plan);
         if (S.used && (grow || replan)) HIPCHECK(ctx, hipEventSynchronize(S.done));
         rc = ensure_work(ctx, S, (size_t)chunk * per_pass, (size_t)W * H, H, n_cand);
         if (rc) return rc;
@@ -3522,7 +3580,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             // (synchronous copies: the host vectors do not outlive the call)
             HIPCHECK(ctx, hipMemcpy(S.d_cand_rows, rows.data(), sizeof(int) * n_cand, hipMemcpyHostToDevice));
             HIPCHECK(ctx, hipMemcpy(S.d_cand_of_row, of_row.data(), sizeof(int) * H, hipMemcpyHostToDevice));
-            std::copy(plan, plan + 4, S.plan);
+            std::copy(plan, plan + 5, S.plan);
         }
         if (S.used) HIPCHECK(ctx, hipStreamWaitEvent(S.st, S.done, 0));
         // start in the predecessor's tail: once its pool is drained (or, without
@@ -3671,6 +3729,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         kp.frame_sc = ctx->d_frame_sc;
         kp.rg = S.d_rg;
         kp.count = count ? 1 : 0;
+        kp.plane = plane_of(p);
         // the slot stream: t0..t1 is the path's per-sample work, raygen_kernel
         // (render_sample's jitter, camera ray, Philox block 0; ~0.2 % of a C2
         // launch) and path_kernel
@@ -3701,7 +3760,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         }
         if (!img) HIPCHECK(ctx, hipEventRecord(S.done, ss));
         if (img) {
-            // the GridRenderPlane replay: on the caller's stream, in call order,
+            // the render plane's replay: on the caller's stream, in call order,
             // after this launch's path kernel
             HIPCHECK(ctx, hipStreamWaitEvent(st, tm.t1, 0));
             HIPCHECK(ctx, hipEventRecord(tm.a0, st));
@@ -3730,7 +3789,10 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             ap.pixel_max = img->pixel_max;
             ap.clk = clk ? clk : ctx->d_clk_dummy;
             dim3 grid((W + 255) / 256, H), block(256);
-            hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, st, ap);
+            if (kp.plane == kPlaneGui)
+                hipLaunchKernelGGL(accumulate_kernel<kPlaneGui>, grid, block, 0, st, ap);
+            else
+                hipLaunchKernelGGL(accumulate_kernel<kPlaneGrid>, grid, block, 0, st, ap);
             HIPCHECK(ctx, hipGetLastError());
             HIPCHECK(ctx, hipEventRecord(tm.a1, st));
             HIPCHECK(ctx, hipEventRecord(S.done, st));

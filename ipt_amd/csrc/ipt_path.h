@@ -769,6 +769,18 @@ IPT_HD void grid_index(float x, float y, int W, int H, int* xi, int* yi) {
     *yi = fy < 0.0f ? 0 : (int)fy;
 }
 IPT_HD int nominal_row(int iy, int H) { return H - 2 - iy > 0 ? H - 2 - iy : 0; }
+// Gui::addRay index mapping (gui.cpp:168-172), its 640 and 639 generalised to
+// W, H and W-1, H-1: no "- 1" inside the truncation, so a source-row-0 sample
+// whose H - y*H rounds to H gives H and is brought back to row H-1 by the min.
+IPT_HD void gui_index(float x, float y, int W, int H, int* xi, int* yi) {
+    const float fx = x * (float)W;
+    const float fy = (float)H - y * (float)H;
+    const int ix = fx < 0.0f ? 0 : (int)fx;  // (size_t) truncation
+    const int iy = fy < 0.0f ? 0 : (int)fy;
+    *xi = ix < W - 1 ? ix : W - 1;
+    *yi = iy < H - 1 ? iy : H - 1;
+}
+IPT_HD int gui_nominal_row(int iy, int H) { return H - 1 - iy; }
 
 // ---------------------------------------------------------- mixture weights
 // CollectionLighting::distributionInPoint + unite (CollectionLighting.cpp:12-21,

@@ -128,6 +128,33 @@ GridRenderPlane::GridRenderPlane(size_t w, size_t hh) : width(w), height(hh) {
     pixel_counters.resize(w * hh);
 }
 
+GuiRenderPlane::GuiRenderPlane(size_t w, size_t hh) : width(w), height(hh) {
+    pixels.resize(w * hh);
+    value_counter.resize(w * hh);
+}
+
+void GuiRenderPlane::resetImage() {
+    std::fill(pixels.begin(), pixels.end(), 0.0f);
+    std::fill(value_counter.begin(), value_counter.end(), (size_t)0);
+}
+
+void GuiRenderPlane::addRay(float x, float y, float value) {
+    // gui.cpp:168-172 with CImg's int width() / height(): float products, the
+    // difference in float, then the conversion to size_t
+    const int w = (int)width, h = (int)height;
+    size_t ix = x * w;
+    size_t iy = h - y * h;
+    ix = std::min(ix, width - 1);  // the reference's 640UL-1UL
+    iy = std::min(iy, height - 1);
+    // gui.cpp:174-178
+    const size_t d = iy * width + ix;
+    float old_v = pixels[d];
+    float sum = old_v * value_counter[d] + value;
+    ++value_counter[d];
+    float new_v = sum / value_counter[d];
+    pixels[d] = new_v;
+}
+
 // ---------------------------------------------------------------- scenes
 Scene make_scene_box() {
     auto lighting = std::make_shared<CollectionLighting>();
@@ -361,7 +388,7 @@ void GpuRenderer::upload(const Scene& s) {
 }
 
 namespace {
-ipt_params to_params(size_t W, size_t H, const RenderParams& p) {
+ipt_params to_params(size_t W, size_t H, const RenderParams& p, uint32_t flags) {
     ipt_params q{};
     q.width = (int)W;
     q.height = (int)H;
@@ -370,7 +397,7 @@ ipt_params to_params(size_t W, size_t H, const RenderParams& p) {
     q.n_rays = p.n_rays;
     q.depth_max = p.depth_max;
     q.seed = p.seed;
-    q.flags = p.counters ? IPT_FLAG_COUNTERS : 0;
+    q.flags = (p.counters ? IPT_FLAG_COUNTERS : 0) | flags;
     if (p.n_shards > 1) {
         q.tile_rows = p.tile_rows;
         q.n_shards = p.n_shards;
@@ -379,27 +406,34 @@ ipt_params to_params(size_t W, size_t H, const RenderParams& p) {
     return q;
 }
 // The plane's size_t counters as the library's 32-bit ones, and a zeroed
-// per-pixel running max (GridRenderPlane::addRay's max_value, per pixel)
+// per-pixel running max (GridRenderPlane::addRay's max_value, per pixel; the
+// Gui keeps none)
 struct PlaneIo {
     std::vector<uint32_t> cnt;
     std::vector<float> pmax;
-    PlaneIo(const GridRenderPlane& plane, int spp) : cnt(plane.pixel_counters.size()), pmax(cnt.size(), 0.0f) {
+    PlaneIo(const std::vector<size_t>& counters, int spp, bool with_max)
+        : cnt(counters.size()), pmax(with_max ? cnt.size() : 0, 0.0f) {
         for (size_t i = 0; i < cnt.size(); ++i) {
-            if (plane.pixel_counters[i] > 0xffffffffull - (size_t)std::max(spp, 0))
+            if (counters[i] > 0xffffffffull - (size_t)std::max(spp, 0))
                 throw IptError(IPT_E_INVALID, "pixel counter would overflow 32 bits");
-            cnt[i] = (uint32_t)plane.pixel_counters[i];
+            cnt[i] = (uint32_t)counters[i];
         }
     }
-    ipt_image image(GridRenderPlane& plane) {
+    PlaneIo(const GridRenderPlane& plane, int spp) : PlaneIo(plane.pixel_counters, spp, true) {}
+    PlaneIo(const GuiRenderPlane& plane, int spp) : PlaneIo(plane.value_counter, spp, false) {}
+    ipt_image image(std::vector<float>& pixels) {
         ipt_image img{};
-        img.pixels = plane.pixels.data();
+        img.pixels = pixels.data();
         img.counters = cnt.data();
-        img.pixel_max = pmax.data();
+        img.pixel_max = pmax.empty() ? nullptr : pmax.data();
         return img;
     }
     void finish(GridRenderPlane& plane) const {
         for (size_t i = 0; i < cnt.size(); ++i) plane.pixel_counters[i] = cnt[i];
         for (float m : pmax) plane.max_value = std::max(plane.max_value, m);
+    }
+    void finish(GuiRenderPlane& plane) const {
+        for (size_t i = 0; i < cnt.size(); ++i) plane.value_counter[i] = cnt[i];
     }
 };
 void check_plane(const GridRenderPlane& plane) {
@@ -407,17 +441,30 @@ void check_plane(const GridRenderPlane& plane) {
     if (plane.pixels.size() != n || plane.pixel_counters.size() != n)
         throw IptError(IPT_E_INVALID, "GridRenderPlane buffers do not match width*height");
 }
+void check_plane(const GuiRenderPlane& plane) {
+    const size_t n = plane.width * plane.height;
+    if (plane.pixels.size() != n || plane.value_counter.size() != n)
+        throw IptError(IPT_E_INVALID, "GuiRenderPlane buffers do not match width*height");
+}
 }  // namespace
 
-void GpuRenderer::render_image(ipt_image& img, size_t width, size_t height, const RenderParams& p) {
-    ipt_params q = to_params(width, height, p);
+void GpuRenderer::render_image(ipt_image& img, size_t width, size_t height, const RenderParams& p, uint32_t flags) {
+    ipt_params q = to_params(width, height, p, flags);
     check(ctx_, ipt_render(ctx_, &q, &img));
+}
+
+void GpuRenderer::render(GuiRenderPlane& plane, const RenderParams& p) {
+    check_plane(plane);
+    PlaneIo io(plane, p.spp);
+    ipt_image img = io.image(plane.pixels);
+    render_image(img, plane.width, plane.height, p, IPT_FLAG_GUI_PLANE);
+    io.finish(plane);
 }
 
 void GpuRenderer::render(GridRenderPlane& plane, const RenderParams& p) {
     check_plane(plane);
     PlaneIo io(plane, p.spp);
-    ipt_image img = io.image(plane);
+    ipt_image img = io.image(plane.pixels);
     render_image(img, plane.width, plane.height, p);
     io.finish(plane);
 }
@@ -470,6 +517,11 @@ void render_samples_gpu(const Scene& scene, GridRenderPlane& plane, const Render
     r.upload(scene);
     r.render(plane, p);
 }
+void render_samples_gpu(const Scene& scene, GuiRenderPlane& plane, const RenderParams& p, int device) {
+    GpuRenderer r(device);
+    r.upload(scene);
+    r.render(plane, p);
+}
 
 MultiGpuRenderer::MultiGpuRenderer(const std::vector<int>& devices, int tile_rows) : tile_rows_(tile_rows) {
     if (devices.empty()) throw IptError(IPT_E_INVALID, "MultiGpuRenderer: no devices");
@@ -493,7 +545,24 @@ void MultiGpuRenderer::render(GridRenderPlane& plane, const RenderParams& p) {
     // and writes only the context's own rows (its device keeps them between
     // calls), so the shards share the host buffers without copies or merging
     PlaneIo io(plane, p.spp);
-    ipt_image img = io.image(plane);
+    render_shards(io.image(plane.pixels), plane.width, plane.height, p, 0);
+    io.finish(plane);
+}
+
+void MultiGpuRenderer::render(GuiRenderPlane& plane, const RenderParams& p) {
+    if (r_.size() == 1) {
+        r_[0]->render(plane, p);
+        return;
+    }
+    check_plane(plane);
+    PlaneIo io(plane, p.spp);
+    render_shards(io.image(plane.pixels), plane.width, plane.height, p, IPT_FLAG_GUI_PLANE);
+    io.finish(plane);
+}
+
+void MultiGpuRenderer::render_shards(ipt_image img, size_t width, size_t height, const RenderParams& p,
+                                     uint32_t flags) {
+    const int n = (int)r_.size();
     std::vector<int> code(n, IPT_OK);
     std::vector<std::string> msg(n);
     std::vector<std::thread> th;
@@ -505,7 +574,7 @@ void MultiGpuRenderer::render(GridRenderPlane& plane, const RenderParams& p) {
             q.shard_id = k;
             try {
                 ipt_image im = img;
-                r_[k]->render_image(im, plane.width, plane.height, q);
+                r_[k]->render_image(im, width, height, q, flags);
             } catch (const IptError& e) {
                 code[k] = e.code;
                 msg[k] = e.what();
@@ -517,7 +586,6 @@ void MultiGpuRenderer::render(GridRenderPlane& plane, const RenderParams& p) {
     for (auto& t : th) t.join();
     for (int k = 0; k < n; ++k)
         if (code[k] != IPT_OK) throw IptError(code[k], "shard " + std::to_string(k) + ": " + msg[k]);
-    io.finish(plane);
 }
 
 void MultiGpuRenderer::transfer_bytes(uint64_t* host_to_device, uint64_t* device_to_host) const {

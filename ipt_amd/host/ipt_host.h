@@ -10,6 +10,8 @@
 //   SimpleCamera(position, direction, up_hint=(0,0,1))  (SimpleCamera.h:9-17)
 //   GridRenderPlane{pixels, pixel_counters, width, height, max_value}
 //                                                       (GridRenderPlane.h:8-18)
+//   GuiRenderPlane{width, height, pixels, value_counter} (gui.h:16-20, the
+//     image and counters of the Gui, the plane main.cpp renders into)
 //   make_scene_box()                                    (sample_scenes.cpp:20-41)
 // plus the synthetic BASELINE scenes (C3 sphere list, C5 light grid).
 //
@@ -154,6 +156,23 @@ struct GridRenderPlane : RenderPlane {
     GridRenderPlane(size_t width, size_t height);
 };
 
+// The Gui's image and value_counter (gui.h:16-20) without its window: the
+// plane the reference program renders into, displays and saves (main.cpp:
+// 250-289). Gui::addRay (gui.cpp:165-182) maps a sample to
+//   ix = min(size_t(x*W), W-1)   iy = min(size_t(H - y*H), H-1)
+// (the reference's 640 and 639 generalised), a plain vertical flip, where
+// GridRenderPlane's size_t(H - y*H - 1) folds source rows H-2 and H-1 into row
+// 0. Filled by the GPU accumulate kernel (IPT_FLAG_GUI_PLANE); addRay here is
+// the CPU restatement, for tests.
+struct GuiRenderPlane : RenderPlane {
+    size_t width, height;
+    std::vector<float> pixels;          // image(ix, iy), row-major
+    std::vector<size_t> value_counter;  // value_counter[iy][ix]
+    GuiRenderPlane(size_t width, size_t height);
+    void resetImage();                  // gui.cpp:154-162
+    void addRay(float x, float y, float value);  // gui.cpp:168-178
+};
+
 // --------------------------------------------------------- sample scenes
 Scene make_scene_box();                                   // sample_scenes[0]
 Scene make_scene_box_lights(int k);                       // [0]'s light as k*k squares (C5: k=16)
@@ -198,9 +217,12 @@ class GpuRenderer {
     void upload(const Scene& s);
     // spp passes of render_sample accumulated into plane (bit-exact GridRenderPlane semantics)
     void render(GridRenderPlane& plane, const RenderParams& p);
+    // the same into the Gui's plane (Gui::addRay's row map, IPT_FLAG_GUI_PLANE)
+    void render(GuiRenderPlane& plane, const RenderParams& p);
     // the same into a C-ABI image (32-bit counters); with p.n_shards > 1 only
-    // the shard's rows of it are read and written (ipt_render)
-    void render_image(ipt_image& img, size_t width, size_t height, const RenderParams& p);
+    // the shard's rows of it are read and written (ipt_render). flags: further
+    // IPT_FLAG_* bits of the call (IPT_FLAG_GUI_PLANE for a Gui plane's image)
+    void render_image(ipt_image& img, size_t width, size_t height, const RenderParams& p, uint32_t flags = 0);
     // host <-> device bytes of the last render (ipt_transfer_bytes): the
     // context keeps its rows of the plane on its device between calls
     void transfer_bytes(uint64_t* host_to_device, uint64_t* device_to_host) const;
@@ -223,6 +245,7 @@ class GpuRenderer {
 
 // One-shot convenience (the INTEGRATION.md adapter's shape).
 void render_samples_gpu(const Scene& scene, GridRenderPlane& plane, const RenderParams& p, int device = 0);
+void render_samples_gpu(const Scene& scene, GuiRenderPlane& plane, const RenderParams& p, int device = 0);
 
 // N contexts (one per entry of `devices`; a device may repeat), i.e. the
 // node's GPUs in one process. The reference renders with several worker
@@ -239,6 +262,7 @@ class MultiGpuRenderer {
     explicit MultiGpuRenderer(const std::vector<int>& devices, int tile_rows = 16);
     void upload(const Scene& s);
     void render(GridRenderPlane& plane, const RenderParams& p);
+    void render(GuiRenderPlane& plane, const RenderParams& p);
     // host <-> device bytes of the last render, summed over the contexts
     void transfer_bytes(uint64_t* host_to_device, uint64_t* device_to_host) const;
     size_t size() const { return r_.size(); }
@@ -247,6 +271,7 @@ class MultiGpuRenderer {
     void last_kernel_ms(float* path_ms, float* accumulate_ms) const;
 
    private:
+    void render_shards(ipt_image img, size_t width, size_t height, const RenderParams& p, uint32_t flags);
     std::vector<std::unique_ptr<GpuRenderer>> r_;
     int tile_rows_;
 };

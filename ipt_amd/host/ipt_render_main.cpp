@@ -11,8 +11,15 @@
 //              [--devices 0,1,...,7 [--tile-rows 16]]
 //              [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]
 //              [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out glare.pfm]
-//              [--gpu-display]
+//              [--gpu-display] [--gui-plane]
 //
+// --gui-plane renders into the Gui's plane (GuiRenderPlane, Gui::addRay's row
+// map, gui.cpp:165-182) instead of a GridRenderPlane: the plane the reference
+// program displays and saves, so that with --gpu-display the chain render ->
+// Gui plane -> glare -> tone map -> 8-bit is the reference's main loop on the
+// device. It composes with --gpu-display, --glare, --passes, --devices, --pfm
+// and --counts; --smooth and --pgm are GridRenderPlane's filter and main.cpp's
+// PGM writer for it and are refused.
 // --gpu-display takes the PNG's bytes from GpuRenderer::display (the display
 // pipeline on the GPU, with the --glare cutoff's bloom when one is given, as
 // Gui::updateDisplay shows it) instead of the host's to_gray8; without
@@ -44,7 +51,7 @@ namespace {
                  "                  [--devices I,J,... [--tile-rows 16]]\n"
                  "                  [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]\n"
                  "                  [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out F.pfm]\n"
-                 "                  [--gpu-display]\n");
+                 "                  [--gpu-display] [--gui-plane]\n");
     std::exit(2);
 }
 }  // namespace
@@ -52,7 +59,7 @@ namespace {
 int main(int argc, char** argv) {
     std::string scene_name = "box", out = "result.png", pfm, counts, pgm, glare_out;
     long smooth = 0;
-    bool gpu_display = false;
+    bool gpu_display = false, gui_plane = false;
     double glare = -1.0;
     long width = 640, height = 640, spp = 16, passes = 1, n_rays = 16, depth = 8, device = 0, tile_rows = 16;
     std::vector<int> devices;
@@ -88,9 +95,12 @@ int main(int argc, char** argv) {
         else if (a == "--glare") glare = std::atof(val());
         else if (a == "--glare-out") glare_out = val();
         else if (a == "--gpu-display") gpu_display = true;
+        else if (a == "--gui-plane") gui_plane = true;
         else usage(("unknown option " + a).c_str());
     }
     if (width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || n_rays < 0 || depth < 0) usage("bad sizes");
+    if (gui_plane && smooth > 0) usage("--smooth is GridRenderPlane::smooth; the Gui plane (--gui-plane) has none");
+    if (gui_plane && !pgm.empty()) usage("--pgm is main.cpp's writer for a GridRenderPlane; not with --gui-plane");
     try {
         const ipt::Scene scene = ipt::make_scene_by_name(scene_name);
         if (devices.empty()) devices.push_back((int)device);
@@ -98,7 +108,10 @@ int main(int argc, char** argv) {
         ipt::MultiGpuRenderer gpus(devices, (int)tile_rows);
         ipt::GpuRenderer& gpu = gpus.context(0);  // post-process runs on the first context
         gpus.upload(scene);
+        // the output stages below read a GridRenderPlane's size, pixels and
+        // counters; a Gui plane's are moved into `plane` once it is rendered
         ipt::GridRenderPlane plane((size_t)width, (size_t)height);
+        ipt::GuiRenderPlane gui(gui_plane ? (size_t)width : 0, gui_plane ? (size_t)height : 0);
         ipt::RenderParams p;
         p.spp = (int)spp;
         p.n_rays = (int)n_rays;
@@ -108,7 +121,8 @@ int main(int argc, char** argv) {
         const auto t0 = std::chrono::steady_clock::now();
         for (long pass = 0; pass < passes; ++pass) {  // progressive: each batch continues the RNG stream
             p.spp_offset = (int)(pass * spp);
-            gpus.render(plane, p);
+            if (gui_plane) gpus.render(gui, p);
+            else gpus.render(plane, p);
             float pm = 0.0f, am = 0.0f;
             gpus.last_kernel_ms(&pm, &am);
             kernel_ms += pm + am;
@@ -116,6 +130,12 @@ int main(int argc, char** argv) {
         const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         uint64_t h2d = 0, d2h = 0;  // the last batch's plane transfers (all contexts)
         gpus.transfer_bytes(&h2d, &d2h);
+        if (gui_plane) {
+            plane.pixels = std::move(gui.pixels);
+            plane.pixel_counters = std::move(gui.value_counter);
+            // (the Gui keeps no max_value; the JSON line reports the plane's largest pixel)
+            for (float v : plane.pixels) plane.max_value = v > plane.max_value ? v : plane.max_value;
+        }
         if (smooth > 0) gpu.smooth(plane, (size_t)smooth);
         if (glare >= 0.0 && !glare_out.empty()) {
             ipt::GridRenderPlane g(plane.width, plane.height);
@@ -140,10 +160,10 @@ int main(int argc, char** argv) {
             "{\"scene\": \"%s\", \"width\": %ld, \"height\": %ld, \"spp\": %ld, \"passes\": %ld, "
             "\"n_rays\": %ld, \"depth_max\": %ld, \"devices\": %zu, \"max_value\": %.9g, \"seconds\": %.4f, "
             "\"Mpaths_per_s\": %.3f, \"kernel_Mpaths_per_s\": %.3f, \"last_batch_h2d_bytes\": %llu, "
-            "\"last_batch_d2h_bytes\": %llu}\n",
+            "\"last_batch_d2h_bytes\": %llu, \"plane\": \"%s\"}\n",
             scene_name.c_str(), width, height, spp, passes, n_rays, depth, gpus.size(), (double)plane.max_value, secs,
             paths / secs / 1e6, kernel_ms > 0 ? paths / (kernel_ms * 1e-3) / 1e6 : 0.0, (unsigned long long)h2d,
-            (unsigned long long)d2h);
+            (unsigned long long)d2h, gui_plane ? "gui" : "grid");
     } catch (const ipt::IptError& e) {
         std::fprintf(stderr, "ipt_render: error %d: %s\n", e.code, e.what());
         return 1;

@@ -1,5 +1,8 @@
 """Image-tile sharding across ranks (one rank per GPU) and the frame-end
-assembly of the GridRenderPlane state.
+assembly of the render plane's state: GridRenderPlane's
+or, with capi.IPT_FLAG_GUI_PLANE in the params' flags, the Gui's. Ownership is
+by DESTINATION row, so nothing here depends on the plane's row map (that is
+ipt_shard_plan's candidate source rows); the flag only travels in Params.
 
 The reference has no multi-device path (its only parallelism is whole-frame
 threads, /root/reference/src/main.cpp:256-285). Every (pixel, pass) sample is
@@ -17,16 +20,17 @@ import numpy as np
 
 from . import capi
 
-FIELDS = 4  # GridRenderPlane pixels (f32), counters (u32 bits), sums (f32), pixel_max (f32)
+FIELDS = 4  # render plane pixels (f32), counters (u32 bits), sums (f32), pixel_max (f32)
 
 
-def owned_rows(width: int, height: int, tile_rows: int, world: int) -> list[np.ndarray]:
-    """Destination rows owned by each rank (ipt_shard_plan, host only)."""
+def owned_rows(width: int, height: int, tile_rows: int, world: int, flags: int = 0) -> list[np.ndarray]:
+    """Destination rows owned by each rank (ipt_shard_plan, host only); the
+    same under either plane kind (`flags`, the renders' ipt_params.flags)."""
     if world <= 1:
         return [np.arange(height)]
     out = []
     for r in range(world):
-        p = capi.make_params(width, height, 1, tile_rows=tile_rows, n_shards=world, shard_id=r)
+        p = capi.make_params(width, height, 1, tile_rows=tile_rows, n_shards=world, shard_id=r, flags=flags)
         out.append(np.nonzero(capi.shard_plan(p)[0])[0])
     return out
 
