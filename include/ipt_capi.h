@@ -364,6 +364,62 @@ int ipt_display_device(ipt_ctx* ctx, const ipt_display_params* p, const float* d
    outputs asked for; processed and tone may be NULL). */
 int ipt_display(ipt_ctx* ctx, const ipt_display_params* p, const float* pixels, float* processed, float* tone,
                 uint8_t* gray8);
+/* ---- display statistics on the GPU (ABI 7 additions), bit-exact ---------------
+   The two parts of Gui::updateDisplay that decide the exposure, beside the
+   pipeline above (entry points and one struct added; no layout changes, as
+   ABI 4 added entry points to ABI 3). With A = processed (the glare output,
+   or the pixels when glare_cutoff == 0):
+     stats[0]  mx, the max fold of ipt_display_device
+     stats[1]  mx / 100000.0f (IEEE f32, subnormals kept; a NaN mx quieted)
+     stats[2]  the white point (below)
+     stats[3]  0
+     hist[b]   CImg get_histogram(hist_buckets, stats[1], mx) of A (gui.cpp:
+               83-88, CImg.h:33484-33495), in double as CImg computes it:
+               vmin, vmax = the two bounds, swapped unless stats[1] < mx; an
+               element counts iff vmin <= val <= vmax; its bucket is nb-1 when
+               val == vmax, otherwise (unsigned)((val - vmin) * nb / (vmax -
+               vmin)). So: an all-zero image counts every pixel in the last
+               bucket, a NaN mx counts nothing, an infinite mx counts the
+               infinities only, a negative mx swaps the bounds. uint32 counts.
+     white     white_rank < 0: mx (normalize() as the reference builds it).
+               white_rank >= width*height: mx (CImg kth_smallest: max()).
+               Otherwise CImg kth_smallest(white_rank) of A (gui.cpp:13), the
+               element at that 0-based index of the ascending order. Two points
+               CImg leaves to its algorithm are stated: -0 orders before +0,
+               and NaNs of either sign order after +inf; a rank that lands
+               among them yields 0x7fc00000.
+     tone      cut(powf(A / white, (float)(1.0f/2.2f)), 0, 1), the pipeline's
+               arithmetic with white in place of mx; gray8 from tone as above.
+   With white_rank < 0, processed, tone and gray8 equal ipt_display_device's
+   bit for bit. dev_processed, dev_tone, dev_gray8, dev_hist and dev_stats may
+   each be NULL, and a stage nobody asked for is not run (a histogram-only call
+   evaluates no powf). Errors: ipt_display_device's rules (no output is
+   mandatory), and hist_buckets outside 0..4096 or hist_buckets > 0 with a NULL
+   dev_hist: IPT_E_INVALID; all refused before a buffer is touched. */
+typedef struct ipt_display_stats_params {
+    int32_t width, height;
+    float glare_cutoff;   /* exactly as ipt_display_params */
+    int32_t hist_buckets; /* 0: no histogram; 1..4096; the Gui's is 400 */
+    int64_t white_rank;   /* < 0: white = the max fold; k >= 0: white = kth_smallest(k) */
+    uint32_t flags;       /* 0 */
+} ipt_display_stats_params;
+
+/* Device buffers; stream and scratch rules are ipt_display_device's: the work
+   runs on `hip_stream` (NULL = the context's stream) and the call returns once
+   it is queued; no value crosses to the host inside the call (mx, the radix
+   prefixes, the remaining rank and the white point stay in device memory,
+   where the next kernel reads them); the scratch (ipt_display_device's plus
+   24 KiB of digit counts) belongs to the context and grows to the largest
+   request, so a repeated call at the same size allocates, frees and
+   synchronises nothing; a call on another stream waits on the previous call's
+   event; ipt_render_wait, ipt_upload_scene and ipt_destroy wait for queued
+   calls. dev_hist holds hist_buckets counts, dev_stats 4 floats. */
+int ipt_display_stats_device(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* dev_pixels,
+                             float* dev_processed, float* dev_tone, uint8_t* dev_gray8, uint32_t* dev_hist,
+                             float* dev_stats, void* hip_stream);
+/* Host buffers: the same kernels, synchronous. */
+int ipt_display_stats(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* pixels, float* processed,
+                      float* tone, uint8_t* gray8, uint32_t* hist, float* stats);
 /* Probes of the display chain's powf (ipt_math.h powf_, glibc 2.35's
    __powf_fma restated): out[i] = powf(x[i], y), host buffers; y finite, > 0
    and not an integer (IPT_E_UNSUPPORTED otherwise). ipt_powf_host is the

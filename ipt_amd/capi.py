@@ -75,6 +75,11 @@ class DisplayParams(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class DisplayStatsParams(C.Structure):  # ABI 7 additions
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("glare_cutoff", C.c_float),
+                ("hist_buckets", C.c_int32), ("white_rank", C.c_int64), ("flags", C.c_uint32)]
+
+
 ABI_VERSION = 7  # include/ipt_capi.h IPT_ABI_VERSION
 ABI_LAYOUT_COMPATIBLE = (3, 4, 5, 6, 7)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
 
@@ -98,6 +103,7 @@ EXPORTED_SYMBOLS = (
     "ipt_shard_plan", "ipt_get_profile", "ipt_math_selfcheck", "ipt_smooth", "ipt_glare", "ipt_ddf_sample", "ipt_ddf_value",
     "ipt_philox", "ipt_transfer_bytes",
     "ipt_display_device", "ipt_display", "ipt_powf_host", "ipt_powf_device",
+    "ipt_display_stats_device", "ipt_display_stats",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -172,6 +178,9 @@ def load(path: str | os.PathLike | None = None):
                                     C.c_void_p]
         lib.ipt_powf_host.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_int64]
         lib.ipt_powf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64]
+    if hasattr(lib, "ipt_display_stats_device"):  # ABI 7 additions
+        lib.ipt_display_stats_device.argtypes = [C.c_void_p, C.POINTER(DisplayStatsParams)] + [C.c_void_p] * 7
+        lib.ipt_display_stats.argtypes = [C.c_void_p, C.POINTER(DisplayStatsParams)] + [C.c_void_p] * 6
     if path is None:
         _lib = lib
     return lib
@@ -225,6 +234,19 @@ def make_display_params(width, height, glare_cutoff=0.0, flags=0) -> DisplayPara
     p = DisplayParams()
     p.width, p.height, p.glare_cutoff, p.flags = width, height, glare_cutoff, flags
     return p
+
+
+def make_display_stats_params(width, height, glare_cutoff=0.0, hist_buckets=0, white_rank=-1,
+                              flags=0) -> DisplayStatsParams:
+    p = DisplayStatsParams()
+    p.width, p.height, p.glare_cutoff, p.flags = width, height, glare_cutoff, flags
+    p.hist_buckets, p.white_rank = hist_buckets, white_rank
+    return p
+
+
+def white_rank_for(width, height, fraction) -> int:
+    """The reference's rank expression (gui.cpp:13): (ulong)(int(w*h) * fraction), in double."""
+    return int(float(int(width) * int(height)) * float(fraction))
 
 
 class Context:
@@ -367,6 +389,31 @@ class Context:
             self.h, C.byref(make_display_params(width, height, glare_cutoff)),
             src.ctypes.data if src.size else None, out["processed"].ctypes.data, out["tone"].ctypes.data,
             out["gray8"].ctypes.data))
+        return out
+
+    def display_stats_device(self, params: DisplayStatsParams, pixels_ptr, processed_ptr=None, tone_ptr=None,
+                             gray8_ptr=None, hist_ptr=None, stats_ptr=None, stream=None):
+        """Queue the display pipeline with its statistics on device buffers
+        (ipt_display_stats_device): the Gui's histogram (params.hist_buckets
+        uint32 counts at hist_ptr), {mx, mx/100000, white, 0} at stats_ptr,
+        and tone / gray8 with the white point of params.white_rank. Every
+        output is optional; complete on `stream`'s order or after wait()."""
+        _check(self.lib, self.h, self.lib.ipt_display_stats_device(
+            self.h, C.byref(params), pixels_ptr, processed_ptr, tone_ptr, gray8_ptr, hist_ptr, stats_ptr, stream))
+
+    def display_stats(self, pixels: np.ndarray, width: int, height: int, glare_cutoff: float = 0.0,
+                      hist_buckets: int = 400, white_rank: int = -1) -> dict:
+        """Host-buffer display statistics (ipt_display_stats):
+        {processed, tone, gray8, hist, stats}."""
+        src = np.ascontiguousarray(pixels, dtype=np.float32)
+        out = {"processed": np.empty(src.size, np.float32), "tone": np.empty(src.size, np.float32),
+               "gray8": np.empty(src.size, np.uint8), "hist": np.zeros(max(hist_buckets, 0), np.uint32),
+               "stats": np.empty(4, np.float32)}
+        _check(self.lib, self.h, self.lib.ipt_display_stats(
+            self.h, C.byref(make_display_stats_params(width, height, glare_cutoff, hist_buckets, white_rank)),
+            src.ctypes.data if src.size else None, out["processed"].ctypes.data, out["tone"].ctypes.data,
+            out["gray8"].ctypes.data, out["hist"].ctypes.data if hist_buckets > 0 else None,
+            out["stats"].ctypes.data))
         return out
 
     def powf_device(self, x: np.ndarray, y: float) -> np.ndarray:

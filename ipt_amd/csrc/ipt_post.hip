@@ -328,6 +328,212 @@ __global__ __launch_bounds__(kPostBlock) void powf_kernel(const float* __restric
     if (i < n) out[i] = powf_(x[i], y);
 }
 
+// ---------------------------------------------------------- display statistics
+// ipt_display_stats_device (ABI 7 additions): Gui::updateDisplay's histogram
+// window (gui.cpp:83-88, CImg get_histogram) and a white point chosen by rank
+// (normalize()'s kth_smallest remedy, gui.cpp:13) beside the max fold. Every
+// count is an integer, so no result depends on the order of the atomics, and
+// the control values (mx, mx/100000, the radix prefix, the remaining rank and
+// the white point) stay in StatsScalars between the kernels.
+//
+// Both histograms are privatised: a workgroup counts into LDS and flushes its
+// non-empty bins with one global atomic each; the grid is a multiple of the
+// CU count, not of n. The LDS atomics are issued per lane: a constant image,
+// where all 64 lanes of a wave hit one address, costs 10-15 % more than a
+// render, and combining equal bins within the wave first (ballot on the first
+// live lane's bin) changed neither by more than the run-to-run spread
+// (DESIGN.md 4.8), so there is none.
+//
+// Rank selection: radix select on the order-preserving key (-0 before +0, NaN
+// of either sign above +inf), most significant digit first, kSelPasses digits
+// of kSelBits[] bits. Per pass: select_hist_kernel counts the digit of the
+// elements that match the prefix so far, select_scan_kernel (one workgroup)
+// finds the digit that holds the remaining rank and extends the prefix.
+constexpr int kSelPasses = 3;  // (four 8-bit passes measured 8-12 % slower: two more launches)
+constexpr int kSelBits[kSelPasses] = {11, 11, 10};
+constexpr int kSelDigits = 2048;      // counts per pass (the widest digit)
+constexpr int kHistMaxBuckets = 4096;  // 16 KiB of LDS
+constexpr int kStatsBlocksPerCu = 8;
+
+struct StatsScalars {
+    float mx, lo, white;
+    unsigned int prefix;     // the selected key's digits so far, in place
+    unsigned int remaining;  // rank among the elements that match the prefix
+    unsigned int pad[3];
+    unsigned int digits[kSelPasses][kSelDigits];
+};
+
+// order-preserving key of the selection (ipt_capi.h): unsigned order == the
+// stated order of floats
+__device__ __forceinline__ unsigned int sel_key_(float v) {
+    const unsigned int u = f2u(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sel_unkey_(unsigned int k) {
+    if (k == 0xffffffffu) return u2f(0x7fc00000u);
+    return u2f((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__device__ __forceinline__ void lds_count_(unsigned int* lh, int b) {
+    if (b >= 0) atomicAdd(&lh[b], 1u);
+}
+
+// mx from the max fold's key (as tone_kernel reads it), mx / 100000.0f, and the
+// selection's start: rank k, or white = mx when no rank is selected
+__global__ void stats_init_kernel(const float* __restrict__ in, const DisplayScalars* __restrict__ sc,
+                                  StatsScalars* __restrict__ ss, unsigned int k, int have_max) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float mx = 0.0f;
+    if (have_max) {
+        const unsigned long long key = sc->max_key;
+        const float first = in[0];
+        mx = (is_nan_(first) || !key) ? first : in[0xffffffffu - (unsigned int)key];
+    }
+    ss->mx = mx;
+    ss->lo = div_x86nan_(mx, 100000.0f);
+    ss->white = mx;
+    ss->prefix = 0u;
+    ss->remaining = k;
+}
+
+// CImg get_histogram(nb, lo, mx) (CImg.h:33484-33495) in double
+__global__ __launch_bounds__(kPostBlock) void bucket_hist_kernel(const float* __restrict__ in, long long n, int nb,
+                                                                 const StatsScalars* __restrict__ ss,
+                                                                 unsigned int* __restrict__ hist) {
+    __shared__ unsigned int lh[kHistMaxBuckets];
+    for (int b = threadIdx.x; b < nb; b += kPostBlock) lh[b] = 0u;
+    __syncthreads();
+    const float lo = ss->lo, mx = ss->mx;
+    const bool lt = lo < mx;
+    const double vmin = (double)(lt ? lo : mx), vmax = (double)(lt ? mx : lo);
+    const double levels = (double)(unsigned int)nb, span = vmax - vmin;
+    const bool vec = ((uintptr_t)in & 15u) == 0;
+    const long long stride = (long long)gridDim.x * kPostBlock * 4;
+    for (long long base = (long long)blockIdx.x * kPostBlock * 4; base < n; base += stride) {
+        const long long i = base + (long long)threadIdx.x * 4;
+        float v[4];
+        load4_(in, i, n, vec, v);
+        for (int j = 0; j < 4; ++j) {
+            const double val = (double)v[j];
+            int b = -1;
+            if (i + j < n && val >= vmin && val <= vmax) {
+                const unsigned int q = val == vmax ? (unsigned int)nb - 1u : (unsigned int)((val - vmin) * levels / span);
+                b = q < (unsigned int)nb ? (int)q : -1;  // (q < nb always: val < vmax by an f32 ulp)
+            }
+            lds_count_(lh, b);
+        }
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < nb; b += kPostBlock) {
+        const unsigned int c = lh[b];
+        if (c) atomicAdd(&hist[b], c);
+    }
+}
+
+// one digit of the keys that match the prefix: bits [shift, shift + bits)
+__global__ __launch_bounds__(kPostBlock) void select_hist_kernel(const float* __restrict__ in, long long n, int shift,
+                                                                 int bits, const StatsScalars* __restrict__ ss,
+                                                                 unsigned int* __restrict__ counts) {
+    __shared__ unsigned int lh[kSelDigits];
+    const int nd = 1 << bits;
+    for (int d = threadIdx.x; d < nd; d += kPostBlock) lh[d] = 0u;
+    __syncthreads();
+    const unsigned int prefix = ss->prefix;
+    const unsigned int above = shift + bits >= 32 ? 0u : ~0u << (shift + bits);
+    const bool vec = ((uintptr_t)in & 15u) == 0;
+    const long long stride = (long long)gridDim.x * kPostBlock * 4;
+    for (long long base = (long long)blockIdx.x * kPostBlock * 4; base < n; base += stride) {
+        const long long i = base + (long long)threadIdx.x * 4;
+        float v[4];
+        load4_(in, i, n, vec, v);
+        for (int j = 0; j < 4; ++j) {
+            const unsigned int key = sel_key_(v[j]);
+            const bool hit = i + j < n && (key & above) == prefix;
+            lds_count_(lh, hit ? (int)((key >> shift) & (unsigned int)(nd - 1)) : -1);
+        }
+    }
+    __syncthreads();
+    for (int d = threadIdx.x; d < nd; d += kPostBlock) {
+        const unsigned int c = lh[d];
+        if (c) atomicAdd(&counts[d], c);
+    }
+}
+
+// one workgroup: the digit whose counts hold the remaining rank; last pass:
+// the key is complete and the white point is its float
+__global__ __launch_bounds__(kPostBlock) void select_scan_kernel(const unsigned int* __restrict__ counts, int shift,
+                                                                 int bits, int last, StatsScalars* __restrict__ ss) {
+    __shared__ unsigned int part[kPostBlock];
+    const int nd = 1 << bits, per = (nd + kPostBlock - 1) / kPostBlock;
+    const int lo = min((int)threadIdx.x * per, nd), hi = min(lo + per, nd);
+    const unsigned int rank = ss->remaining, prefix = ss->prefix;
+    unsigned int s = 0;
+    for (int d = lo; d < hi; ++d) s += counts[d];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned int acc = 0;
+        for (int t = 0; t < kPostBlock; ++t) {
+            const unsigned int v = part[t];
+            part[t] = acc;
+            acc += v;
+        }
+    }
+    __syncthreads();
+    unsigned int off = part[threadIdx.x];
+    if (rank >= off && rank - off < s)  // exactly one thread: rank < the sum of all counts
+        for (int d = lo; d < hi; ++d) {
+            const unsigned int c = counts[d];
+            if (rank - off < c) {
+                const unsigned int key = prefix | ((unsigned int)d << shift);
+                ss->prefix = key;
+                ss->remaining = rank - off;
+                if (last) ss->white = sel_unkey_(key);
+                break;
+            }
+            off += c;
+        }
+}
+
+// tone_kernel with the white point of StatsScalars in place of the max fold
+__global__ __launch_bounds__(kPostBlock) void tone_white_kernel(const float* __restrict__ in, float* __restrict__ tone,
+                                                                long long n, float p,
+                                                                const StatsScalars* __restrict__ ss,
+                                                                DisplayScalars* __restrict__ sc) {
+    __shared__ unsigned int red[kPostWaves];
+    const float white = ss->white;
+    const long long i = ((long long)blockIdx.x * kPostBlock + threadIdx.x) * 4;
+    float v[4];
+    load4_(in, i, n, ((uintptr_t)in & 15u) == 0, v);
+    unsigned int hi = 0u, lo_inv = 0u;
+    for (int j = 0; j < 4; ++j) {
+        const float w = powf_(div_x86nan_(v[j], white), p);
+        v[j] = w < 0.0f ? 0.0f : (w > 1.0f ? 1.0f : w);
+        if (i + j < n && !is_nan_(v[j])) {
+            hi = max(hi, f2u(v[j]));
+            lo_inv = max(lo_inv, ~f2u(v[j]));
+        }
+    }
+    if (((uintptr_t)tone & 15u) == 0 && i + 3 < n) {
+        *reinterpret_cast<float4*>(tone + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int j = 0; j < 4; ++j)
+            if (i + j < n) tone[i + j] = v[j];
+    }
+    hi = block_max_(hi, red);
+    lo_inv = block_max_(lo_inv, red);
+    if (threadIdx.x == 0) {
+        if (hi) atomicMax(&sc->tone_max, hi);
+        if (lo_inv) atomicMax(&sc->tone_min_inv, lo_inv);
+    }
+}
+
+__global__ void stats_out_kernel(const StatsScalars* __restrict__ ss, float* __restrict__ stats) {
+    const unsigned int t = threadIdx.x;
+    if (t < 4 && blockIdx.x == 0) stats[t] = t == 0 ? ss->mx : (t == 1 ? ss->lo : (t == 2 ? ss->white : 0.0f));
+}
+
 // powf_'s stated domain for y (ipt_math.h)
 bool powf_y_ok(float y) { return isfinite_(y) && y > 0.0f && y != std::trunc(y); }
 
@@ -366,6 +572,21 @@ int display_check(ipt_ctx* ctx, const ipt_display_params* p, const float* pixels
         return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_display: glare on images up to 4096 x 4096");
     if ((long long)p->width * p->height > (1ll << 31) || p->flags != 0 || !isfinite_(p->glare_cutoff))
         return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_display: at most 2^31 pixels, finite cutoff, flags 0");
+    return IPT_OK;
+}
+
+// the argument rules of ipt_display_stats / ipt_display_stats_device:
+// display_check's (no output is mandatory here) and the histogram's
+int stats_check(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* pixels, const uint32_t* hist) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!p || !pixels || p->width <= 0 || p->height <= 0 || !(p->glare_cutoff >= 0.0f) || p->hist_buckets < 0 ||
+        p->hist_buckets > kHistMaxBuckets || (p->hist_buckets > 0 && !hist))
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_display_stats: bad arguments");
+    if (p->glare_cutoff > 0.0f && (p->width > 4096 || p->height > 4096))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_display_stats: glare on images up to 4096 x 4096");
+    if ((long long)p->width * p->height > (1ll << 31) || p->flags != 0 || !isfinite_(p->glare_cutoff))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
+                                      "ipt_display_stats: at most 2^31 pixels, finite cutoff, flags 0");
     return IPT_OK;
 }
 
@@ -524,6 +745,133 @@ int ipt_display(ipt_ctx* ctx, const ipt_display_params* p, const float* pixels, 
     return IPT_OK;
 }
 
+int ipt_display_stats_device(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* dev_pixels,
+                             float* dev_processed, float* dev_tone, uint8_t* dev_gray8, uint32_t* dev_hist,
+                             float* dev_stats, void* hip_stream) {
+    if (const int rc = stats_check(ctx, p, dev_pixels, dev_hist)) return rc;
+    const bool glare = p->glare_cutoff > 0.0f;
+    const long long n = (long long)p->width * p->height;
+    const int nb = p->hist_buckets;
+    // what was asked for decides what runs
+    const bool want_tone = dev_tone || dev_gray8;
+    const bool select = p->white_rank >= 0 && p->white_rank < n && (want_tone || dev_stats);
+    const bool want_max = nb > 0 || dev_stats || (want_tone && !select);
+    const bool want_image = want_max || select || want_tone;  // the glare output is read at all
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    const bool run_glare = glare && (want_image || dev_processed);
+    const size_t nblk = (size_t)((n + kCompactSpan - 1) / kCompactSpan);
+    const size_t need_bright = run_glare ? (size_t)n : 0, need_blocks = run_glare ? nblk : 0;
+    const size_t need_processed = run_glare && !dev_processed ? (size_t)n : 0;
+    const size_t need_tone = dev_gray8 && !dev_tone ? (size_t)n : 0;
+    if (!S.done || !S.scalars || !S.stats || need_bright > S.bright_cap || need_blocks > S.blocks_cap ||
+        need_processed > S.processed_cap || need_tone > S.tone_cap) {
+        // (first call or a larger image: the only path that allocates or waits)
+        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
+        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+        size_t one = 0;
+        if (!S.scalars)
+            if (const int rc = post_grow(ctx, S.scalars, one, 1, sizeof(DisplayScalars))) return rc;
+        if (!S.stats)
+            if (const int rc = post_grow(ctx, S.stats, one, 1, sizeof(StatsScalars))) return rc;
+        if (need_bright > S.bright_cap)
+            if (const int rc = post_grow(ctx, S.bright, S.bright_cap, need_bright, sizeof(Bright))) return rc;
+        if (need_blocks > S.blocks_cap)
+            if (const int rc = post_grow(ctx, S.blocks, S.blocks_cap, need_blocks, sizeof(unsigned int))) return rc;
+        if (need_processed > S.processed_cap)
+            if (const int rc = post_grow(ctx, S.processed, S.processed_cap, need_processed, sizeof(float))) return rc;
+        if (need_tone > S.tone_cap)
+            if (const int rc = post_grow(ctx, S.tone, S.tone_cap, need_tone, sizeof(float))) return rc;
+    }
+    // the scratch is shared: a call on another stream runs after the previous one
+    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
+    DisplayScalars* sc = static_cast<DisplayScalars*>(S.scalars);
+    StatsScalars* ss = static_cast<StatsScalars*>(S.stats);
+    POSTCHECK(ctx, hipMemsetAsync(sc, 0, sizeof(DisplayScalars), st));
+    if (select) POSTCHECK(ctx, hipMemsetAsync(ss->digits, 0, sizeof(ss->digits[0]) * kSelPasses, st));
+    if (nb > 0) POSTCHECK(ctx, hipMemsetAsync(dev_hist, 0, (size_t)nb * sizeof(uint32_t), st));
+    const float* processed = dev_pixels;
+    if (run_glare) {
+        Bright* bright = static_cast<Bright*>(S.bright);
+        float* out = dev_processed ? dev_processed : S.processed;
+        const float cutoff = p->glare_cutoff;
+        hipLaunchKernelGGL(bright_count_kernel, dim3((unsigned)nblk), dim3(kPostBlock), 0, st, dev_pixels, n, cutoff,
+                           S.blocks);
+        hipLaunchKernelGGL(bright_scan_kernel, dim3(1), dim3(kPostBlock), 0, st, S.blocks, (int)nblk, sc);
+        hipLaunchKernelGGL(bright_scatter_kernel, dim3((unsigned)nblk), dim3(kPostBlock), 0, st, dev_pixels, p->width, n,
+                           cutoff, (const unsigned int*)S.blocks, bright);
+        dim3 grid((p->width + kPostBlock - 1) / kPostBlock, p->height);
+        hipLaunchKernelGGL(glare_kernel, grid, dim3(kPostBlock), 0, st, dev_pixels, out, p->width, p->height,
+                           (const Bright*)bright, 0, cutoff, (const unsigned int*)&sc->nb);
+        processed = out;
+    } else if (dev_processed) {
+        POSTCHECK(ctx, hipMemcpyAsync(dev_processed, dev_pixels, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    const unsigned int quads = (unsigned int)((n + 4ll * kPostBlock - 1) / (4ll * kPostBlock));
+    // the histograms' grid follows the device, not the image
+    const unsigned int hgrid = std::min<unsigned int>(quads, (unsigned)(std::max(ipt_internal::ctx_cus(ctx), 1) * kStatsBlocksPerCu));
+    if (want_max) hipLaunchKernelGGL(image_max_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, n, sc);
+    if (want_image)
+        hipLaunchKernelGGL(stats_init_kernel, dim3(1), dim3(64), 0, st, processed, (const DisplayScalars*)sc, ss,
+                           select ? (unsigned int)p->white_rank : 0u, want_max ? 1 : 0);
+    if (nb > 0)
+        hipLaunchKernelGGL(bucket_hist_kernel, dim3(hgrid), dim3(kPostBlock), 0, st, processed, n, nb,
+                           (const StatsScalars*)ss, dev_hist);
+    if (select)
+        for (int pass = 0, shift = 32; pass < kSelPasses; ++pass) {
+            shift -= kSelBits[pass];
+            hipLaunchKernelGGL(select_hist_kernel, dim3(hgrid), dim3(kPostBlock), 0, st, processed, n, shift,
+                               kSelBits[pass], (const StatsScalars*)ss, ss->digits[pass]);
+            hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kPostBlock), 0, st,
+                               (const unsigned int*)ss->digits[pass], shift, kSelBits[pass],
+                               pass == kSelPasses - 1 ? 1 : 0, ss);
+        }
+    if (want_tone) {
+        float* tone = dev_tone ? dev_tone : S.tone;
+        const float inv_gamma = 2.2f;
+        const float gamma = (float)(double)(1.0f / inv_gamma);  // tone_map's exponent (gui.cpp:11-16)
+        hipLaunchKernelGGL(tone_white_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, tone, n, gamma,
+                           (const StatsScalars*)ss, sc);
+        if (dev_gray8)
+            hipLaunchKernelGGL(gray8_kernel, dim3(quads), dim3(kPostBlock), 0, st, (const float*)tone, dev_gray8, n,
+                               (const DisplayScalars*)sc);
+    }
+    if (dev_stats) hipLaunchKernelGGL(stats_out_kernel, dim3(1), dim3(64), 0, st, (const StatsScalars*)ss, dev_stats);
+    POSTCHECK(ctx, hipGetLastError());
+    POSTCHECK(ctx, hipEventRecord(S.done, st));
+    S.used = true;
+    S.last_stream = st;
+    return IPT_OK;
+}
+
+int ipt_display_stats(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* pixels, float* processed,
+                      float* tone, uint8_t* gray8, uint32_t* hist, float* stats) {
+    if (const int rc = stats_check(ctx, p, pixels, hist)) return rc;
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = ipt_internal::ctx_stream(ctx);
+    const size_t n = (size_t)p->width * p->height, nb = (size_t)p->hist_buckets;
+    DevBuf<float> din, dproc, dtone, dstats;
+    DevBuf<uint8_t> dgray;
+    DevBuf<uint32_t> dhist;
+    POSTCHECK(ctx, hipMalloc(&din.p, n * sizeof(float)));
+    if (processed) POSTCHECK(ctx, hipMalloc(&dproc.p, n * sizeof(float)));
+    if (tone) POSTCHECK(ctx, hipMalloc(&dtone.p, n * sizeof(float)));
+    if (gray8) POSTCHECK(ctx, hipMalloc(&dgray.p, n));
+    if (nb) POSTCHECK(ctx, hipMalloc(&dhist.p, nb * sizeof(uint32_t)));
+    if (stats) POSTCHECK(ctx, hipMalloc(&dstats.p, 4 * sizeof(float)));
+    POSTCHECK(ctx, hipMemcpyAsync(din.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (const int rc = ipt_display_stats_device(ctx, p, din.p, dproc.p, dtone.p, dgray.p, dhist.p, dstats.p, st))
+        return rc;
+    if (processed) POSTCHECK(ctx, hipMemcpyAsync(processed, dproc.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (tone) POSTCHECK(ctx, hipMemcpyAsync(tone, dtone.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (gray8) POSTCHECK(ctx, hipMemcpyAsync(gray8, dgray.p, n, hipMemcpyDeviceToHost, st));
+    if (nb) POSTCHECK(ctx, hipMemcpyAsync(hist, dhist.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (stats) POSTCHECK(ctx, hipMemcpyAsync(stats, dstats.p, 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    POSTCHECK(ctx, hipStreamSynchronize(st));
+    return IPT_OK;
+}
+
 int ipt_powf_host(const float* x, float y, float* out, int64_t n) {
     if (!x || !out || n < 0) return IPT_E_INVALID;
     if (!powf_y_ok(y)) return IPT_E_UNSUPPORTED;
@@ -572,7 +920,7 @@ int post_wait(ipt_ctx* ctx) {
 
 void post_release(ipt_ctx* ctx) {
     PostScratch& S = ctx_post(ctx);
-    for (void* b : {S.bright, (void*)S.blocks, S.scalars, (void*)S.processed, (void*)S.tone})
+    for (void* b : {S.bright, (void*)S.blocks, S.scalars, S.stats, (void*)S.processed, (void*)S.tone})
         if (b) (void)hipFree(b);
     if (S.done) (void)hipEventDestroy(S.done);
     S = PostScratch{};

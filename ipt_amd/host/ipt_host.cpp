@@ -512,6 +512,40 @@ std::vector<uint8_t> GpuRenderer::display(const GridRenderPlane& plane, float gl
     return out;
 }
 
+namespace {
+DisplayStats run_display_stats(ipt_ctx* ctx, const std::vector<float>& pixels, size_t width, size_t height,
+                               float glare_cutoff, int buckets, int64_t white_rank) {
+    ipt_display_stats_params q{};
+    q.width = (int32_t)width;
+    q.height = (int32_t)height;
+    q.glare_cutoff = glare_cutoff;
+    q.hist_buckets = buckets;
+    q.white_rank = white_rank;
+    DisplayStats out;
+    out.gray8.resize(pixels.size());
+    out.hist.resize(buckets > 0 ? (size_t)buckets : 0);
+    float stats[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    check(ctx, ipt_display_stats(ctx, &q, pixels.data(), nullptr, nullptr, out.gray8.data(),
+                                 buckets > 0 ? out.hist.data() : nullptr, stats));
+    out.max = stats[0];
+    out.hist_min = stats[1];
+    out.white = stats[2];
+    return out;
+}
+}  // namespace
+
+DisplayStats GpuRenderer::display_stats(const GridRenderPlane& plane, float glare_cutoff, int buckets,
+                                        int64_t white_rank) {
+    check_plane(plane);
+    return run_display_stats(ctx_, plane.pixels, plane.width, plane.height, glare_cutoff, buckets, white_rank);
+}
+
+DisplayStats GpuRenderer::display_stats(const GuiRenderPlane& plane, float glare_cutoff, int buckets,
+                                        int64_t white_rank) {
+    check_plane(plane);
+    return run_display_stats(ctx_, plane.pixels, plane.width, plane.height, glare_cutoff, buckets, white_rank);
+}
+
 void render_samples_gpu(const Scene& scene, GridRenderPlane& plane, const RenderParams& p, int device) {
     GpuRenderer r(device);
     r.upload(scene);
@@ -628,6 +662,60 @@ std::vector<float> tone_map(const GridRenderPlane& plane) {
         out[i] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
     }
     return out;
+}
+
+std::vector<float> tone_map(const GridRenderPlane& plane, float white) {
+    const float inv_gamma = 2.2f;
+    const float p = (float)(double)(1.0f / inv_gamma);
+    std::vector<float> out(plane.pixels.size());
+    for (size_t i = 0; i < out.size(); ++i) {
+        float v = plane.pixels[i] / white;
+        v = std::pow(v, p);
+        out[i] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
+    }
+    return out;
+}
+
+std::vector<uint32_t> histogram(const GridRenderPlane& plane, int buckets) {
+    std::vector<uint32_t> res(buckets > 0 ? (size_t)buckets : 0, 0u);
+    if (res.empty() || plane.pixels.empty()) return res;
+    float mx = plane.pixels[0];
+    for (float v : plane.pixels) mx = std::max(mx, v);
+    // get_histogram(nb_levels, min_value, max_value) with Gui's arguments
+    const unsigned int nb_levels = (unsigned int)buckets;
+    const float min_value = mx / 100000.0f, max_value = mx;
+    const double vmin = (double)(min_value < max_value ? min_value : max_value),
+                 vmax = (double)(min_value < max_value ? max_value : min_value);
+    for (const float val : plane.pixels)
+        if (val >= vmin && val <= vmax)
+            ++res[val == vmax ? nb_levels - 1 : (unsigned int)((val - vmin) * nb_levels / (vmax - vmin))];
+    return res;
+}
+
+float kth_smallest(const GridRenderPlane& plane, uint64_t k) {
+    if (plane.pixels.empty()) return 0.0f;
+    if (k >= plane.pixels.size()) {  // CImg: max()
+        float mx = plane.pixels[0];
+        for (float v : plane.pixels) mx = std::max(mx, v);
+        return mx;
+    }
+    // the stated total order as unsigned keys: negatives reversed, NaN on top
+    std::vector<uint32_t> keys(plane.pixels.size());
+    for (size_t i = 0; i < keys.size(); ++i) {
+        uint32_t u;
+        std::memcpy(&u, &plane.pixels[i], 4);
+        keys[i] = (u & 0x7fffffffu) > 0x7f800000u ? 0xffffffffu : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+    }
+    std::nth_element(keys.begin(), keys.begin() + (std::ptrdiff_t)k, keys.end());
+    const uint32_t key = keys[(size_t)k];
+    const uint32_t u = key == 0xffffffffu ? 0x7fc00000u : ((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+    float out;
+    std::memcpy(&out, &u, 4);
+    return out;
+}
+
+uint64_t white_rank_for(size_t width, size_t height, double fraction) {
+    return (uint64_t)((double)(int)(width * height) * fraction);
 }
 
 std::vector<uint8_t> to_gray8(const GridRenderPlane& plane) {

@@ -208,6 +208,14 @@ struct FlatScene {
 };
 FlatScene flatten(const Scene& s);  // throws IptError(IPT_E_UNSUPPORTED)
 
+// What GpuRenderer::display_stats returns: the 8-bit picture, the histogram
+// counts and {max, max / 100000.0f, white point} of the processed image.
+struct DisplayStats {
+    std::vector<uint8_t> gray8;
+    std::vector<uint32_t> hist;
+    float max = 0.0f, hist_min = 0.0f, white = 0.0f;
+};
+
 class GpuRenderer {
    public:
     explicit GpuRenderer(int device = 0);
@@ -237,6 +245,14 @@ class GpuRenderer {
     // glare_cutoff when it is > 0, tone map, normalize(0, 255), 8-bit cast.
     // With glare_cutoff 0 the bytes equal to_gray8(plane).
     std::vector<uint8_t> display(const GridRenderPlane& plane, float glare_cutoff = 0.0f);
+    // The same with Gui::updateDisplay's statistics (ipt_display_stats): the
+    // histogram window's counts (gui.cpp:83-88; buckets 0: none) and the white
+    // point of normalize()'s kth_smallest remedy (gui.cpp:13; white_rank < 0:
+    // the maximum, and gray8 then equals display()'s).
+    DisplayStats display_stats(const GridRenderPlane& plane, float glare_cutoff = 0.0f, int buckets = 400,
+                               int64_t white_rank = -1);
+    DisplayStats display_stats(const GuiRenderPlane& plane, float glare_cutoff = 0.0f, int buckets = 400,
+                               int64_t white_rank = -1);
     ipt_ctx* handle() const { return ctx_; }
 
    private:
@@ -279,6 +295,18 @@ class MultiGpuRenderer {
 // --------------------------------------------------------------- output
 // Gui's display normalisation (gui.cpp:11-16): (v / max)^(1/2.2), cut to [0, 1].
 std::vector<float> tone_map(const GridRenderPlane& plane);
+// ... with a chosen white point in place of the maximum (the remedy noted at gui.cpp:13)
+std::vector<float> tone_map(const GridRenderPlane& plane, float white);
+// Gui::updateDisplay's histogram window (gui.cpp:83-88): CImg
+// get_histogram(buckets, max / 100000.0f, max) of the plane (CImg.h:33484-33495).
+std::vector<uint32_t> histogram(const GridRenderPlane& plane, int buckets = 400);
+// CImg kth_smallest(k) (CImg.h:29441-29473): the element at 0-based index k of
+// the ascending order, the maximum for k >= size; -0 before +0, NaNs after
+// +inf (a rank among them gives the quiet NaN 0x7fc00000), as ipt_capi.h states.
+float kth_smallest(const GridRenderPlane& plane, uint64_t k);
+// The reference's rank expression, arg.width()*arg.height()*0.95 (gui.cpp:13),
+// for any fraction: (uint64_t)((int)(width*height) * fraction), in double.
+uint64_t white_rank_for(size_t width, size_t height, double fraction);
 // Gui::save (gui.cpp:133-135): tone map, CImg normalize(0, 255) (CImg.h
 // normalize(a,b): (v - min)/(max - min)*255), then the 8-bit PNG writer's
 // (unsigned char) cast. Written as a grayscale 8-bit PNG.

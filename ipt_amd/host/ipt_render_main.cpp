@@ -11,7 +11,8 @@
 //              [--devices 0,1,...,7 [--tile-rows 16]]
 //              [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]
 //              [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out glare.pfm]
-//              [--gpu-display] [--gui-plane]
+//              [--gpu-display] [--gui-plane] [--white-percentile F]
+//              [--histogram hist.txt [--hist-buckets 400]]
 //
 // --gui-plane renders into the Gui's plane (GuiRenderPlane, Gui::addRay's row
 // map, gui.cpp:165-182) instead of a GridRenderPlane: the plane the reference
@@ -24,6 +25,13 @@
 // pipeline on the GPU, with the --glare cutoff's bloom when one is given, as
 // Gui::updateDisplay shows it) instead of the host's to_gray8; without
 // --glare the file is the same bytes.
+// --white-percentile F (with --gpu-display) divides by the value at rank
+// (int)(W*H)*F of the displayed image instead of its maximum, the remedy the
+// reference notes beside normalize() (gui.cpp:13; F = 0.95 is its constant):
+// the PNG's bytes come from GpuRenderer::display_stats.
+// --histogram writes the counts of Gui::updateDisplay's histogram window
+// (gui.cpp:83-88, --hist-buckets of them, 400 as the Gui's) of the displayed
+// image, one per line, computed on the GPU by the same call.
 // --smooth applies GridRenderPlane::smooth(SIDE) on the GPU before output;
 // --glare writes Gui's glare bloom of the plane (gui.cpp:28-52, GPU) as PFM;
 // --pgm writes main.cpp's contrast/gamma PGM (main.cpp:297-309).
@@ -51,13 +59,16 @@ namespace {
                  "                  [--devices I,J,... [--tile-rows 16]]\n"
                  "                  [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]\n"
                  "                  [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out F.pfm]\n"
-                 "                  [--gpu-display] [--gui-plane]\n");
+                 "                  [--gpu-display] [--gui-plane] [--white-percentile F]\n"
+                 "                  [--histogram hist.txt [--hist-buckets 400]]\n");
     std::exit(2);
 }
 }  // namespace
 
 int main(int argc, char** argv) {
-    std::string scene_name = "box", out = "result.png", pfm, counts, pgm, glare_out;
+    std::string scene_name = "box", out = "result.png", pfm, counts, pgm, glare_out, hist_out;
+    double white_percentile = -1.0;
+    long hist_buckets = 400;
     long smooth = 0;
     bool gpu_display = false, gui_plane = false;
     double glare = -1.0;
@@ -96,11 +107,17 @@ int main(int argc, char** argv) {
         else if (a == "--glare-out") glare_out = val();
         else if (a == "--gpu-display") gpu_display = true;
         else if (a == "--gui-plane") gui_plane = true;
+        else if (a == "--white-percentile") white_percentile = std::atof(val());
+        else if (a == "--histogram") hist_out = val();
+        else if (a == "--hist-buckets") hist_buckets = std::atol(val());
         else usage(("unknown option " + a).c_str());
     }
     if (width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || n_rays < 0 || depth < 0) usage("bad sizes");
     if (gui_plane && smooth > 0) usage("--smooth is GridRenderPlane::smooth; the Gui plane (--gui-plane) has none");
     if (gui_plane && !pgm.empty()) usage("--pgm is main.cpp's writer for a GridRenderPlane; not with --gui-plane");
+    if (white_percentile >= 0.0 && !gpu_display) usage("--white-percentile needs --gpu-display");
+    if (!(white_percentile < 0.0) && !(white_percentile <= 1.0)) usage("--white-percentile takes a fraction in [0, 1]");
+    if (hist_buckets < 1 || hist_buckets > 4096) usage("--hist-buckets takes 1..4096");
     try {
         const ipt::Scene scene = ipt::make_scene_by_name(scene_name);
         if (devices.empty()) devices.push_back((int)device);
@@ -143,7 +160,19 @@ int main(int argc, char** argv) {
             ipt::write_pfm(glare_out, g);
         }
         if (!pgm.empty()) ipt::write_pgm(pgm, plane);
-        if (!out.empty())
+        if (white_percentile >= 0.0 || !hist_out.empty()) {
+            // one call gives the picture, the histogram and the white point
+            const int64_t rank =
+                white_percentile >= 0.0 ? (int64_t)ipt::white_rank_for(plane.width, plane.height, white_percentile) : -1;
+            const ipt::DisplayStats ds = gpu.display_stats(plane, gpu_display && glare > 0.0 ? (float)glare : 0.0f,
+                                                           hist_out.empty() ? 0 : (int)hist_buckets, rank);
+            if (!hist_out.empty()) {
+                std::ofstream f(hist_out);
+                for (uint32_t c : ds.hist) f << c << "\n";
+            }
+            if (!out.empty())
+                ipt::write_png_gray8(out, plane.width, plane.height, gpu_display ? ds.gray8 : ipt::to_gray8(plane));
+        } else if (!out.empty())
             ipt::write_png_gray8(out, plane.width, plane.height,
                                  gpu_display ? gpu.display(plane, glare > 0.0 ? (float)glare : 0.0f)
                                              : ipt::to_gray8(plane));
