@@ -945,13 +945,18 @@ __device__ __forceinline__ void sphere_grid_walk_wave2(const KParams& kp, bool w
 
 // Nearest geometry hit for both geometry kinds. prim: 0..4 plane, 5 the
 // r=0.5 sphere, 6+i extra sphere i (original index), -1 miss.
-template <bool COUNT, int GEOM>
-__device__ __forceinline__ float trace_geometry(const KParams& kp, vec3 o, vec3 d, int* prim, uint32_t& c_nodes,
-                                                uint32_t& c_tests) {
+template <bool COUNT, int GEOM, bool NEAREST>
+__device__ __forceinline__ float trace_geometry(const KParams& kp, vec3 o, vec3 d, int* prim, vec3* hit,
+                                                uint32_t& c_nodes, uint32_t& c_tests) {
     // kp.box_inrange: every ray origin (camera, wall/floor hits, listed spheres)
     // lies within 2^39, so the planes' divisions take the range-free sequence
-    if (GEOM == IPT_GEOM_SPHERE_IN_BOX)
+    // (*hit: the box's hit point o + d*t where NEAREST, see resolve's kBoxHit)
+    if (GEOM == IPT_GEOM_SPHERE_IN_BOX) {
+        if (NEAREST)
+            return (IPT_BOXDIV && kp.box_inrange) ? trace_box_hit<true>(o, d, prim, hit)
+                                                  : trace_box_hit<false>(o, d, prim, hit);
         return (IPT_BOXDIV && kp.box_inrange) ? trace_box<true>(o, d, prim) : trace_box<false>(o, d, prim);
+    }
     if (GEOM == IPT_GEOM_FLOOR) {  // GeometryFloor.cpp:11-13
         const float t = box_plane_t(o.z, d.z, -1.0f, o, d);
         *prim = t == inf_() ? -1 : 0;
@@ -1100,6 +1105,13 @@ enum { kLightsOne = 1, kLightsLds = 2, kLightsGlobal = 3, kLightsAny = 4, kLight
 // 1024-thread workgroup per CU (block_of), chosen when the LDS fits (+5 % C5)
 __host__ __device__ constexpr bool grid_lights(int lm) { return lm >= kLightsGridA10 && lm <= kLightsGridA01L; }
 __host__ __device__ constexpr bool lattice_a10(int lm) { return lm == kLightsGridA10 || lm == kLightsGridA10L; }
+// the instances whose box trace takes the nearest-candidate planes (ipt_knobs.h
+// IPT_BOX_NEAREST): the box with one light or a light list. The lattice
+// instances, at their SGPR limit, lose 0.2 % with it and the sphere-list
+// instances' walls gain nothing measurable: both keep the full form.
+__host__ __device__ constexpr bool box_nearest(int lm, int geom) {
+    return IPT_BOX_NEAREST && geom == IPT_GEOM_SPHERE_IN_BOX && !grid_lights(lm);
+}
 __host__ __device__ constexpr bool lax_in_lds(int lm) { return lm == kLightsGridA10L || lm == kLightsGridA01L; }
 __host__ __device__ constexpr bool global_lights(int lm) { return lm == kLightsGlobal || grid_lights(lm); }
 // kLightsOneA10 / A01: the single light is an axis-aligned AreaLight
@@ -1380,6 +1392,8 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     // a step costs the budget, not the longest walk of the workgroup.
     constexpr bool kRes = resumable_geom(GEOM);
     constexpr bool kResL = resumable_lights(LMODE, GEOM);
+    // the box instances' direct trace hands its hit point to resolve (box_hitp)
+    constexpr bool kBoxHit = !kRes && !kResL && GEOM == IPT_GEOM_SPHERE_IN_BOX && box_nearest(LMODE, GEOM);
     // the frame-entry prefetch pays where every lane iterates every step; in the
     // resumable instances (lanes parked in walks) it measured -5 % on C5
     constexpr int kFramePf = (kRes || kResL) ? 0 : IPT_FRAME_PF;
@@ -2051,6 +2065,10 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         // --------------------------------------------- phase 4: trace + resolve
         // the child's value (main.cpp:100-143) from its traces, then push it,
         // add it to the current node's sum, or finish the path
+        // kBoxHit: the trace already holds the winner's point box_hitp = o + d*t
+        // wherever prim >= 0, the only place si_pos is observed (uninitialised
+        // like the ray: no merge moves)
+        vec3 box_hitp;
         auto resolve = [&](bool traced, float t, int prim, vec3 o, vec3 d, int depth, bool iter, float mult,
                            bool has_li, float li_y, float li_pow) {
             float cv = 0.0f;
@@ -2066,7 +2084,10 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     c_surf += has_si ? 1u : 0u;
                     c_light += has_li ? 1u : 0u;
                 }
-                si_pos = o + d * t;
+                if constexpr (kBoxHit)  // (no capture of box_hitp in the other instances)
+                    si_pos = box_hitp;
+                else
+                    si_pos = o + d * t;
                 // y = |li_pos - o|^2, computed by the caller
                 const vec3 ea = si_pos - o;
                 const float x = dot(ea, ea), y = li_y;
@@ -2205,7 +2226,8 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     float t = inf_();
                     if (xrdepth < kp.depth_max) {
                         IPT_PHASE(9);
-                        t = trace_geometry<COUNT, GEOM>(kp, xro, xrd, &prim, c_nodes, c_tests);
+                        vec3 hitp;
+                        t = trace_geometry<COUNT, GEOM, box_nearest(LMODE, GEOM)>(kp, xro, xrd, &prim, &hitp, c_nodes, c_tests);
                     }
                     const vec3 eb = xli_pos - xro;
                     resolve(xrdepth < kp.depth_max, t, prim, xro, xrd, xrdepth, xis_iter, mult, xhas_li, dot(eb, eb),
@@ -2410,7 +2432,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 float t = inf_();
                 if (rdepth < kp.depth_max) {
                     IPT_PHASE(9);
-                    t = trace_geometry<COUNT, GEOM>(kp, ro, rd, &prim, c_nodes, c_tests);
+                    t = trace_geometry<COUNT, GEOM, box_nearest(LMODE, GEOM)>(kp, ro, rd, &prim, &box_hitp, c_nodes, c_tests);
                     IPT_STAMP_AT(10);  // mixture value + geometry trace
                 }
                 const vec3 eb = li_pos - ro;

@@ -273,6 +273,110 @@ IPT_HD float trace_box_planes_only(vec3 o, vec3 d, int* prim) {
     *prim = none ? -1 : bi;
     return dnan ? inf_() : best;
 }
+
+// the largest of the numbers among a, b, c (fmaxf: a NaN operand is dropped; NaN only if all three are)
+IPT_HD float max3_nn_(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+
+// trace_box_planes_only with the hit point of the NEAREST candidate alone
+// (IPT_BOX_NEAREST). U_a is plane a's t after the rejections that need no hit
+// point (|d_a| < 1e-6, t < 1e-6, the y plane for d.y <= 0), m the scan's
+// winner over U ("nearer, or as near with a lower index") and p = o + d*U_m:
+//   * U_m = inf: every plane misses in the form above too;
+//   * every |p_c| <= 1: plane m passes its own tests there, every other
+//     accepted t is that plane's U_a >= U_m, and among equal t m has the
+//     lowest index -- m is the answer;
+//   * some p_c beyond the bound on d_c's side, s_c p_c > 1 with s_c = +1
+//     for d_c > 0 and -1 otherwise: t -> RN(o_c + RN(d_c t)) is monotone in t
+//     with d_c's sign (rounding is monotone; for a zero d_c it is constant,
+//     so either s_c serves), hence every plane with t' >= U_m fails the same
+//     bound: no hit. (s_c p_c is exact, and no product p_c d_c, which can
+//     underflow to -0, is asked for its sign; the largest of the three
+//     s_c p_c decides, a NaN among them counting as "not beyond" as in a
+//     compare of its own.)
+// Everything else -- a failing coordinate that moves inwards with t (a ray
+// from outside that crosses a plane's extension before it enters), any NaN in
+// U or p (a NaN p_c fails `|p_c| <= 1` and passes no `> 1`) -- takes the form
+// above behind one wave vote; a NaN direction component makes that p_c NaN
+// unless U_m = inf, so the dnan rule needs no test here.
+// *hit is the winner's point o + d*t (read only behind prim >= 0). *cls (the
+// host check's statistics) is the outcome: 0 no candidate, 1 the candidate
+// hits, 2 monotone miss, 3 the full form.
+template <bool INRANGE = false>
+IPT_HD float trace_box_planes_nearest(vec3 o, vec3 d, int* prim, vec3* hit, int* cls = nullptr) {
+    const bool xp = d.x > 0.0f, yp = d.y > 0.0f, zp = d.z > 0.0f;
+    const float sx = xp ? 1.0f : -1.0f, sy = yp ? 1.0f : -1.0f, sz = zp ? 1.0f : -1.0f;
+    auto cand = [](float oa, float da, float sgn, bool rej) {
+        const float dp = fabs_(da);
+        const float num = __builtin_fmaf(-sgn, oa, 1.0f);
+        const float t = INRANGE ? div_inrange_(num, dp) : div_(num, dp);
+        return (lt_1em6(dp) | lt_1em6(t) | rej) ? inf_() : t;
+    };
+    float best = cand(o.x, d.x, sx, false);
+    int bi = xp ? 0 : 3;
+    const float uy = cand(o.y, d.y, 1.0f, !yp);
+    const bool take_y = (uy < best) | ((uy == best) & (1 < bi) & (uy != inf_()));
+    best = take_y ? uy : best;
+    bi = take_y ? 1 : bi;
+    const float uz = cand(o.z, d.z, sz, false);
+    const int iz = zp ? 2 : 4;
+    const bool take_z = (uz < best) | ((uz == best) & (iz < bi) & (uz != inf_()));
+    best = take_z ? uz : best;
+    bi = take_z ? iz : bi;
+    vec3 p = v3(o.x + d.x * best, o.y + d.y * best, o.z + d.z * best);
+    const bool none = best == inf_();
+    const bool fail = !(fabs_(p.x) <= 1.0f) | !(fabs_(p.y) <= 1.0f) | !(fabs_(p.z) <= 1.0f);
+    const bool mono = max3_nn_(sx * p.x, sy * p.y, sz * p.z) > 1.0f;
+    const bool miss = none | mono;
+    best = miss ? inf_() : best;
+    bi = miss ? -1 : bi;
+    const bool fb = fail & !miss;
+    if (cls) *cls = none ? 0 : (mono ? 2 : (fb ? 3 : 1));
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_expect(__any(fb), 0))
+#endif
+        if (fb) {
+            best = trace_box_planes_only<INRANGE>(o, d, &bi);
+            p = v3(o.x + d.x * best, o.y + d.y * best, o.z + d.z * best);
+        }
+    *prim = bi;
+    *hit = p;
+    return best;
+}
+
+// sphere_t<true, INR> that also hands out its pos = o + d*t (the box
+// instances' hit point where the sphere wins: resolve reads it behind
+// prim >= 0 instead of forming the same expression again).
+template <bool INR>
+IPT_HD float box_sphere_t(float radius, vec3 o, vec3 d, vec3* hit) {
+    const float b = dot(o, d);
+    const float desc = INR ? 4.0f * (b * b - (dot(o, o) - radius * radius))
+                           : 4.0f * (b * b) - 4.0f * (dot(o, o) - radius * radius);
+    const float sd = INR ? sqrt_inrange_(desc) : sqrt_(desc);
+    const float m2b = -2.0f * b;
+    float t1 = (m2b - sd) * 0.5f;
+    float t2 = (m2b + sd) * 0.5f;
+    float t;
+    if (INR) {
+        // sd is finite (desc < 2^84) and >= 0 or NaN: then t1 <= t2 (rounding is
+        // monotone), so min(t1', t2') of the two roots after their rejection is
+        // t1 unless it is rejected, else t2'; with a NaN t1 both forms give t1
+        // (a NaN sd or b reaches both roots; desc < 0 is decided below; a NaN t2
+        // beside a rejected number t1 would need m2b = -inf, sd = +inf)
+        // (two selects on bitwise conditions: no exec-mask region)
+        const bool r1 = lt_1em6(t1), r2 = lt_1em6(t2);
+        t = r1 ? t2 : t1;
+        t = (r1 & r2) ? inf_() : t;
+    } else {
+        t1 = lt_1em6(t1) ? inf_() : t1;
+        t2 = lt_1em6(t2) ? inf_() : t2;
+        t = (t2 < t1) ? t2 : t1;
+    }
+    const vec3 pos = o + d * t;
+    const bool back = dot(pos, o - pos) <= 0.0f;
+    *hit = pos;
+    return (desc < 0.0f) ? inf_() : ((t == inf_()) ? t : (back ? inf_() : t));
+}
+
 template <bool INRANGE = false>
 IPT_HD float trace_box(vec3 o, vec3 d, int* prim) {
     int bi;
@@ -280,6 +384,19 @@ IPT_HD float trace_box(vec3 o, vec3 d, int* prim) {
     const float ts = sphere_t<true, INRANGE>(0.5f, o, d);
     if (ts < best) { best = ts; bi = 5; }
     *prim = bi;
+    return best;
+}
+// trace_box from the nearest-plane form, with the winner's point: the plane's
+// p where a plane wins, the sphere's pos where the sphere does.
+template <bool INRANGE = false>
+IPT_HD float trace_box_hit(vec3 o, vec3 d, int* prim, vec3* hit) {
+    int bi;
+    vec3 p, ps;
+    float best = trace_box_planes_nearest<INRANGE>(o, d, &bi, &p);
+    const float ts = box_sphere_t<INRANGE>(0.5f, o, d, &ps);
+    if (ts < best) { best = ts; bi = 5; p = ps; }
+    *prim = bi;
+    *hit = p;
     return best;
 }
 // FractalSpheres' acceptance "std::abs(dist) > 1e-6" (double literal):
