@@ -12,8 +12,9 @@
  * Conventions: plain pointers and sizes, no exceptions, every call returns
  * IPT_OK (0) or a negative IPT_E_* code, the message of the last failure is
  * available from ipt_last_error(). Calls are synchronous unless they take a
- * stream argument and say otherwise (ipt_render_device_async and
- * ipt_display_device return once their work is queued). One context per HIP device; contexts are independent, a
+ * stream argument and say otherwise (ipt_render_device_async, ipt_display_device,
+ * ipt_display_stats_device, ipt_smooth_device and ipt_pgm_device return once
+ * their work is queued). One context per HIP device; contexts are independent, a
  * single context is not reentrant. There is NO CPU fallback: without a usable
  * gfx950 device every rendering call fails with IPT_E_DEVICE.
  */
@@ -426,6 +427,98 @@ int ipt_display_stats(ipt_ctx* ctx, const ipt_display_stats_params* p, const flo
    library's host build of the code the kernels run. */
 int ipt_powf_host(const float* x, float y, float* out, int64_t n);
 int ipt_powf_device(ipt_ctx* ctx, const float* x, float y, float* out, int64_t n);
+
+/* ---- PGM output on the GPU (ABI 7 additions), bit-exact -------------------------
+   The reference's written output (main.cpp:291-309) for a plane that stays on
+   the device: GridRenderPlane::smooth(2) -> computeSmoothedMax(5) ->
+   n_val(v, max_value, 500, 0.6f) -> result.pgm (entry points and one struct
+   added; no layout changes).
+
+   ipt_smooth_device: ipt_smooth on device buffers, in stream order.
+     dev_out != NULL  GridRenderPlane::smooth(side): dev_out gets the filtered
+                      plane (pixels with x < side-1 or y < side-1 keep their
+                      input value). dev_out == dev_in is allowed (the context's
+                      scratch holds the copy the filter reads).
+     dev_out == NULL  computeSmoothedMax(side): no pixel is written.
+     dev_max          1 float, may be NULL: the reference's max_value, the
+                      running `accum > max` from 0 over the window means (a
+                      NaN never wins, an all-negative plane gives +0).
+   side 0 and a side larger than the image are valid: no pixel qualifies, the
+   maximum is 0 and the pixels are unchanged (copied when out of place).
+   Errors, all raised before a buffer is touched: a NULL ctx or dev_in, a
+   non-positive size, a negative side, or buffers that overlap other than
+   dev_out == dev_in: IPT_E_INVALID; side 1 (undefined behaviour in the
+   reference), a side above 64 (a queued kernel is bounded at 64^2 adds per
+   pixel; the reference uses 2 and 5) or more than 2^31 pixels:
+   IPT_E_UNSUPPORTED. */
+int ipt_smooth_device(ipt_ctx* ctx, const float* dev_in, float* dev_out /* NULL: computeSmoothedMax */, int width,
+                      int height, int side, float* dev_max /* 1 float, may be NULL */, void* hip_stream);
+
+/* ipt_pgm_device: the whole chain. width*height row-major buffers.
+     smoothed  the pixels n_val reads: smooth(smooth_side) of dev_pixels, or a
+               copy of them when smooth_side == 0
+     max_value the one n_val divides by; the reference's sequence decides (the
+               last stage that sets it wins), the first matching rule applies:
+                 1. max_side >= 2: computeSmoothedMax(max_side) of `smoothed`
+                 2. smooth_side >= 2: smooth's value
+                 3. dev_pixel_max != NULL: its fold from 0 with `>`
+                    (GridRenderPlane::max_value of an ipt_image's pixel_max)
+                 4. otherwise p->max_value as given, any float
+     gray8     ipt::n_val / main.cpp:225-235 per pixel, in f32:
+                 adj = v * contrast / max_value   (two operations, IEEE
+                       division, subnormals kept)
+                 adj = contrast < adj ? contrast : adj;  adj = adj < 1 ? 1 : adj
+                       (std::min / std::max exactly: a NaN adj stays)
+                 fn = logf(adj) / logf(contrast);  fn = powf(fn, gamma)
+                 n = (int)(256.0f * fn) clamped to 0..255; a NaN gives 0 (the
+                       x86 conversion yields INT_MIN, then max(0, .))
+               with glibc 2.35's logf and powf restated (ipt_math.h). E.g. with
+               contrast 500, gamma 0.6: max_value 0 gives 255 for every v > 0
+               and 0 for v <= 0 or NaN; an infinite or NaN max_value gives 0.
+     stats     {max_value used, logf(contrast), 0, 0}
+   dev_pixel_max, dev_smoothed, dev_gray8 and dev_stats may each be NULL, and a
+   stage nobody asked for is not run. dev_pixels (and dev_pixel_max) are only
+   read and may not overlap an output; outputs may not overlap each other.
+   Errors, all raised before a buffer is touched: a NULL that is not optional,
+   a non-positive size, a negative side or an overlap: IPT_E_INVALID; side 1, a
+   side above 64, flags != 0, more than 2^31 pixels, contrast not finite or not
+   > 1, gamma outside powf's domain here (finite, > 0, no integer):
+   IPT_E_UNSUPPORTED. */
+typedef struct ipt_pgm_params {
+    int32_t width, height;
+    int32_t smooth_side; /* 0: none; >= 2: GridRenderPlane::smooth(side) first (main.cpp: 2) */
+    int32_t max_side;    /* 0: none; >= 2: computeSmoothedMax(side) of the (smoothed) pixels (main.cpp: 5) */
+    float contrast;      /* main.cpp: 500 */
+    float gamma;         /* main.cpp: 0.6f */
+    float max_value;     /* used only by rule 4 */
+    uint32_t flags;      /* 0 */
+} ipt_pgm_params;
+
+/* Device buffers, any alignment a float / byte array may have. Stream and
+   scratch rules are ipt_display_device's (for both calls above): the work
+   runs on `hip_stream` (NULL = the context's stream) and the call returns once
+   it is queued; no value crosses to the host inside the call (the maxima,
+   max_value and logf(contrast) stay in device memory, where the next kernel
+   reads them); the scratch (32 B of scalars, 4 B per pixel when smooth runs
+   without dev_smoothed or in place) belongs to the context and grows to the
+   largest request, so a repeated call at the same size allocates, frees and
+   synchronises nothing; a call on another stream waits on the previous call's
+   event; ipt_render_wait, ipt_upload_scene and ipt_destroy wait for queued
+   calls. */
+int ipt_pgm_device(ipt_ctx* ctx, const ipt_pgm_params* p, const float* dev_pixels,
+                   const float* dev_pixel_max /* may be NULL */, float* dev_smoothed /* may be NULL */,
+                   uint8_t* dev_gray8 /* may be NULL */, float* dev_stats /* 4 floats, may be NULL */,
+                   void* hip_stream);
+/* Host buffers: the same kernels (and limits), synchronous. */
+int ipt_pgm(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const float* pixel_max, float* smoothed,
+            uint8_t* gray8, float* stats);
+/* Probes of the PGM chain's logf (ipt_math.h logf_, glibc 2.35's __logf_fma
+   restated): out[i] = logf(x[i]) for x in [1, FLT_MAX], host buffers. Outside
+   that domain (x < 1, negative, +inf, NaN) both return the quiet NaN
+   0x7fc00000 by definition, so that host and device agree there too.
+   ipt_logf_host is the library's host build of the code the kernels run. */
+int ipt_logf_host(const float* x, float* out, int64_t n);
+int ipt_logf_device(ipt_ctx* ctx, const float* x, float* out, int64_t n);
 
 /* ---- the path's DDF samplers, exactly as the kernels evaluate them -----------
    For sampler validation (the reference's chi^2 harness, check_ddf.cpp:114-203)

@@ -80,6 +80,11 @@ class DisplayStatsParams(C.Structure):  # ABI 7 additions
                 ("hist_buckets", C.c_int32), ("white_rank", C.c_int64), ("flags", C.c_uint32)]
 
 
+class PgmParams(C.Structure):  # ABI 7 additions
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("smooth_side", C.c_int32), ("max_side", C.c_int32),
+                ("contrast", C.c_float), ("gamma", C.c_float), ("max_value", C.c_float), ("flags", C.c_uint32)]
+
+
 ABI_VERSION = 7  # include/ipt_capi.h IPT_ABI_VERSION
 ABI_LAYOUT_COMPATIBLE = (3, 4, 5, 6, 7)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
 
@@ -104,6 +109,7 @@ EXPORTED_SYMBOLS = (
     "ipt_philox", "ipt_transfer_bytes",
     "ipt_display_device", "ipt_display", "ipt_powf_host", "ipt_powf_device",
     "ipt_display_stats_device", "ipt_display_stats",
+    "ipt_smooth_device", "ipt_pgm_device", "ipt_pgm", "ipt_logf_host", "ipt_logf_device",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -181,6 +187,13 @@ def load(path: str | os.PathLike | None = None):
     if hasattr(lib, "ipt_display_stats_device"):  # ABI 7 additions
         lib.ipt_display_stats_device.argtypes = [C.c_void_p, C.POINTER(DisplayStatsParams)] + [C.c_void_p] * 7
         lib.ipt_display_stats.argtypes = [C.c_void_p, C.POINTER(DisplayStatsParams)] + [C.c_void_p] * 6
+    if hasattr(lib, "ipt_pgm_device"):  # ABI 7 additions
+        lib.ipt_smooth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p]
+        lib.ipt_pgm_device.argtypes = [C.c_void_p, C.POINTER(PgmParams)] + [C.c_void_p] * 6
+        lib.ipt_pgm.argtypes = [C.c_void_p, C.POINTER(PgmParams)] + [C.c_void_p] * 5
+        lib.ipt_logf_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        lib.ipt_logf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     if path is None:
         _lib = lib
     return lib
@@ -241,6 +254,15 @@ def make_display_stats_params(width, height, glare_cutoff=0.0, hist_buckets=0, w
     p = DisplayStatsParams()
     p.width, p.height, p.glare_cutoff, p.flags = width, height, glare_cutoff, flags
     p.hist_buckets, p.white_rank = hist_buckets, white_rank
+    return p
+
+
+def make_pgm_params(width, height, smooth_side=0, max_side=0, contrast=500.0, gamma=0.6, max_value=0.0,
+                    flags=0) -> PgmParams:
+    """main.cpp's written output: smooth_side 2, max_side 5, contrast 500, gamma 0.6f."""
+    p = PgmParams()
+    p.width, p.height, p.smooth_side, p.max_side = width, height, smooth_side, max_side
+    p.contrast, p.gamma, p.max_value, p.flags = contrast, gamma, max_value, flags
     return p
 
 
@@ -416,6 +438,43 @@ class Context:
             out["stats"].ctypes.data))
         return out
 
+    def smooth_device(self, in_ptr, out_ptr, width: int, height: int, side: int, max_ptr=None, stream=None):
+        """Queue GridRenderPlane::smooth (out_ptr, which may equal in_ptr) or
+        computeSmoothedMax (out_ptr None) on device buffers (ipt_smooth_device);
+        max_value goes to the float at max_ptr. Complete on `stream`'s order
+        or after wait()."""
+        _check(self.lib, self.h, self.lib.ipt_smooth_device(self.h, in_ptr, out_ptr, width, height, side, max_ptr,
+                                                            stream))
+
+    def pgm_device(self, params: PgmParams, pixels_ptr, pixel_max_ptr=None, smoothed_ptr=None, gray8_ptr=None,
+                   stats_ptr=None, stream=None):
+        """Queue main.cpp's PGM chain on device buffers (ipt_pgm_device):
+        smooth, smoothed max, n_val bytes at gray8_ptr, {max_value used,
+        logf(contrast), 0, 0} at stats_ptr. Every output is optional; complete
+        on `stream`'s order or after wait()."""
+        _check(self.lib, self.h, self.lib.ipt_pgm_device(self.h, C.byref(params), pixels_ptr, pixel_max_ptr,
+                                                         smoothed_ptr, gray8_ptr, stats_ptr, stream))
+
+    def pgm(self, pixels: np.ndarray, width: int, height: int, smooth_side: int = 0, max_side: int = 0,
+            contrast: float = 500.0, gamma: float = 0.6, max_value: float = 0.0, pixel_max=None) -> dict:
+        """Host-buffer PGM chain (ipt_pgm): {smoothed, gray8, stats}."""
+        src = np.ascontiguousarray(pixels, dtype=np.float32)
+        pm = None if pixel_max is None else np.ascontiguousarray(pixel_max, dtype=np.float32)
+        out = {"smoothed": np.empty(src.size, np.float32), "gray8": np.empty(src.size, np.uint8),
+               "stats": np.empty(4, np.float32)}
+        _check(self.lib, self.h, self.lib.ipt_pgm(
+            self.h, C.byref(make_pgm_params(width, height, smooth_side, max_side, contrast, gamma, max_value)),
+            src.ctypes.data if src.size else None, None if pm is None else pm.ctypes.data,
+            out["smoothed"].ctypes.data, out["gray8"].ctypes.data, out["stats"].ctypes.data))
+        return out
+
+    def logf_device(self, x: np.ndarray) -> np.ndarray:
+        """logf(x) as the PGM kernels compute it, on the device."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.empty_like(x)
+        _check(self.lib, self.h, self.lib.ipt_logf_device(self.h, x.ctypes.data, out.ctypes.data, x.size))
+        return out
+
     def powf_device(self, x: np.ndarray, y: float) -> np.ndarray:
         """powf(x, y) as the display kernels compute it, on the device."""
         x = np.ascontiguousarray(x, np.float32)
@@ -477,6 +536,17 @@ def powf_host(x: np.ndarray, y: float) -> np.ndarray:
     rc = lib.ipt_powf_host(x.ctypes.data, C.c_float(y), out.ctypes.data, x.size)
     if rc != IPT_OK:
         raise IptError(rc, "ipt_powf_host")
+    return out
+
+
+def logf_host(x: np.ndarray) -> np.ndarray:
+    """logf(x) by the library's host build of the PGM kernels' logf_."""
+    lib = load()
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.empty_like(x)
+    rc = lib.ipt_logf_host(x.ctypes.data, out.ctypes.data, x.size)
+    if rc != IPT_OK:
+        raise IptError(rc, "ipt_logf_host")
     return out
 
 

@@ -23,7 +23,8 @@ struct PostScratch {
     unsigned int* blocks = nullptr;  // per-block bright counts, then their exclusive scan
     void* scalars = nullptr;       // bright count, image max key, tone min / max
     void* stats = nullptr;         // ipt_display_stats_device: mx, white point, radix prefix, digit counts
-    float* processed = nullptr;    // glare output when the caller passes none
+    void* pgm = nullptr;           // ipt_smooth_device / ipt_pgm_device: the maxima, max_value, logf(contrast)
+    float* processed = nullptr;    // glare output (smooth output, in-place copy) when the caller passes none
     float* tone = nullptr;         // tone-mapped image when the caller passes none
     size_t bright_cap = 0, blocks_cap = 0, processed_cap = 0, tone_cap = 0;
     hipEvent_t done = nullptr;

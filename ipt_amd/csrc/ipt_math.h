@@ -23,6 +23,8 @@
 //                 to glibc's for every float input in tests/.
 //      powf  -> ARM optimized-routines powf (__powf_fma), for the display
 //                 chain's gamma only (powf_ below; tests/test_display_cpu.py)
+//      logf  -> ARM optimized-routines logf (__logf_fma), for the PGM chain's
+//                 n_val only (logf_ below, x in [1, FLT_MAX]; tests/test_pgm_cpu.py)
 //    Constants were read from the image's libm.so.6 .rodata and the operation
 //    graphs from its disassembly; tests/test_math_exhaustive.py checks every
 //    float input of each function's reachable domain against the host libm.
@@ -567,6 +569,48 @@ IPT_HD float powf_(float x, float y) {
     double e = fma_(C2, rr, 1.0);
     e = fma_(zz, rr2, e);
     return (float)(e * s);
+}
+
+// ------------------------------------------------------------------ logf
+// ARM optimized-routines logf as built into glibc 2.35
+// (sysdeps/ieee754/flt-32/e_logf.c, logf_data.c): a 16-entry {invc, logc}
+// table and a cubic, in double. Table read from libm .rodata (__logf_data
+// 0xb2ce0: {invc, logc}[16], then ln2 and poly[3] at 0xb2de0). The plain
+// (uncontracted) form below and the form with every multiply-add fused both
+// equal the image's logf (__logf_fma) on all 1 065 353 216 floats of
+// [1, FLT_MAX], so this is built with -ffp-contract=off as everything else.
+//
+// Scope (the PGM chain: n_val's adj is clamped to [1, contrast]): x in
+// [1, FLT_MAX]. Outside it (x < 1, negative, +inf, NaN) the result is the quiet
+// NaN 0x7fc00000 by definition, the same on the host and on the device.
+IPT_HD float logf_(float x) {
+    const uint64_t tab[16][2] = {
+        {0x3ff661ec79f8f3beull, 0xbfd57bf7808caadeull}, {0x3ff571ed4aaf883dull, 0xbfd2bef0a7c06ddbull},
+        {0x3ff49539f0f010b0ull, 0xbfd01eae7f513a67ull}, {0x3ff3c995b0b80385ull, 0xbfcb31d8a68224e9ull},
+        {0x3ff30d190c8864a5ull, 0xbfc6574f0ac07758ull}, {0x3ff25e227b0b8ea0ull, 0xbfc1aa2bc79c8100ull},
+        {0x3ff1bb4a4a1a343full, 0xbfba4e76ce8c0e5eull}, {0x3ff12358f08ae5baull, 0xbfb1973c5a611cccull},
+        {0x3ff0953f419900a7ull, 0xbfa252f438e10c1eull}, {0x3ff0000000000000ull, 0x0000000000000000ull},
+        {0x3fee608cfd9a47acull, 0x3faaa5aa5df25984ull}, {0x3feca4b31f026aa0ull, 0x3fbc5e53aa362eb4ull},
+        {0x3feb2036576afce6ull, 0x3fc526e57720db08ull}, {0x3fe9c2d163a1aa2dull, 0x3fcbc2860d224770ull},
+        {0x3fe886e6037841edull, 0x3fd1058bc8a07ee1ull}, {0x3fe767dcf5534862ull, 0x3fd4043057b6ee09ull}};
+    const double ln2 = u2d(0x3fe62e42fefa39efull);
+    const double A0 = u2d(0xbfd00ea348b88334ull), A1 = u2d(0x3fd5575b0be00b6aull), A2 = u2d(0xbfdffffef20a4123ull);
+    const uint32_t ix = f2u(x);
+    if (ix - 0x3f800000u > 0x7f7fffffu - 0x3f800000u) return u2f(0x7fc00000u);  // outside [1, FLT_MAX]
+    if (ix == 0x3f800000u) return 0.0f;
+    const uint32_t tmp = ix - 0x3f330000u;
+    const int i = (int)((tmp >> 19) & 15u);
+    const int k = (int32_t)tmp >> 23;
+    const uint32_t iz = ix - (tmp & 0xff800000u);
+    const double invc = u2d(tab[i][0]), logc = u2d(tab[i][1]);
+    const double z = (double)u2f(iz);
+    const double r = z * invc - 1.0;
+    const double y0 = logc + (double)k * ln2;
+    const double r2 = r * r;
+    double y = A1 * r + A2;
+    y = A0 * r2 + y;
+    y = y * r2 + (y0 + r);
+    return (float)y;
 }
 
 // a / b with the NaN results of the x86 host the reference runs on stated

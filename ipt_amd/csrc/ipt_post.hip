@@ -3,6 +3,8 @@
 //   GridRenderPlane::smooth(side) / computeSmoothedMax(side)
 //                                  (src/GridRenderPlane.cpp:10-59)
 //   Gui's glare bloom               (src/gui.cpp:28-52: draw_halo + glare)
+//   main.cpp's PGM output           (src/main.cpp:225-235, 291-309: n_val after
+//                                    smooth and computeSmoothedMax; "PGM path" below)
 //
 // smooth: the reference filters in place, walking y and x downwards from the
 // bottom-right corner and reading pixels (y-yy, x-xx), yy, xx < side. Every
@@ -39,10 +41,15 @@ using namespace ipt;
 
 constexpr int kPostBlock = 256;
 
+// KEEP: a pixel the filter leaves alone (x < side-1 or y < side-1) is copied
+// from `in`, so that `out` is the whole filtered plane (ipt_smooth_device out
+// of place; ipt_smooth copies the plane first instead)
+template <bool KEEP>
 __global__ __launch_bounds__(kPostBlock) void smooth_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                             int W, int H, int side, unsigned int* max_bits) {
     const int x = blockIdx.x * kPostBlock + threadIdx.x, y = blockIdx.y;
     float cand = 0.0f;
+    if (KEEP && x < W && (x < side - 1 || y < side - 1)) out[(size_t)y * W + x] = in[(size_t)y * W + x];
     if (x < W && x >= side - 1 && y >= side - 1) {
         float accum = 0.0f;
         for (int yy = 0; yy < side; ++yy) {
@@ -534,6 +541,89 @@ __global__ void stats_out_kernel(const StatsScalars* __restrict__ ss, float* __r
     if (t < 4 && blockIdx.x == 0) stats[t] = t == 0 ? ss->mx : (t == 1 ? ss->lo : (t == 2 ? ss->white : 0.0f));
 }
 
+// ------------------------------------------------------------------ PGM path
+// ipt_smooth_device / ipt_pgm_device (ABI 7 additions): main.cpp:291-309 on a
+// plane that stays on the device, smooth(side) -> computeSmoothedMax(side) ->
+// n_val -> bytes. Every maximum is a fold from 0 with `>`, i.e. the largest
+// positive element (NaN never wins), so it is an integer max of bit patterns
+// and does not depend on dispatch order. The maxima, the max_value n_val
+// divides by and logf_(contrast) stay in PgmScalars between the kernels.
+struct PgmScalars {
+    unsigned int smooth_max;  // bits of smooth()'s max_value
+    unsigned int window_max;  // bits of computeSmoothedMax()'s
+    unsigned int fold_max;    // bits of the pixel_max plane's fold
+    unsigned int pad;
+    float max_value;     // the one n_val divides by (ipt_capi.h: the last stage that sets it)
+    float log_contrast;  // logf_(contrast)
+    float zero[2];
+};
+enum { kPgmMaxGiven = 0, kPgmMaxSmooth, kPgmMaxWindow, kPgmMaxFold };
+
+// GridRenderPlane::max_value as PlaneIo::finish folds pixel_max: from 0, `v > max`
+__global__ __launch_bounds__(kPostBlock) void fold_max_kernel(const float* __restrict__ in, long long n,
+                                                              unsigned int* __restrict__ max_bits) {
+    __shared__ unsigned int red[kPostWaves];
+    const long long i = ((long long)blockIdx.x * kPostBlock + threadIdx.x) * 4;
+    float v[4];
+    load4_(in, i, n, ((uintptr_t)in & 15u) == 0, v);  // (0 past n: the fold's start)
+    unsigned int m = 0u;
+    for (int j = 0; j < 4; ++j) m = max(m, v[j] > 0.0f ? f2u(v[j]) : 0u);
+    m = block_max_(m, red);
+    if (threadIdx.x == 0 && m) atomicMax(max_bits, m);
+}
+
+__global__ void pgm_setup_kernel(PgmScalars* __restrict__ ps, int which, float given, float contrast,
+                                 float* __restrict__ stats) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const float mx = which == kPgmMaxWindow   ? u2f(ps->window_max)
+                     : which == kPgmMaxSmooth ? u2f(ps->smooth_max)
+                     : which == kPgmMaxFold   ? u2f(ps->fold_max)
+                                              : given;
+    const float lc = logf_(contrast);
+    ps->max_value = mx;
+    ps->log_contrast = lc;
+    if (stats) stats[0] = mx, stats[1] = lc, stats[2] = 0.0f, stats[3] = 0.0f;
+}
+
+// ipt::n_val (main.cpp:225-235). adj is in [1, contrast] or NaN after the two
+// clamps (std::min / std::max: a NaN first argument stays); a NaN ends as
+// byte 0 on the host (cvttss2si gives INT_MIN, then max(0, .)), stated here.
+__device__ __forceinline__ uint8_t n_val_(float val, float mx, float contrast, float log_contrast, float gamma) {
+    float adj = val * contrast / mx;
+    adj = contrast < adj ? contrast : adj;
+    adj = adj < 1.0f ? 1.0f : adj;
+    if (is_nan_(adj)) return 0;
+    float fn = logf_(adj) / log_contrast;
+    fn = powf_(fn, gamma);
+    const float t = 256.0f * fn;  // in [0, 256]: 0 <= fn <= 1
+    const int n = (int)t;
+    return (uint8_t)(n < 0 ? 0 : (n > 255 ? 255 : n));
+}
+
+__global__ __launch_bounds__(kPostBlock) void n_val_kernel(const float* __restrict__ in, uint8_t* __restrict__ out,
+                                                           long long n, float contrast, float gamma,
+                                                           const PgmScalars* __restrict__ ps) {
+    const float mx = ps->max_value, lc = ps->log_contrast;
+    const long long i = ((long long)blockIdx.x * kPostBlock + threadIdx.x) * 4;
+    if (i >= n) return;
+    float v[4];
+    load4_(in, i, n, ((uintptr_t)in & 15u) == 0, v);
+    uint8_t b[4];
+    for (int j = 0; j < 4; ++j) b[j] = n_val_(v[j], mx, contrast, lc, gamma);
+    if (((uintptr_t)out & 3u) == 0 && i + 3 < n) {
+        *reinterpret_cast<uchar4*>(out + i) = make_uchar4(b[0], b[1], b[2], b[3]);
+    } else {
+        for (int j = 0; j < 4; ++j)
+            if (i + j < n) out[i + j] = b[j];
+    }
+}
+
+__global__ __launch_bounds__(kPostBlock) void logf_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                          long long n) {
+    const long long i = (long long)blockIdx.x * kPostBlock + threadIdx.x;
+    if (i < n) out[i] = logf_(x[i]);
+}
+
 // powf_'s stated domain for y (ipt_math.h)
 bool powf_y_ok(float y) { return isfinite_(y) && y > 0.0f && y != std::trunc(y); }
 
@@ -590,6 +680,101 @@ int stats_check(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* pi
     return IPT_OK;
 }
 
+// [a, a + na) and [b, b + nb) share a byte (a NULL range shares none)
+bool overlap_(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + nb && y < x + na;
+}
+
+constexpr int kSmoothMaxSide = 64;  // 64^2 adds per pixel bound a queued kernel
+
+// the side rules of ipt_smooth_device / ipt_pgm_device, after the INVALID ones
+bool side_unsupported_(int side) { return side == 1 || side > kSmoothMaxSide; }
+
+// the argument rules of ipt_smooth_device (ipt_capi.h)
+int smooth_check(ipt_ctx* ctx, const float* in, const float* out, int width, int height, int side, const float* mx) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!in || width <= 0 || height <= 0 || side < 0)
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_smooth_device: bad arguments");
+    const size_t bytes = (size_t)width * (size_t)height * sizeof(float);
+    if ((out != in && overlap_(in, bytes, out, bytes)) || overlap_(in, bytes, mx, sizeof(float)) ||
+        overlap_(out, bytes, mx, sizeof(float)))
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_smooth_device: the buffers overlap");
+    if (side_unsupported_(side) || (long long)width * height > (1ll << 31))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
+                                      "ipt_smooth_device: side 0 or 2..64 (1 is undefined behaviour in the "
+                                      "reference), at most 2^31 pixels");
+    return IPT_OK;
+}
+
+// the argument rules of ipt_pgm / ipt_pgm_device (ipt_capi.h)
+int pgm_check(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const float* pixel_max,
+              const float* smoothed, const uint8_t* gray8, const float* stats) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!p || !pixels || p->width <= 0 || p->height <= 0 || p->smooth_side < 0 || p->max_side < 0)
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_pgm: bad arguments");
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    const void* buf[5] = {pixels, pixel_max, smoothed, gray8, stats};
+    const size_t len[5] = {n * sizeof(float), n * sizeof(float), n * sizeof(float), n, 4 * sizeof(float)};
+    for (int a = 0; a < 5; ++a)
+        for (int b = std::max(a + 1, 2); b < 5; ++b)  // every pair but the two inputs
+            if (overlap_(buf[a], len[a], buf[b], len[b]))
+                return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_pgm: the buffers overlap");
+    if (side_unsupported_(p->smooth_side) || side_unsupported_(p->max_side) || p->flags != 0 ||
+        (long long)p->width * p->height > (1ll << 31))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
+                                      "ipt_pgm: sides 0 or 2..64, flags 0, at most 2^31 pixels");
+    if (!isfinite_(p->contrast) || !(p->contrast > 1.0f) || !powf_y_ok(p->gamma))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
+                                      "ipt_pgm: contrast finite and > 1, gamma finite, > 0 and no integer");
+    return IPT_OK;
+}
+
+// The PGM path's share of the context's scratch: the scalars and, where a call
+// needs a plane of its own, `processed`. Only the first call or a larger image
+// allocates or waits; then the call is ordered behind the previous one.
+int pgm_scratch(ipt_ctx* ctx, size_t need_processed, hipStream_t st) {
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    if (!S.done || !S.pgm || need_processed > S.processed_cap) {
+        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
+        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+        size_t one = 0;
+        if (!S.pgm)
+            if (const int rc = post_grow(ctx, S.pgm, one, 1, sizeof(PgmScalars))) return rc;
+        if (need_processed > S.processed_cap)
+            if (const int rc = post_grow(ctx, S.processed, S.processed_cap, need_processed, sizeof(float))) return rc;
+    }
+    // the scratch is shared: a call on another stream runs after the previous one
+    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
+    POSTCHECK(ctx, hipMemsetAsync(S.pgm, 0, sizeof(PgmScalars), st));
+    return IPT_OK;
+}
+
+int pgm_queued(ipt_ctx* ctx, hipStream_t st) {
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    POSTCHECK(ctx, hipGetLastError());
+    POSTCHECK(ctx, hipEventRecord(S.done, st));
+    S.used = true;
+    S.last_stream = st;
+    return IPT_OK;
+}
+
+// smooth(side) of `in` into `out` (the whole plane; NULL: the maximum alone),
+// max_value's bits into *max_bits (zeroed by the caller). in != out.
+// side 0 or larger than the image: no pixel qualifies, the plane is copied and
+// the maximum stays 0.
+hipError_t launch_smooth(hipStream_t st, const float* in, float* out, int W, int H, int side,
+                         unsigned int* max_bits) {
+    if (side < 2 || side > W || side > H)
+        return out ? hipMemcpyAsync(out, in, (size_t)W * H * sizeof(float), hipMemcpyDeviceToDevice, st) : hipSuccess;
+    dim3 grid((W + kPostBlock - 1) / kPostBlock, H);
+    if (out)
+        hipLaunchKernelGGL(smooth_kernel<true>, grid, dim3(kPostBlock), 0, st, in, out, W, H, side, max_bits);
+    else
+        hipLaunchKernelGGL(smooth_kernel<false>, grid, dim3(kPostBlock), 0, st, in, out, W, H, side, max_bits);
+    return hipSuccess;
+}
+
 }  // namespace
 
 extern "C" {
@@ -614,7 +799,8 @@ int ipt_smooth(ipt_ctx* ctx, float* pixels, int width, int height, int side, int
     POSTCHECK(ctx, hipMemsetAsync(dmax.p, 0, sizeof(unsigned int), st));
     if (side >= 2 && side <= width && side <= height) {
         dim3 grid((width + kPostBlock - 1) / kPostBlock, height);
-        hipLaunchKernelGGL(smooth_kernel, grid, dim3(kPostBlock), 0, st, din.p, dout.p, width, height, side, dmax.p);
+        hipLaunchKernelGGL(smooth_kernel<false>, grid, dim3(kPostBlock), 0, st, din.p, dout.p, width, height, side,
+                           dmax.p);
         POSTCHECK(ctx, hipGetLastError());
     }
     unsigned int mb = 0;
@@ -872,6 +1058,122 @@ int ipt_display_stats(ipt_ctx* ctx, const ipt_display_stats_params* p, const flo
     return IPT_OK;
 }
 
+int ipt_smooth_device(ipt_ctx* ctx, const float* dev_in, float* dev_out, int width, int height, int side,
+                      float* dev_max, void* hip_stream) {
+    if (const int rc = smooth_check(ctx, dev_in, dev_out, width, height, side, dev_max)) return rc;
+    const size_t n = (size_t)width * (size_t)height;
+    const bool filters = side >= 2 && side <= width && side <= height;  // some pixel qualifies
+    const bool in_place = dev_out == dev_in;
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
+    if (const int rc = pgm_scratch(ctx, in_place && filters ? n : 0, st)) return rc;
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    PgmScalars* ps = static_cast<PgmScalars*>(S.pgm);
+    if (in_place) {  // the filter reads the context's copy (nothing changes when no pixel qualifies)
+        if (filters) {
+            POSTCHECK(ctx, hipMemcpyAsync(S.processed, dev_in, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            dim3 grid((width + kPostBlock - 1) / kPostBlock, height);
+            hipLaunchKernelGGL(smooth_kernel<false>, grid, dim3(kPostBlock), 0, st, (const float*)S.processed, dev_out,
+                               width, height, side, &ps->smooth_max);
+        }
+    } else {
+        POSTCHECK(ctx, launch_smooth(st, dev_in, dev_out, width, height, side, &ps->smooth_max));
+    }
+    if (dev_max) POSTCHECK(ctx, hipMemcpyAsync(dev_max, &ps->smooth_max, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return pgm_queued(ctx, st);
+}
+
+int ipt_pgm_device(ipt_ctx* ctx, const ipt_pgm_params* p, const float* dev_pixels, const float* dev_pixel_max,
+                   float* dev_smoothed, uint8_t* dev_gray8, float* dev_stats, void* hip_stream) {
+    if (const int rc = pgm_check(ctx, p, dev_pixels, dev_pixel_max, dev_smoothed, dev_gray8, dev_stats)) return rc;
+    const int W = p->width, H = p->height;
+    const long long n = (long long)W * H;
+    const bool smooth = p->smooth_side >= 2, window = p->max_side >= 2;
+    const int which = window ? kPgmMaxWindow : smooth ? kPgmMaxSmooth : dev_pixel_max ? kPgmMaxFold : kPgmMaxGiven;
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
+    // a stage nobody reads is not run: smooth's pixels feed the bytes, the
+    // window maximum and dev_smoothed, its maximum only rule 2
+    const bool run_smooth = smooth && (dev_smoothed || dev_gray8 || window || dev_stats);
+    if (const int rc = pgm_scratch(ctx, run_smooth && !dev_smoothed ? (size_t)n : 0, st)) return rc;
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    PgmScalars* ps = static_cast<PgmScalars*>(S.pgm);
+    const float* plane = dev_pixels;  // the pixels n_val reads
+    if (run_smooth) {
+        float* out = dev_smoothed ? dev_smoothed : S.processed;
+        POSTCHECK(ctx, launch_smooth(st, dev_pixels, out, W, H, p->smooth_side, &ps->smooth_max));
+        plane = out;
+    } else if (dev_smoothed) {
+        POSTCHECK(ctx, hipMemcpyAsync(dev_smoothed, dev_pixels, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    const unsigned int quads = (unsigned int)((n + 4ll * kPostBlock - 1) / (4ll * kPostBlock));
+    if (dev_gray8 || dev_stats) {
+        if (window) POSTCHECK(ctx, launch_smooth(st, plane, nullptr, W, H, p->max_side, &ps->window_max));
+        if (which == kPgmMaxFold)
+            hipLaunchKernelGGL(fold_max_kernel, dim3(quads), dim3(kPostBlock), 0, st, dev_pixel_max, n, &ps->fold_max);
+        hipLaunchKernelGGL(pgm_setup_kernel, dim3(1), dim3(64), 0, st, ps, which, p->max_value, p->contrast, dev_stats);
+    }
+    if (dev_gray8)
+        hipLaunchKernelGGL(n_val_kernel, dim3(quads), dim3(kPostBlock), 0, st, plane, dev_gray8, n, p->contrast,
+                           p->gamma, (const PgmScalars*)ps);
+    return pgm_queued(ctx, st);
+}
+
+int ipt_pgm(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const float* pixel_max, float* smoothed,
+            uint8_t* gray8, float* stats) {
+    if (const int rc = pgm_check(ctx, p, pixels, pixel_max, smoothed, gray8, stats)) return rc;
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = ipt_internal::ctx_stream(ctx);
+    const size_t n = (size_t)p->width * p->height;
+    const bool need_fold = pixel_max && p->smooth_side < 2 && p->max_side < 2;  // the only rule that reads it
+    DevBuf<float> din, dpmax, dsm, dstats;
+    DevBuf<uint8_t> dgray;
+    POSTCHECK(ctx, hipMalloc(&din.p, n * sizeof(float)));
+    if (need_fold) POSTCHECK(ctx, hipMalloc(&dpmax.p, n * sizeof(float)));
+    if (smoothed) POSTCHECK(ctx, hipMalloc(&dsm.p, n * sizeof(float)));
+    if (gray8) POSTCHECK(ctx, hipMalloc(&dgray.p, n));
+    if (stats) POSTCHECK(ctx, hipMalloc(&dstats.p, 4 * sizeof(float)));
+    POSTCHECK(ctx, hipMemcpyAsync(din.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (need_fold) POSTCHECK(ctx, hipMemcpyAsync(dpmax.p, pixel_max, n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (const int rc = ipt_pgm_device(ctx, p, din.p, dpmax.p, dsm.p, dgray.p, dstats.p, st)) return rc;
+    if (smoothed) POSTCHECK(ctx, hipMemcpyAsync(smoothed, dsm.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (gray8) POSTCHECK(ctx, hipMemcpyAsync(gray8, dgray.p, n, hipMemcpyDeviceToHost, st));
+    if (stats) POSTCHECK(ctx, hipMemcpyAsync(stats, dstats.p, 4 * sizeof(float), hipMemcpyDeviceToHost, st));
+    POSTCHECK(ctx, hipStreamSynchronize(st));
+    return IPT_OK;
+}
+
+int ipt_logf_host(const float* x, float* out, int64_t n) {
+    if (!x || !out || n < 0) return IPT_E_INVALID;
+    const int nt = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t)
+        th.emplace_back([=]() {
+            const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
+            for (int64_t i = lo; i < hi; ++i) out[i] = logf_(x[i]);
+        });
+    for (auto& t : th) t.join();
+    return IPT_OK;
+}
+
+int ipt_logf_device(ipt_ctx* ctx, const float* x, float* out, int64_t n) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!x || !out || n < 0) return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_logf_device: bad arguments");
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = ipt_internal::ctx_stream(ctx);
+    DevBuf<float> din, dout;
+    POSTCHECK(ctx, hipMalloc(&din.p, std::max<int64_t>(n, 1) * sizeof(float)));
+    POSTCHECK(ctx, hipMalloc(&dout.p, std::max<int64_t>(n, 1) * sizeof(float)));
+    POSTCHECK(ctx, hipMemcpyAsync(din.p, x, n * sizeof(float), hipMemcpyHostToDevice, st));
+    if (n > 0)
+        hipLaunchKernelGGL(logf_kernel, dim3((unsigned)((n + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0, st,
+                           (const float*)din.p, dout.p, (long long)n);
+    POSTCHECK(ctx, hipGetLastError());
+    POSTCHECK(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    POSTCHECK(ctx, hipStreamSynchronize(st));
+    return IPT_OK;
+}
+
 int ipt_powf_host(const float* x, float y, float* out, int64_t n) {
     if (!x || !out || n < 0) return IPT_E_INVALID;
     if (!powf_y_ok(y)) return IPT_E_UNSUPPORTED;
@@ -920,7 +1222,7 @@ int post_wait(ipt_ctx* ctx) {
 
 void post_release(ipt_ctx* ctx) {
     PostScratch& S = ctx_post(ctx);
-    for (void* b : {S.bright, (void*)S.blocks, S.scalars, S.stats, (void*)S.processed, (void*)S.tone})
+    for (void* b : {S.bright, (void*)S.blocks, S.scalars, S.stats, S.pgm, (void*)S.processed, (void*)S.tone})
         if (b) (void)hipFree(b);
     if (S.done) (void)hipEventDestroy(S.done);
     S = PostScratch{};

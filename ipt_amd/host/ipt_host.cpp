@@ -546,6 +546,23 @@ DisplayStats GpuRenderer::display_stats(const GuiRenderPlane& plane, float glare
     return run_display_stats(ctx_, plane.pixels, plane.width, plane.height, glare_cutoff, buckets, white_rank);
 }
 
+std::vector<uint8_t> GpuRenderer::pgm(const GridRenderPlane& plane, size_t smooth_side, size_t max_side, float contrast,
+                                      float gamma) {
+    check_plane(plane);
+    if (smooth_side > 0x7fffffffu || max_side > 0x7fffffffu) throw IptError(IPT_E_INVALID, "pgm: side too large");
+    ipt_pgm_params q{};
+    q.width = (int32_t)plane.width;
+    q.height = (int32_t)plane.height;
+    q.smooth_side = (int32_t)smooth_side;
+    q.max_side = (int32_t)max_side;
+    q.contrast = contrast;
+    q.gamma = gamma;
+    q.max_value = plane.max_value;
+    std::vector<uint8_t> out(plane.pixels.size());
+    check(ctx_, ipt_pgm(ctx_, &q, plane.pixels.data(), nullptr, nullptr, out.data(), nullptr));
+    return out;
+}
+
 void render_samples_gpu(const Scene& scene, GridRenderPlane& plane, const RenderParams& p, int device) {
     GpuRenderer r(device);
     r.upload(scene);
@@ -830,6 +847,18 @@ void write_pgm(const std::string& path, const GridRenderPlane& plane, float cont
     for (size_t y = 0; y < plane.height; ++y) {
         for (size_t x = 0; x < plane.width; ++x)
             std::fprintf(fp, "%d ", n_val(plane.pixels[y * plane.width + x], plane.max_value, contrast, gamma));
+        std::fprintf(fp, "\n");
+    }
+    std::fclose(fp);
+}
+
+void write_pgm_bytes(const std::string& path, size_t width, size_t height, const std::vector<uint8_t>& bytes) {
+    if (bytes.size() != width * height) throw IptError(IPT_E_INVALID, "write_pgm_bytes: size mismatch");
+    FILE* fp = std::fopen(path.c_str(), "wb");
+    if (!fp) throw IptError(IPT_E_INVALID, "cannot open " + path);
+    std::fprintf(fp, "P2\n%lu %lu\n%d\n", (unsigned long)width, (unsigned long)height, 255);
+    for (size_t y = 0; y < height; ++y) {
+        for (size_t x = 0; x < width; ++x) std::fprintf(fp, "%d ", (int)bytes[y * width + x]);
         std::fprintf(fp, "\n");
     }
     std::fclose(fp);

@@ -253,6 +253,14 @@ class GpuRenderer {
                                int64_t white_rank = -1);
     DisplayStats display_stats(const GuiRenderPlane& plane, float glare_cutoff = 0.0f, int buckets = 400,
                                int64_t white_rank = -1);
+    // main.cpp's written output on the GPU (ipt_pgm): the bytes of result.pgm
+    // for the plane as it stands, n_val(pixel, max_value, contrast, gamma) per
+    // pixel, after GridRenderPlane::smooth(smooth_side) and
+    // computeSmoothedMax(max_side) of a copy when a side is >= 2 (main.cpp: 2
+    // and 5). With both sides 0 the plane's max_value divides, and the bytes
+    // equal what write_pgm(path, plane, contrast, gamma) prints.
+    std::vector<uint8_t> pgm(const GridRenderPlane& plane, size_t smooth_side = 0, size_t max_side = 0,
+                             float contrast = 500.0f, float gamma = 0.6f);
     ipt_ctx* handle() const { return ctx_; }
 
    private:
@@ -319,5 +327,7 @@ void write_pfm(const std::string& path, const GridRenderPlane& plane);
 // mapped by log(clamp(v*contrast/max, 1, contrast))/log(contrast), ^gamma, *256.
 int n_val(float val, float max, float contrast, float gamma);
 void write_pgm(const std::string& path, const GridRenderPlane& plane, float contrast = 500.0f, float gamma = 0.6f);
+// The same ASCII P2 layout from bytes already mapped (GpuRenderer::pgm).
+void write_pgm_bytes(const std::string& path, size_t width, size_t height, const std::vector<uint8_t>& bytes);
 
 }  // namespace ipt

@@ -10,7 +10,8 @@
 //              [--n-rays 16] [--depth 8] [--seed 20241223] [--device 0]
 //              [--devices 0,1,...,7 [--tile-rows 16]]
 //              [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]
-//              [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out glare.pfm]
+//              [--pgm result.pgm] [--smooth SIDE] [--smoothed-max SIDE]
+//              [--glare CUTOFF --glare-out glare.pfm]
 //              [--gpu-display] [--gui-plane] [--white-percentile F]
 //              [--histogram hist.txt [--hist-buckets 400]]
 //
@@ -19,8 +20,8 @@
 // program displays and saves, so that with --gpu-display the chain render ->
 // Gui plane -> glare -> tone map -> 8-bit is the reference's main loop on the
 // device. It composes with --gpu-display, --glare, --passes, --devices, --pfm
-// and --counts; --smooth and --pgm are GridRenderPlane's filter and main.cpp's
-// PGM writer for it and are refused.
+// and --counts; --smooth, --smoothed-max and --pgm are GridRenderPlane's
+// filters and main.cpp's PGM writer for it and are refused.
 // --gpu-display takes the PNG's bytes from GpuRenderer::display (the display
 // pipeline on the GPU, with the --glare cutoff's bloom when one is given, as
 // Gui::updateDisplay shows it) instead of the host's to_gray8; without
@@ -34,7 +35,12 @@
 // image, one per line, computed on the GPU by the same call.
 // --smooth applies GridRenderPlane::smooth(SIDE) on the GPU before output;
 // --glare writes Gui's glare bloom of the plane (gui.cpp:28-52, GPU) as PFM;
-// --pgm writes main.cpp's contrast/gamma PGM (main.cpp:297-309).
+// --pgm writes main.cpp's contrast/gamma PGM (main.cpp:297-309), after
+// GridRenderPlane::computeSmoothedMax(SIDE) with --smoothed-max (main.cpp:293;
+// the reference's sequence is --smooth 2 --smoothed-max 5). With --gpu-display
+// the PGM's numbers come from GpuRenderer::pgm (the smoothed maximum, logf,
+// powf and the 8-bit mapping on the GPU) instead of the host's n_val loop; the
+// file is the same bytes.
 // --devices renders with one context per listed device (MultiGpuRenderer: the
 // rows cut into --tile-rows tiles dealt round-robin, owned rows assembled at
 // the end of each batch; a device may repeat); the image is the same bits.
@@ -58,7 +64,8 @@ namespace {
                  "                  [--n-rays N] [--depth D] [--seed X] [--device I]\n"
                  "                  [--devices I,J,... [--tile-rows 16]]\n"
                  "                  [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]\n"
-                 "                  [--pgm result.pgm] [--smooth SIDE] [--glare CUTOFF --glare-out F.pfm]\n"
+                 "                  [--pgm result.pgm] [--smooth SIDE] [--smoothed-max SIDE]\n"
+                 "                  [--glare CUTOFF --glare-out F.pfm]\n"
                  "                  [--gpu-display] [--gui-plane] [--white-percentile F]\n"
                  "                  [--histogram hist.txt [--hist-buckets 400]]\n");
     std::exit(2);
@@ -69,7 +76,7 @@ int main(int argc, char** argv) {
     std::string scene_name = "box", out = "result.png", pfm, counts, pgm, glare_out, hist_out;
     double white_percentile = -1.0;
     long hist_buckets = 400;
-    long smooth = 0;
+    long smooth = 0, smoothed_max = 0;
     bool gpu_display = false, gui_plane = false;
     double glare = -1.0;
     long width = 640, height = 640, spp = 16, passes = 1, n_rays = 16, depth = 8, device = 0, tile_rows = 16;
@@ -103,6 +110,7 @@ int main(int argc, char** argv) {
         else if (a == "--counts") counts = val();
         else if (a == "--pgm") pgm = val();
         else if (a == "--smooth") smooth = std::atol(val());
+        else if (a == "--smoothed-max") smoothed_max = std::atol(val());
         else if (a == "--glare") glare = std::atof(val());
         else if (a == "--glare-out") glare_out = val();
         else if (a == "--gpu-display") gpu_display = true;
@@ -114,6 +122,8 @@ int main(int argc, char** argv) {
     }
     if (width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || n_rays < 0 || depth < 0) usage("bad sizes");
     if (gui_plane && smooth > 0) usage("--smooth is GridRenderPlane::smooth; the Gui plane (--gui-plane) has none");
+    if (gui_plane && smoothed_max > 0) usage("--smoothed-max is GridRenderPlane::computeSmoothedMax; not with --gui-plane");
+    if (smoothed_max < 0 || (smoothed_max > 0 && pgm.empty())) usage("--smoothed-max takes a side and needs --pgm");
     if (gui_plane && !pgm.empty()) usage("--pgm is main.cpp's writer for a GridRenderPlane; not with --gui-plane");
     if (white_percentile >= 0.0 && !gpu_display) usage("--white-percentile needs --gpu-display");
     if (!(white_percentile < 0.0) && !(white_percentile <= 1.0)) usage("--white-percentile takes a fraction in [0, 1]");
@@ -159,7 +169,12 @@ int main(int argc, char** argv) {
             g.pixels = gpu.glare(plane, (float)glare);
             ipt::write_pfm(glare_out, g);
         }
-        if (!pgm.empty()) ipt::write_pgm(pgm, plane);
+        if (!pgm.empty() && gpu_display) {
+            ipt::write_pgm_bytes(pgm, plane.width, plane.height, gpu.pgm(plane, 0, (size_t)smoothed_max));
+        } else if (!pgm.empty()) {
+            if (smoothed_max > 0) gpu.computeSmoothedMax(plane, (size_t)smoothed_max);
+            ipt::write_pgm(pgm, plane);
+        }
         if (white_percentile >= 0.0 || !hist_out.empty()) {
             // one call gives the picture, the histogram and the white point
             const int64_t rank =
