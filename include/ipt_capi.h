@@ -152,7 +152,35 @@ enum {
        of plane an image holds is the caller's business: calls with and
        without the flag into one image mix the two mappings. Without the flag
        nothing changes. */
-    IPT_FLAG_GUI_PLANE = 2u
+    IPT_FLAG_GUI_PLANE = 2u,
+    /* ABI 7 addition: the estimator is ray_power_preview (main.cpp:55-92)
+       instead of ray_power_recursive -- the frame a viewer shows while the
+       camera moves. Everything else of render_sample (main.cpp:189-216) is
+       unchanged: the two jitter draws (draws 0 and 1 of the same Philox
+       stream), the camera ray, the clamp value >= 0 ? value : 0, the render
+       plane's index math and drift codes. With si = Geometry::traceRay and li
+       = Lighting::traceRayToLight of the camera ray (the nearest hits the full
+       estimator computes at depth 0), a sample's value is
+         1.0f  where li exists and (si is absent or
+               length(si.position - origin) > length(li.position - origin)),
+         0.0f  otherwise where si is absent,
+         dot(si.normal, -direction) / length(direction), clamped, otherwise.
+       n_rays and depth_max are not read (the reference's parameters are
+       unnamed): any values are accepted and give the same frame; every other
+       parameter is validated as without the flag. Composes with ipt_render,
+       ipt_render_device, ipt_render_device_async, ipt_render_values,
+       IPT_FLAG_GUI_PLANE, sharding, preloaded planes, sums / pixel_max,
+       spp_offset, chunked launches and IPT_FLAG_COUNTERS (paths, traced_rays,
+       surface_hits, light_hits, light_traces and drifted count the preview's
+       events, the acceleration-structure counters what the kernel ran, the
+       others stay 0). One fused kernel per launch, one thread per sample: no
+       sampling table is read or built (a context that only renders previews
+       never allocates them) and a sample takes 5 B of work buffer. Preview
+       launches take no tail-overlap gate and stay ordered with queued
+       full-estimator launches into the same image on the same stream. Which
+       estimator's samples a plane holds is the caller's business. Without the
+       flag nothing changes. */
+    IPT_FLAG_PREVIEW = 4u
 };
 
 /* Caller-owned GridRenderPlane state (GridRenderPlane.h:9-12), width*height
@@ -204,9 +232,10 @@ const char* ipt_last_error(ipt_ctx* ctx); /* ctx may be NULL (creation errors) *
 
 /* A context owns its stream and device buffers. The first render allocates its
  * exact sampling tables once: CosineDdf 192 MiB and, for sphere-in-box scenes,
- * the RotateDdf frame-angle table 1 GiB (freed by ipt_destroy). Work buffers
+ * the RotateDdf frame-angle table 1 GiB (freed by ipt_destroy); a render with
+ * IPT_FLAG_PREVIEW reads neither and does not allocate them. Work buffers
  * grow to the largest render: 37 B per sample (radiance, drift code, raygen
- * record) in equal chunks of at most 2^29 samples (18.5 GiB) and at most 3/4
+ * record; 5 B for a preview sample, which has no record) in equal chunks of at most 2^29 samples (18.5 GiB) and at most 3/4
  * of the device memory free at the call (plus the context's own work
  * buffers), so a context's footprint is <= ~20 GiB and contexts sharing a
  * device get smaller chunks rather than IPT_E_OOM; a call renders all its
@@ -279,6 +308,19 @@ int ipt_render_wait(ipt_ctx* ctx);
    (ix, max(H-2-iy,0)), or (ix, H-1-iy) with IPT_FLAG_GUI_PLANE; 0x05 =
    nominal). Host buffers of spp*width*height. */
 int ipt_render_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t* codes);
+
+/* The preview estimator's samples with their first hits (ABI 7 addition): the
+   verification surface of IPT_FLAG_PREVIEW and an AOV output (hit class,
+   position, normal). The preview is implied whether or not the flag is set.
+   Host buffers of spp*width*height samples; values and codes as
+   ipt_render_values returns them with the flag. kinds and hits may be NULL.
+   kinds[s][iy][ix]: bits 0-1 the outcome (0 miss, 1 surface, 2 light), bit 2
+   set if si exists, bit 3 set if li exists; 0xff for a sample that was not
+   traced (code 0xfe / 0xff).
+   hits[s][iy][ix][6]: outcome 1: si.position, si.normal; outcome 2:
+   li.position and a zero normal; miss or untraced: zeros. */
+int ipt_preview_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t* codes,
+                       uint8_t* kinds, float* hits);
 
 /* Host-only (no device needed): the tile plan of a sharded render.
    owned_rows[H] = 1 for destination rows this shard accumulates;

@@ -35,6 +35,7 @@ IPT_LIGHT_AREA_TRIANGLE = 1
 IPT_LIGHT_SPHERE, IPT_LIGHT_POINT, IPT_LIGHT_OUTER_SPHERE = 2, 3, 4
 IPT_FLAG_COUNTERS = 1
 IPT_FLAG_GUI_PLANE = 2  # Gui::addRay's row map instead of GridRenderPlane::addRay's (ABI 7)
+IPT_FLAG_PREVIEW = 4  # ray_power_preview instead of ray_power_recursive (ABI 7 addition)
 
 F3 = C.c_float * 3
 
@@ -110,6 +111,7 @@ EXPORTED_SYMBOLS = (
     "ipt_display_device", "ipt_display", "ipt_powf_host", "ipt_powf_device",
     "ipt_display_stats_device", "ipt_display_stats",
     "ipt_smooth_device", "ipt_pgm_device", "ipt_pgm", "ipt_logf_host", "ipt_logf_device",
+    "ipt_preview_values",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -194,6 +196,8 @@ def load(path: str | os.PathLike | None = None):
         lib.ipt_pgm.argtypes = [C.c_void_p, C.POINTER(PgmParams)] + [C.c_void_p] * 5
         lib.ipt_logf_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         lib.ipt_logf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    if hasattr(lib, "ipt_preview_values"):  # ABI 7 addition
+        lib.ipt_preview_values.argtypes = [C.c_void_p, C.POINTER(Params)] + [C.c_void_p] * 4
     if path is None:
         _lib = lib
     return lib
@@ -307,6 +311,21 @@ class Context:
             self.h, C.byref(p), vals.ctypes.data, codes.ctypes.data))
         shape = (p.spp, p.height, p.width)
         return vals.reshape(shape), codes.reshape(shape)
+
+    def preview_values(self, p: Params, kinds: bool = True, hits: bool = True):
+        """The preview estimator's samples (ipt_preview_values): (values, codes,
+        kinds or None, hits or None), shaped [spp][H][W] and [spp][H][W][6]."""
+        n = p.spp * p.width * p.height
+        vals = np.zeros(n, np.float32)
+        codes = np.zeros(n, np.uint8)
+        kd = np.zeros(n, np.uint8) if kinds else None
+        ht = np.zeros(6 * n, np.float32) if hits else None
+        _check(self.lib, self.h, self.lib.ipt_preview_values(
+            self.h, C.byref(p), vals.ctypes.data, codes.ctypes.data,
+            kd.ctypes.data if kinds else None, ht.ctypes.data if hits else None))
+        shape = (p.spp, p.height, p.width)
+        return (vals.reshape(shape), codes.reshape(shape), kd.reshape(shape) if kinds else None,
+                ht.reshape(shape + (6,)) if hits else None)
 
     def render(self, p: Params, img: dict):
         """Host-buffer render into img = {pixels, counters, sums?, pixel_max?} (numpy)."""

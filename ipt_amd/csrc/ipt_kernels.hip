@@ -2563,6 +2563,125 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     }
 }
 
+// ------------------------------------------------------------------ preview
+// ray_power_preview (main.cpp:55-92) in place of ray_power_recursive
+// (IPT_FLAG_PREVIEW): one geometry trace and one traceRayToLight per camera
+// ray, 1 for a visible light, 0 for a miss, dot(normal, -direction) /
+// length(direction) for a surface. One thread per work unit, raygen, trace and
+// shade fused: no unit pool, no DFS stack, no raygen records, no LDS, and
+// neither sampling table is read.
+// ipt_preview_values' per-sample outputs (FULL instances; either may be null)
+struct PreviewOut {
+    uint8_t* kinds;  // [units] outcome | si << 2 | li << 3, 0xff untraced
+    float* hits;     // [units][6] position, normal
+};
+// surface_intersection::normal of the hit primitive, as geometry_trace's
+// callers see it: -planes[i] of GeometrySphereInBox.cpp:13-17 (the negated
+// zeros included), GeometryFloor / GeometryCorner's constants,
+// normalize(position [- centre]) and GeometrySmallPt.cpp:41's flip (the path
+// kernel's frame_normal, normalized)
+template <int GEOM>
+__device__ __forceinline__ vec3 preview_normal(const KParams& kp, int prim, vec3 pos) {
+    if (GEOM == IPT_GEOM_FLOOR) return v3(0.0f, 0.0f, 1.0f);
+    if (GEOM == IPT_GEOM_CORNER) return v3(prim == 0 ? 1.0f : 0.0f, prim == 1 ? 1.0f : 0.0f, prim == 2 ? 1.0f : 0.0f);
+    if (prim < 5) {
+        const float one = prim >= 3 ? 1.0f : -1.0f;
+        return v3(prim == 0 || prim == 3 ? one : -0.0f, prim == 1 ? one : -0.0f, prim == 2 || prim == 4 ? one : -0.0f);
+    }
+    if (GEOM == IPT_GEOM_SPHERE_IN_BOX) return normalize(pos);
+    const float4 sp = kp.spheres[prim - 6];
+    const vec3 v = normalize(pos - v3(sp.x, sp.y, sp.z));
+    if (GEOM == IPT_GEOM_SMALLPT && !((double)sp.w < 100.0)) return -v;
+    return v;
+}
+// FULL: the counting / AOV instance (IPT_FLAG_COUNTERS, ipt_preview_values);
+// the displayed path's instance carries neither the counters nor the stores.
+template <bool FULL, int GEOM>
+__global__ __launch_bounds__(256) void preview_kernel(const KParams kp, const PreviewOut po) {
+    const unsigned long long unit = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    // (every lane stays to the end: the FULL instances' wave sums)
+    const bool in = unit < kp.total_units;
+    uint32_t c_nodes = 0, c_tests = 0, c_lnode = 0, c_ltest = 0;
+    bool drift = false, valid = false, has_si = false, has_li = false;
+    if (in) {
+        const bool sharded = !(kp.n_shards <= 1 || kp.tile_rows <= 0);
+        const RayGen g = new_path_setup(kp, unit, sharded, kp.cand_rows);
+        drift = g.drift;
+        valid = g.valid;
+        uint8_t kind = 0xff;
+        vec3 hpos = v3(0, 0, 0), hnrm = v3(0, 0, 0);
+        if (valid) {
+            const vec3 o = kp.cam_pos, d = g.rd;
+            // CollectionLighting::traceRayToLight (CollectionLighting.cpp:23-34):
+            // the running compare in index order. More than kLdsLights
+            // AreaLights: the index-ordered light BVH (a skipped light is
+            // never hit); otherwise the scan itself, lights of any type
+            vec3 li_pos = v3(0, 0, 0);
+            auto light_step = [&](int l) {
+                vec3 hp, hn;
+                const bool h = light_trace<true>(kp.lights[l], o, d, &hp, &hn);
+                if (FULL) ++c_ltest;
+                if (h && (!has_li || longer(li_pos - o, hp - o))) {
+                    has_li = true;
+                    li_pos = hp;
+                }
+            };
+            if (kp.n_light_nodes > 0) {
+                const vec3 inv = v3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
+                int i = 0;
+                while (i < kp.n_light_nodes) {
+                    const BvhNode nd = kp.light_nodes[i];
+                    if (FULL) ++c_lnode;
+                    const bool enter = bvh_box_entry(nd, o, inv) != inf_();
+                    if (enter && nd.leaf >= 0) {
+                        const int first = nd.leaf & 0xffffff, cnt = nd.leaf >> 24;
+                        for (int l = first; l < first + cnt; ++l) light_step(l);
+                    }
+                    i = (enter && nd.leaf < 0) ? i + 1 : nd.skip;
+                }
+            } else {
+                for (int l = 0; l < kp.n_lights; ++l) light_step(l);
+            }
+            int prim = -1;
+            vec3 unused;
+            const float t = trace_geometry<FULL, GEOM, false>(kp, o, d, &prim, &unused, c_nodes, c_tests);
+            has_si = prim >= 0;
+            const vec3 si_pos = o + d * t;
+            // main.cpp:64-66 (the path kernel's depth-0 comparison)
+            const bool li_wins = has_li && (!has_si || longer(si_pos - o, li_pos - o));
+            float v = li_wins ? 1.0f : 0.0f;
+            if (!li_wins && has_si) {
+                hnrm = preview_normal<GEOM>(kp, prim, si_pos);
+                hpos = si_pos;
+                v = div_(dot(hnrm, -d), length(d));  // main.cpp:88
+            }
+            kp.values[unit] = v >= 0.0f ? v : 0.0f;  // main.cpp:214
+            if (li_wins) hpos = li_pos;
+            kind = (uint8_t)((li_wins ? 2 : (has_si ? 1 : 0)) | (has_si ? 4 : 0) | (has_li ? 8 : 0));
+        }
+        if (FULL) {
+            if (po.kinds) po.kinds[unit] = kind;
+            if (po.hits) {
+                float* h = po.hits + 6 * unit;
+                h[0] = hpos.x; h[1] = hpos.y; h[2] = hpos.z;
+                h[3] = hnrm.x; h[4] = hnrm.y; h[5] = hnrm.z;
+            }
+        }
+    }
+    if (FULL && kp.count) {
+        // the reference restatement's events: a path and a traced ray per
+        // valid sample, every light traced once by traceRayToLight
+        const uint32_t nl = valid ? (uint32_t)kp.n_lights : 0u;
+        const uint32_t vals[10] = {valid ? 1u : 0u, valid ? 1u : 0u, has_si ? 1u : 0u, has_li ? 1u : 0u, nl,
+                                   drift ? 1u : 0u, c_nodes, c_tests, c_lnode, c_ltest};
+        const int slot[10] = {0, 1, 2, 3, 9, 10, 11, 12, 13, 14};
+        for (int k = 0; k < 10; ++k) {
+            const int s = wave_scan_add((int)vals[k]);  // (< 2^31 per wave)
+            if ((threadIdx.x & 63) == 63 && s) atomicAdd(&kp.counters[slot[k]], (unsigned long long)(uint32_t)s);
+        }
+    }
+}
+
 struct AParams {
     int W, H, spp, n_cand;
     const int* cand_of_row;  // [H] candidate index or -1
@@ -3058,6 +3177,10 @@ struct WorkSlot {
     uint8_t* d_codes = nullptr;
     uint4* d_rg = nullptr;  // raygen_kernel records, 2 x 16 B per element
     size_t work_cap = 0;    // elements
+    size_t rg_cap = 0;      // elements of d_rg (full-estimator launches only)
+    uint8_t* d_kinds = nullptr;  // ipt_preview_values' per-sample outputs
+    float* d_hits = nullptr;
+    size_t kinds_cap = 0, hits_cap = 0;
     uint8_t* d_flags = nullptr;
     size_t flags_cap = 0;
     int* d_cand_rows = nullptr;
@@ -3257,26 +3380,45 @@ int ensure_frame_table(ipt_ctx* ctx, hipStream_t st) {
 // Work buffers grow on demand. A buffer's capacity is dropped to 0 together
 // with the buffer, so a failed regrowth never leaves a stale capacity over a
 // null pointer.
-int ensure_work(ipt_ctx* ctx, WorkSlot& S, size_t elems, size_t npix, int H, int n_cand) {
+// rg_elems: the raygen records (0 for a preview launch, which has none: 5 B
+// per unit instead of 37); kinds_elems / hits_elems: ipt_preview_values' outputs.
+int ensure_work(ipt_ctx* ctx, WorkSlot& S, size_t elems, size_t npix, int H, int n_cand, size_t rg_elems,
+                size_t kinds_elems, size_t hits_elems) {
     // (the caller has waited for the slot's previous launch and its readers)
     if (elems > S.work_cap) {
         if (S.d_values) hipFree(S.d_values);
         if (S.d_codes) hipFree(S.d_codes);
-        if (S.d_rg) hipFree(S.d_rg);
         S.d_values = nullptr;
         S.d_codes = nullptr;
-        S.d_rg = nullptr;
         S.work_cap = 0;
         DevBuf<float> v;
         DevBuf<uint8_t> c;
-        DevBuf<uint4> g;
         HIPCHECK(ctx, hipMalloc(&v.p, elems * sizeof(float)));
         HIPCHECK(ctx, hipMalloc(&c.p, elems));
-        if (IPT_RAYGEN) HIPCHECK(ctx, hipMalloc(&g.p, elems * 2 * sizeof(uint4)));
         S.d_values = v.release();
         S.d_codes = c.release();
-        S.d_rg = g.release();
         S.work_cap = elems;
+    }
+    if (IPT_RAYGEN && rg_elems > S.rg_cap) {
+        if (S.d_rg) hipFree(S.d_rg);
+        S.d_rg = nullptr;
+        S.rg_cap = 0;
+        HIPCHECK(ctx, hipMalloc(&S.d_rg, rg_elems * 2 * sizeof(uint4)));
+        S.rg_cap = rg_elems;
+    }
+    if (kinds_elems > S.kinds_cap) {
+        if (S.d_kinds) hipFree(S.d_kinds);
+        S.d_kinds = nullptr;
+        S.kinds_cap = 0;
+        HIPCHECK(ctx, hipMalloc(&S.d_kinds, kinds_elems));
+        S.kinds_cap = kinds_elems;
+    }
+    if (hits_elems > S.hits_cap) {
+        if (S.d_hits) hipFree(S.d_hits);
+        S.d_hits = nullptr;
+        S.hits_cap = 0;
+        HIPCHECK(ctx, hipMalloc(&S.d_hits, hits_elems * 6 * sizeof(float)));
+        S.hits_cap = hits_elems;
     }
     if (npix > S.flags_cap) {
         if (S.d_flags) hipFree(S.d_flags);
@@ -3420,7 +3562,7 @@ unsigned long long word_threshold(float c) {
 }
 
 int needed_susp(const ipt_params* p);
-int validate(ipt_ctx* ctx, const ipt_params* p) {
+int validate(ipt_ctx* ctx, const ipt_params* p, bool preview = false) {
     if (!ctx) return IPT_E_INVALID;
     if (!p) return fail(ctx, IPT_E_INVALID, "params is NULL");
     if (!ctx->has_scene) return fail(ctx, IPT_E_NOSCENE, "no scene uploaded");
@@ -3429,6 +3571,11 @@ int validate(ipt_ctx* ctx, const ipt_params* p) {
     if ((int64_t)p->width * p->height > (int64_t)1 << 31)
         return fail(ctx, IPT_E_INVALID, "frame larger than 2^31 pixels");
     if (p->spp < 0 || p->spp_offset < 0) return fail(ctx, IPT_E_INVALID, "negative spp");
+    const bool bad_shard = p->n_shards > 1 && (p->shard_id < 0 || p->shard_id >= p->n_shards);
+    // the preview estimator reads neither n_rays nor depth_max (main.cpp:55's
+    // unnamed parameters): any values are accepted
+    if (preview || (p->flags & IPT_FLAG_PREVIEW))
+        return bad_shard ? fail(ctx, IPT_E_INVALID, "shard_id out of range") : IPT_OK;
     // a suspended level stores its iteration count in the low bits of its meta
     // word (ti | kind << s, ti <= n_rays): s = 8 for n_rays < 256, else 16,
     // which leaves 16 bits for the node kind (6 + sphere index)
@@ -3441,8 +3588,7 @@ int validate(ipt_ctx* ctx, const ipt_params* p) {
     // depth_max <= 9 (the MAXSUSP = 8 instances)
     if (needed_susp(p) > 8)
         return fail(ctx, IPT_E_UNSUPPORTED, "n_rays > 255 with depth_max > 9: more than 8 suspended levels");
-    if (p->n_shards > 1 && (p->shard_id < 0 || p->shard_id >= p->n_shards))
-        return fail(ctx, IPT_E_INVALID, "shard_id out of range");
+    if (bad_shard) return fail(ctx, IPT_E_INVALID, "shard_id out of range");
     return IPT_OK;
 }
 
@@ -3539,8 +3685,30 @@ int launch_path(ipt_ctx* ctx, const KParams& kp, hipStream_t st, bool count) {
     return count ? launch_path2<MAXSUSP, true>(ctx, kp, st) : launch_path2<MAXSUSP, false>(ctx, kp, st);
 }
 
+template <bool FULL>
+int launch_preview(ipt_ctx* ctx, const KParams& kp, const PreviewOut& po, hipStream_t st) {
+    const dim3 grid((unsigned)((kp.total_units + 255) / 256)), block(256);
+    switch (kp.geometry_kind) {
+#define IPT_PREVIEW_CASE(G) \
+    case G: hipLaunchKernelGGL((preview_kernel<FULL, G>), grid, block, 0, st, kp, po); break;
+        IPT_PREVIEW_CASE(IPT_GEOM_SPHERES_IN_BOX)
+        IPT_PREVIEW_CASE(IPT_GEOM_FLOOR)
+        IPT_PREVIEW_CASE(IPT_GEOM_CORNER)
+        IPT_PREVIEW_CASE(IPT_GEOM_SPHERES)
+        IPT_PREVIEW_CASE(IPT_GEOM_SMALLPT)
+#undef IPT_PREVIEW_CASE
+        default: hipLaunchKernelGGL((preview_kernel<FULL, IPT_GEOM_SPHERE_IN_BOX>), grid, block, 0, st, kp, po); break;
+    }
+    HIPCHECK(ctx, hipGetLastError());
+    return IPT_OK;
+}
+
+// preview: ray_power_preview's launches (IPT_FLAG_PREVIEW, or forced by
+// ipt_preview_values, whose host_kinds / host_hits may each be null)
 int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t st,
-                  float* host_values, uint8_t* host_codes) {
+                  float* host_values, uint8_t* host_codes, bool preview = false, uint8_t* host_kinds = nullptr,
+                  float* host_hits = nullptr) {
+    preview = preview || (p->flags & IPT_FLAG_PREVIEW) != 0;
     std::vector<int> rows, of_row;
     candidate_rows(p, rows, of_row);
     const int n_cand = (int)rows.size();
@@ -3557,31 +3725,38 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
     // out of work (the longest paths finish alone; 7 % of a 32-spp C2 launch),
     // so few large launches beat many small ones (C2 1024^2 x 256 spp is a
     // single launch).
-    constexpr size_t kUnitBytes = sizeof(float) + 1 + (IPT_RAYGEN ? 2 * sizeof(uint4) : 0);
+    // (a preview unit is its value and code, 5 B, plus ipt_preview_values'
+    // outputs; it has no raygen record and its launches read no table)
+    constexpr size_t kRgBytes = IPT_RAYGEN ? 2 * sizeof(uint4) : 0;
+    const size_t unit_bytes = sizeof(float) + 1 + (preview ? (host_kinds ? 1 : 0) + (host_hits ? 6 * sizeof(float) : 0) : kRgBytes);
     size_t budget = (size_t)1 << 29;
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            size_t avail = free_b + (ctx->slot[0].work_cap + ctx->slot[1].work_cap) * kUnitBytes;
-            const size_t tables = (ctx->d_cos_a ? 0 : ((size_t)3 << 26)) +
+            size_t avail = free_b + (ctx->slot[0].work_cap + ctx->slot[1].work_cap) * (sizeof(float) + 1) +
+                           (preview ? 0 : (ctx->slot[0].rg_cap + ctx->slot[1].rg_cap) * kRgBytes);
+            const size_t tables = preview ? 0 :
+                                  (ctx->d_cos_a ? 0 : ((size_t)3 << 26)) +
                                   (ctx->d_frame_sc || !frame_table_user(ctx->geometry_kind)
                                        ? 0 : kFrameTabEntries * sizeof(float2));
             avail = avail > tables ? avail - tables : 0;
             // (two slots: consecutive launches hold a chunk each)
-            budget = std::min(budget, std::max<size_t>(per_pass, avail / 8 * 3 / kUnitBytes));
+            budget = std::min(budget, std::max<size_t>(per_pass, avail / 8 * 3 / unit_bytes));
         }
     }
     if (ctx->chunk_cap_test) budget = std::min(budget, std::max<size_t>(per_pass, ctx->chunk_cap_test));
     const size_t n_chunks = std::max<size_t>(1, ((size_t)p->spp * per_pass + budget - 1) / budget);
     int chunk = (int)std::max<size_t>(1, ((size_t)p->spp + n_chunks - 1) / n_chunks);
     while (chunk > 1 && (size_t)chunk * per_pass > budget) --chunk;
-    int rc = ensure_cos_tables(ctx, st);
+    // (the preview reads neither table: a context that only renders previews
+    // never builds them)
+    int rc = preview ? IPT_OK : ensure_cos_tables(ctx, st);
     if (rc) return rc;
-    if (frame_table_user(ctx->geometry_kind)) {  // path_kernel's frame builds
+    if (!preview && frame_table_user(ctx->geometry_kind)) {  // path_kernel's frame builds
         rc = ensure_frame_table(ctx, st);
         if (rc) return rc;
     }
-    const int susp = needed_susp(p);  // <= 8 (validate)
+    const int susp = preview ? 0 : needed_susp(p);  // <= 8 (validate)
     const bool count = (p->flags & IPT_FLAG_COUNTERS) != 0;
     for (int s0 = 0; s0 < p->spp; s0 += chunk) {
         const int ns = std::min(chunk, p->spp - s0);
@@ -3591,12 +3766,15 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         // the host only where it rewrites device memory itself
         WorkSlot& S = ctx->slot[ctx->next_slot];
         ctx->next_slot ^= 1u;
-        const bool grow = (size_t)chunk * per_pass > S.work_cap || (size_t)W * H > S.flags_cap ||
-                          n_cand > S.cand_cap_rows || H > S.cand_cap_h;
+        const size_t elems = (size_t)chunk * per_pass;
+        const size_t rg_elems = preview ? 0 : elems, kinds_elems = host_kinds ? elems : 0, hits_elems = host_hits ? elems : 0;
+        const bool grow = elems > S.work_cap || (size_t)W * H > S.flags_cap || n_cand > S.cand_cap_rows ||
+                          H > S.cand_cap_h || (IPT_RAYGEN && rg_elems > S.rg_cap) || kinds_elems > S.kinds_cap ||
+                          hits_elems > S.hits_cap;
         const int plan[5] = {H, p->tile_rows, p->n_shards, p->shard_id, plane_of(p)};
         const bool replan = !std::equal(plan, plan + 5, S.plan);
         if (S.used && (grow || replan)) HIPCHECK(ctx, hipEventSynchronize(S.done));
-        rc = ensure_work(ctx, S, (size_t)chunk * per_pass, (size_t)W * H, H, n_cand);
+        rc = ensure_work(ctx, S, elems, (size_t)W * H, H, n_cand, rg_elems, kinds_elems, hits_elems);
         if (rc) return rc;
         if (replan) {
             // (synchronous copies: the host vectors do not outlive the call)
@@ -3611,7 +3789,10 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         WorkSlot& P = ctx->slot[sidx ^ 1u];
         // (P's counter is reset only by P's next launch, which waits for this
         // launch's pool in turn, so this wait cannot miss its value)
-        if (P.used && !P.idle) {
+        // (a preview launch has no tail to overlap and takes no gate; a preview
+        // predecessor leaves P.seq at that of P's last full launch, which
+        // precedes it in P's stream)
+        if (!preview && P.used && !P.idle) {
             if (ctx->gate_on_pool)
                 HIPCHECK(ctx, hipStreamWaitValue64(S.st, P.d_drained, P.seq, hipStreamWaitValueGte, ~0ull));
             else
@@ -3764,14 +3945,21 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         HIPCHECK(ctx, hipMemsetAsync(S.d_unit, 0, sizeof(unsigned long long), ss));
         HIPCHECK(ctx, hipMemsetAsync(S.d_flags, 0, (size_t)W * H, ss));
         HIPCHECK(ctx, hipEventRecord(tm.t0, ss));
+        if (preview) {
+            // one fused kernel; the counting / AOV instance only where asked
+            const PreviewOut po{host_kinds ? S.d_kinds : nullptr, host_hits ? S.d_hits : nullptr};
+            rc = (count || po.kinds || po.hits) ? launch_preview<true>(ctx, kp, po, ss) : launch_preview<false>(ctx, kp, po, ss);
+            if (rc) return rc;
+        } else {
         if (IPT_RAYGEN) {
             hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((kp.total_units + 255) / 256)), dim3(256), 0, ss, kp);
             HIPCHECK(ctx, hipGetLastError());
         }
         rc = susp <= 4 ? launch_path<4>(ctx, kp, ss, count) : launch_path<8>(ctx, kp, ss, count);
         if (rc) return rc;
-        S.total = kp.total_units;
         S.seq = kp.drain_seq;
+        }
+        S.total = kp.total_units;
         HIPCHECK(ctx, hipEventRecord(tm.t1, ss));
         HIPCHECK(ctx, hipEventRecord(S.path_end, ss));
         if (host_values) {  // [spp][H][W] (whole frames: per_pass == W * H)
@@ -3780,6 +3968,11 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             HIPCHECK(ctx, hipMemcpyAsync(host_codes + (size_t)s0 * per_pass, S.d_codes, ns * per_pass,
                                          hipMemcpyDeviceToHost, ss));
         }
+        if (host_kinds)
+            HIPCHECK(ctx, hipMemcpyAsync(host_kinds + (size_t)s0 * per_pass, S.d_kinds, ns * per_pass, hipMemcpyDeviceToHost, ss));
+        if (host_hits)
+            HIPCHECK(ctx, hipMemcpyAsync(host_hits + (size_t)s0 * per_pass * 6, S.d_hits, sizeof(float) * 6 * ns * per_pass,
+                                         hipMemcpyDeviceToHost, ss));
         if (!img) HIPCHECK(ctx, hipEventRecord(S.done, ss));
         if (img) {
             // the render plane's replay: on the caller's stream, in call order,
@@ -3966,7 +4159,7 @@ void ipt_destroy(ipt_ctx* ctx) {
     for (void* b : bufs)
         if (b) hipFree(b);
     for (WorkSlot& S : ctx->slot) {
-        void* sb[] = {S.d_values, S.d_codes, S.d_rg, S.d_flags, S.d_cand_rows, S.d_cand_of_row, S.d_unit, S.d_drained};
+        void* sb[] = {S.d_values, S.d_codes, S.d_rg, S.d_kinds, S.d_hits, S.d_flags, S.d_cand_rows, S.d_cand_of_row, S.d_unit, S.d_drained};
         for (void* b : sb)
             if (b) hipFree(b);
         if (S.done) hipEventDestroy(S.done);
@@ -4480,6 +4673,20 @@ int ipt_render_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t*
     if (p->n_shards > 1) return fail(ctx, IPT_E_UNSUPPORTED, "ipt_render_values renders whole frames");
     hipSetDevice(ctx->device);
     rc = render_chunks(ctx, p, nullptr, ctx->stream, values, codes);
+    const int rw = drain(ctx);  // the host copies run on the slot streams
+    if (rc) return rc;
+    if (rw) return rw;
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return IPT_OK;
+}
+
+int ipt_preview_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t* codes, uint8_t* kinds, float* hits) {
+    int rc = validate(ctx, p, true);
+    if (rc) return rc;
+    if (!values || !codes) return fail(ctx, IPT_E_INVALID, "values/codes are NULL");
+    if (p->n_shards > 1) return fail(ctx, IPT_E_UNSUPPORTED, "ipt_preview_values renders whole frames");
+    hipSetDevice(ctx->device);
+    rc = render_chunks(ctx, p, nullptr, ctx->stream, values, codes, true, kinds, hits);
     const int rw = drain(ctx);  // the host copies run on the slot streams
     if (rc) return rc;
     if (rw) return rw;

@@ -193,6 +193,10 @@ struct RenderParams {
     int depth_max = 8;    // main.cpp:94
     uint64_t seed = 20241223;
     bool counters = false;
+    // ray_power_preview (main.cpp:55-92) instead of ray_power_recursive: the
+    // frame shown while the camera moves (IPT_FLAG_PREVIEW; n_rays and
+    // depth_max are then not read). Every render call below takes it.
+    bool preview = false;
     // destination-row tile shard of this call (ipt_params.tile_rows / n_shards /
     // shard_id): n_shards <= 1 renders the whole frame
     int tile_rows = 16;
@@ -229,7 +233,8 @@ class GpuRenderer {
     void render(GuiRenderPlane& plane, const RenderParams& p);
     // the same into a C-ABI image (32-bit counters); with p.n_shards > 1 only
     // the shard's rows of it are read and written (ipt_render). flags: further
-    // IPT_FLAG_* bits of the call (IPT_FLAG_GUI_PLANE for a Gui plane's image)
+    // IPT_FLAG_* bits of the call (IPT_FLAG_GUI_PLANE for a Gui plane's image,
+    // IPT_FLAG_PREVIEW as p.preview sets it)
     void render_image(ipt_image& img, size_t width, size_t height, const RenderParams& p, uint32_t flags = 0);
     // host <-> device bytes of the last render (ipt_transfer_bytes): the
     // context keeps its rows of the plane on its device between calls

@@ -12,7 +12,7 @@
 //              [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]
 //              [--pgm result.pgm] [--smooth SIDE] [--smoothed-max SIDE]
 //              [--glare CUTOFF --glare-out glare.pfm]
-//              [--gpu-display] [--gui-plane] [--white-percentile F]
+//              [--gpu-display] [--gui-plane] [--preview] [--white-percentile F]
 //              [--histogram hist.txt [--hist-buckets 400]]
 //
 // --gui-plane renders into the Gui's plane (GuiRenderPlane, Gui::addRay's row
@@ -22,6 +22,11 @@
 // device. It composes with --gpu-display, --glare, --passes, --devices, --pfm
 // and --counts; --smooth, --smoothed-max and --pgm are GridRenderPlane's
 // filters and main.cpp's PGM writer for it and are refused.
+// --preview renders with the reference's preview estimator (ray_power_preview,
+// main.cpp:55-92: one geometry trace and one light trace per camera ray, the
+// frame a viewer shows while the camera moves; IPT_FLAG_PREVIEW). --n-rays and
+// --depth are then not read. It composes with --gui-plane, --gpu-display,
+// --devices and every output option.
 // --gpu-display takes the PNG's bytes from GpuRenderer::display (the display
 // pipeline on the GPU, with the --glare cutoff's bloom when one is given, as
 // Gui::updateDisplay shows it) instead of the host's to_gray8; without
@@ -66,7 +71,7 @@ namespace {
                  "                  [--out result.png] [--pfm pixels.pfm] [--counts counts.u32]\n"
                  "                  [--pgm result.pgm] [--smooth SIDE] [--smoothed-max SIDE]\n"
                  "                  [--glare CUTOFF --glare-out F.pfm]\n"
-                 "                  [--gpu-display] [--gui-plane] [--white-percentile F]\n"
+                 "                  [--gpu-display] [--gui-plane] [--preview] [--white-percentile F]\n"
                  "                  [--histogram hist.txt [--hist-buckets 400]]\n");
     std::exit(2);
 }
@@ -77,7 +82,7 @@ int main(int argc, char** argv) {
     double white_percentile = -1.0;
     long hist_buckets = 400;
     long smooth = 0, smoothed_max = 0;
-    bool gpu_display = false, gui_plane = false;
+    bool gpu_display = false, gui_plane = false, preview = false;
     double glare = -1.0;
     long width = 640, height = 640, spp = 16, passes = 1, n_rays = 16, depth = 8, device = 0, tile_rows = 16;
     std::vector<int> devices;
@@ -115,6 +120,7 @@ int main(int argc, char** argv) {
         else if (a == "--glare-out") glare_out = val();
         else if (a == "--gpu-display") gpu_display = true;
         else if (a == "--gui-plane") gui_plane = true;
+        else if (a == "--preview") preview = true;
         else if (a == "--white-percentile") white_percentile = std::atof(val());
         else if (a == "--histogram") hist_out = val();
         else if (a == "--hist-buckets") hist_buckets = std::atol(val());
@@ -144,6 +150,7 @@ int main(int argc, char** argv) {
         p.n_rays = (int)n_rays;
         p.depth_max = (int)depth;
         p.seed = seed;
+        p.preview = preview;
         double kernel_ms = 0.0;
         const auto t0 = std::chrono::steady_clock::now();
         for (long pass = 0; pass < passes; ++pass) {  // progressive: each batch continues the RNG stream
