@@ -212,13 +212,11 @@ inline void bvh_build_spheres(const float* cr, int n, const float cam[3], float 
 // candidate. Exactness, with the BVH's padded sphere boxes and margin:
 // * registration: a sphere's padded box (ipt_bvh.h header) is the bound of
 //   its padded ball (centre c, radius R = r + pad: the box's half-width), and
-//   any ray the exact sphere_t accepts passes within R of c. With
-//   IPT_GRID_SPHERE_REG (default) the sphere is registered in every cell of
-//   its box range (inflated by m, computed in double, rounded outward) whose
-//   distance to the box centre is at most R + m + 1e-6 (1 + |c|_1) (the last
-//   term covers the box centre's offset from the float centre, i.e. the
-//   roundings of c -+ r), times (1 + 1e-9); without it, in every cell of the
-//   box range;
+//   any ray the exact sphere_t accepts passes within R of c. The sphere is
+//   registered in every cell of its box range (inflated by m, computed in
+//   double, rounded outward) whose distance to the box centre is at most
+//   R + m + 1e-6 (1 + |c|_1) (the last term covers the box centre's offset
+//   from the float centre, i.e. the roundings of c -+ r), times (1 + 1e-9);
 // * walk: the DDA's float rounding (approximate reciprocals, cell-boundary
 //   t's) can only make it visit a cell adjacent to the exact ray's where the
 //   ray passes within ~1e-6 |t| of a cell edge. Let q be the exact ray's
@@ -245,33 +243,6 @@ struct SphereGrid {
     std::vector<int> start;         // [cells + 1]
     std::vector<BvhSphere> items;   // per-cell sphere records
 };
-
-// A grid cell with its first three items inline (64 bytes, one cache line):
-// the walk's next cell is known from the DDA alone, so its record -- item
-// range and first items -- is fetched one cell ahead in a single round trip
-// instead of the range, then the items. Items beyond the third are read from
-// SphereGrid::items[s0 + 3, s1) as before; it[q] copies items[s0 + q].c / r.
-struct GridCell {
-    int s0, s1, pad0, pad1;
-    float it[3][4];
-};
-static_assert(sizeof(GridCell) == 64, "GridCell is one 64-byte line");
-inline void grid_cells_build(const SphereGrid& g, std::vector<GridCell>& cells) {
-    const size_t nc = g.start.size() - 1;
-    cells.assign(nc, GridCell{});
-    for (size_t c = 0; c < nc; ++c) {
-        GridCell& r = cells[c];
-        r.s0 = g.start[c];
-        r.s1 = g.start[c + 1];
-        for (int q = 0; q < 3 && r.s0 + q < r.s1; ++q) {
-            const BvhSphere& b = g.items[(size_t)r.s0 + q];
-            r.it[q][0] = b.c[0];
-            r.it[q][1] = b.c[1];
-            r.it[q][2] = b.c[2];
-            r.it[q][3] = b.r;
-        }
-    }
-}
 
 inline bool grid_build_spheres(const float* cr, int n, const float cam[3], float B, SphereGrid& g) {
     if (n <= 0) return false;
@@ -335,36 +306,31 @@ inline bool grid_build_spheres(const float* cr, int n, const float cam[3], float
         for (int i = 0; i < n; ++i) {
             int r0[3], r1[3];
             for (int a = 0; a < 3; ++a) range(a, lo[3 * (size_t)i + a], hi[3 * (size_t)i + a], &r0[a], &r1[a]);
-            // IPT_GRID_SPHERE_REG: of the padded box's cells, only those within
+            // of the padded box's cells, only those within
             // the padded sphere's reach (the box is that sphere's bound: its
             // half-width pad + r enlarges the radius), inflated by m plus a
             // rounding allowance, in double
-            double cc[3], reach2 = 0.0;
-            if (IPT_GRID_SPHERE_REG) {
-                double rr = 0.0;
-                for (int a = 0; a < 3; ++a) {
-                    cc[a] = 0.5 * (lo[3 * (size_t)i + a] + hi[3 * (size_t)i + a]);
-                    rr = std::max(rr, 0.5 * (hi[3 * (size_t)i + a] - lo[3 * (size_t)i + a]));
-                }
-                // + the box centre's offset from the float centre (fl(c -+ r) roundings)
-                const double reach = (rr + m + 1e-6 * (1.0 + std::fabs(cc[0]) + std::fabs(cc[1]) + std::fabs(cc[2]))) *
-                                     (1.0 + 1e-9);
-                reach2 = reach * reach;
+            double cc[3], rr = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                cc[a] = 0.5 * (lo[3 * (size_t)i + a] + hi[3 * (size_t)i + a]);
+                rr = std::max(rr, 0.5 * (hi[3 * (size_t)i + a] - lo[3 * (size_t)i + a]));
             }
+            // + the box centre's offset from the float centre (fl(c -+ r) roundings)
+            const double reach = (rr + m + 1e-6 * (1.0 + std::fabs(cc[0]) + std::fabs(cc[1]) + std::fabs(cc[2]))) *
+                                 (1.0 + 1e-9);
+            const double reach2 = reach * reach;
             for (int z = r0[2]; z <= r1[2]; ++z)
                 for (int y = r0[1]; y <= r1[1]; ++y)
                     for (int x = r0[0]; x <= r1[0]; ++x) {
-                        if (IPT_GRID_SPHERE_REG) {
-                            const int xyz[3] = {x, y, z};
-                            double d2 = 0.0;
-                            for (int a = 0; a < 3; ++a) {
-                                const double c0 = (double)g.g0[a] + (double)xyz[a] * (double)g.h[a];
-                                const double c1 = (double)g.g0[a] + (double)(xyz[a] + 1) * (double)g.h[a];
-                                const double dd = cc[a] < c0 ? c0 - cc[a] : (cc[a] > c1 ? cc[a] - c1 : 0.0);
-                                d2 += dd * dd;
-                            }
-                            if (d2 > reach2) continue;
+                        const int xyz[3] = {x, y, z};
+                        double d2 = 0.0;
+                        for (int a = 0; a < 3; ++a) {
+                            const double c0 = (double)g.g0[a] + (double)xyz[a] * (double)g.h[a];
+                            const double c1 = (double)g.g0[a] + (double)(xyz[a] + 1) * (double)g.h[a];
+                            const double dd = cc[a] < c0 ? c0 - cc[a] : (cc[a] > c1 ? cc[a] - c1 : 0.0);
+                            d2 += dd * dd;
                         }
+                        if (d2 > reach2) continue;
                         const size_t c = (size_t)x + (size_t)g.n[0] * ((size_t)y + (size_t)g.n[1] * z);
                         if (pass == 0) {
                             ++g.start[c + 1];

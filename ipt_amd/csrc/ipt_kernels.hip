@@ -54,6 +54,13 @@ constexpr int kStackFields = 6;   // pos3, res, mult, meta(i | kind<<8)
 constexpr int kPoolChunk = 256;   // work units per global atomic
 constexpr int kNumCounters = 15;
 
+// Unread fields: the fields marked (unread) below lost their last reader when
+// the build switches that selected their code were retired; the host leaves
+// them zero. They keep their places because KParams' layout decides how the
+// compiler groups the kernel-argument loads: taking any of them out regroups
+// those loads in some kernel and changes its register assignment or its
+// instruction count (DESIGN.md §9 has the counts per field group). Removing
+// them is a change of device code, to be measured as one.
 struct KParams {
     int W, H, spp, spp_offset, n_rays, depth_max;
     int meta_shift;  // a suspended level's meta word: ti | kind << meta_shift (8, or 16 for n_rays > 255)
@@ -92,15 +99,14 @@ struct KParams {
     float grid_g1[3];                     // g0 + (float)n * h, the grid's far corner (host-computed)
     int grid_n[3];
     const int* __restrict__ grid_start;   // [cells + 1]
-    // IPT_GRID_LDS: grid_start packed for LDS staging -- [grid_packed_nb] u32
-    // bases of 8-entry blocks, then [cells + 1] u8 offsets from them
+    // (unread: see the note on unread fields above KParams)
     const int* __restrict__ grid_packed;
     int grid_packed_words, grid_packed_nb;
-    const GridCell* __restrict__ grid_cells;  // [cells] range + first three items (IPT_GRID_INLINE)
+    const void* __restrict__ grid_cells;
     const BvhSphere* __restrict__ grid_items;
-    // the same items packed for the pipelined walk (IPT_GRID_C4): centre and
-    // radius as one float4 per item (16-byte stride: a cell's items share
-    // lines), original indices in a separate array
+    // the same items packed for the wave walk: centre and radius as one float4
+    // per item (16-byte stride: a cell's items share lines), original indices
+    // in a separate array
     const float4* __restrict__ grid_c4;
     const int* __restrict__ grid_idx;
     const BvhNode* __restrict__ bvh_nodes;     // n_nodes > 0: sphere BVH (ipt_bvh.h)
@@ -111,7 +117,7 @@ struct KParams {
     int lnodes_lds;                       // light BVH staged in LDS (kLightsGlobal)
     // kLightsGridA10/A01: coplanar axis-aligned lights on a lattice (LightGrid)
     const int* __restrict__ lgrid;        // [lg_nu * lg_nv] light index per cell, -1 = none
-    const float4* __restrict__ lax;       // [n_lights][3] LightAx records (IPT_LIGHT_AX_REC)
+    const float4* __restrict__ lax;       // [n_lights][3] LightAx records
     int lg_nu, lg_nv;
     float lg_u0, lg_v0, lg_icw, lg_ich;   // cell coordinates: (q - u0) * icw
     float lg_e;                           // candidate margin in cells (LightGrid::e)
@@ -119,36 +125,28 @@ struct KParams {
     // sa_pz and the light normal is (+-0, +-0, sa_nz): light picks at nodes
     // with sa_nz * (sa_pz - z) >= 0 are certain skips (sa_on, host-checked)
     // u01(w) < c  <=>  w < (ceil(c 2^24) << 8) (clamped to [0, 2^32]) for the
-    // draw word w: the single light's cdf[0], cdf[1] (pk_u0, pk_u1) and sa_cl
-    // (sa_u) as word thresholds (host: word_threshold)
+    // draw word w: the single light's cdf[0], cdf[1] (pk_u0, pk_u1) and the
+    // light-pick bound (sa_u: one light: cdf[0]; a lattice with a non-decreasing
+    // cdf: cdf[nl - 1]; else 0, never) as word thresholds (host: word_threshold)
     unsigned long long pk_u0, pk_u1, sa_u;
     int sa_on;
     float sa_pz, sa_nz;
-    // a pick r < sa_cl is a light pick (one light: cdf[0]; a lattice with a
-    // non-decreasing cdf: cdf[nl - 1]; else 0, never)
-    float sa_cl;
+    float sa_cl;                          // (unread)
     float lg_pn, lg_nn;                   // the lights' shared plane: P[na], n[na]
     int cdf_bsearch;                      // cdf non-decreasing: pick by binary search
     // |cdf[i] - (i+1) 2^-e| < 2^-e/2 for every light i and a non-decreasing
     // cdf (host-checked): the pick is floor(r 2^e) - 1, + 0 or + 1 by two cdf
-    // entries, then cdf[nl] decides past the lights (cdf_p2s = 2^e)
-    int cdf_p2;  // 1: near-uniform as above; 2: every threshold exact (KParams::cdf_p2e)
-    float cdf_p2s, cdf_end;
-    // the same pick on the draw's 24-bit integer g = w >> 8 (IPT_PICK_INT_CDF):
-    // floor(r 2^e) = g >> (24 - e) and r < c <=> g < ceil(c 2^24); the staged
-    // cdf then holds those integer thresholds (cdf_end_t: cdf[nl]'s)
+    // entries, then cdf[nl] decides past the lights. It is taken on the draw's
+    // 24-bit integer g = w >> 8: floor(r 2^e) = g >> (24 - e) and r < c <=> g <
+    // ceil(c 2^24); the staged cdf then holds those integer thresholds
+    // (cdf_end_t: cdf[nl]'s)
+    int cdf_p2;  // 1: near-uniform as above; 2: every threshold exact, no cdf read
+    float cdf_p2s, cdf_end;               // (unread)
     int cdf_p2e;
     uint32_t cdf_end_t;
-    // IPT_LPF_CALC: the lattice lights' sample fields are a formula of the
-    // light index i (host-checked for every light): P.x = lc_x0 + (float)(i &
-    // (2^lc_shift - 1)) * lc_dx, P.y = lc_y0 + (float)(i >> lc_shift) * lc_dy,
-    // x[XA] = lc_ax, y[YA] = lc_ay (C5's 16 x 16 split light, built that way)
+    // (unread)
     int lpf_calc, lc_shift;
     float lc_x0, lc_y0, lc_dx, lc_dy, lc_ax, lc_ay;
-    // IPT_LTR_CALC (with lpf_calc): every lattice light's inverse entries,
-    // area and power are the same (lc_ix .. lc_spow), so a light test reads
-    // only the light's weight; lg_ident 1 / 2: cell (i, j) holds light
-    // i + nu j / j + nv i (every cell, host-checked), no cell read
     int ltr_calc, lg_ident;
     float lc_ix, lc_iy, lc_area, lc_spow;
     const int* __restrict__ cdf_lo;       // [kCdfBuckets] or null: first c with cdf[c] > b/256
@@ -156,9 +154,9 @@ struct KParams {
     uint32_t per_pass32;                  // n_cand*W (< 2^32)
     int box_inrange;                      // camera and sphere list within 2^39 (box_plane_t<true>)
     const float* __restrict__ cos_a;      // [2^24] CosineDdf table by u1's 24 bits: sin(acos(sqrt(u1)))
-    const float2* __restrict__ cos_b;     // [2^24] by u2's 24 bits: (cos phi, sin phi)
+    const float2* __restrict__ cos_b;     // (unread)
     const float2* __restrict__ frame_sc;  // frame_table_kernel: RotateDdf angle (sin, cos) by to.z
-    const uint4* __restrict__ rg;         // IPT_RAYGEN: [total_units][2] raygen_kernel records
+    const uint4* __restrict__ rg;         // [total_units][2] raygen_kernel records
     int count;                            // raygen_kernel: accumulate the drift counter
     int plane;                            // new_path_setup: kPlaneGrid / kPlaneGui (IPT_FLAG_GUI_PLANE)
 };
@@ -351,192 +349,15 @@ __device__ __forceinline__ void sphere_grid_init(const KParams& kp, vec3 o, vec3
     cell = ia[0] | ia[1] << 8 | ia[2] << 16;
     tmx = v3(tm[0], tm[1], tm[2]);
 }
-__device__ __forceinline__ float4 grid_item(const KParams& kp, int k) {
-    if constexpr (IPT_GRID_C4) return kp.grid_c4[k];
-    return *reinterpret_cast<const float4*>(kp.grid_items[k].c);
-}
-__device__ __forceinline__ int grid_item_index(const KParams& kp, int k) {
-    if constexpr (IPT_GRID_C4) return kp.grid_idx[k];
-    return kp.grid_items[k].index;
-}
-// POS (the pipelined walk of the resumable instances, IPT_GRID_PIPE): bidx is
-// the best item's position in grid_items instead of its original index, so an
-// item is one 16-byte load and its index is read only on a tie (the caller
-// converts when the walk is done); IPT_GRID_ITEMS item loads are issued before
-// their tests, and the next cell's item range is fetched with them.
-template <bool COUNT, bool POS = false>
+// the wave walk's items: centre and radius as one 16-byte record, the original
+// index apart (read only on a tie and when the walk is done)
+__device__ __forceinline__ float4 grid_item(const KParams& kp, int k) { return kp.grid_c4[k]; }
+__device__ __forceinline__ int grid_item_index(const KParams& kp, int k) { return kp.grid_idx[k]; }
+template <bool COUNT>
 __device__ __forceinline__ void sphere_grid_walk(const KParams& kp, vec3 o, vec3 d, int& cell, vec3& tmx, float& best,
                                                  int& bidx, int budget, uint32_t& c_nodes,
-                                                 uint32_t& c_tests IPT_DIAG_PARAMS) {
+                                                 uint32_t& c_tests) {
     const vec3 inv = v3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
-    auto accept = [&](float t, int k2) {  // FractalSpheres.cpp:75-84's rule on item positions
-        if (isfinite_(t) && gt_1em6(fabs_(t))) {
-            if (t < best)
-                bidx = k2;
-            else if (t == best && bidx >= 0 && kp.grid_items[k2].index < kp.grid_items[bidx].index)
-                bidx = k2;
-            best = t < best ? t : best;
-        }
-    };
-    if constexpr (POS && IPT_GRID_INLINE) {
-        // cells as 64-byte records (GridCell: the item range and the first
-        // three items): the next cell follows from tmx alone, so its record is
-        // fetched while the current cell's items are tested -- one round trip
-        // per cell, overlapped, instead of a range load and then item loads.
-        // Same cells, items, tests and exit decisions as the walk below.
-        if (cell < 0 || budget <= 0) return;
-        auto lin_of = [&](int c) {
-            return (c & 0xff) + kp.grid_n[0] * (((c >> 8) & 0xff) + kp.grid_n[1] * (c >> 16));
-        };
-        auto load = [&](int l, int& a, int& b, float4* it) {
-            const uint4* r = reinterpret_cast<const uint4*>(kp.grid_cells + l);
-            const uint4 h = r[0];
-            it[0] = __builtin_bit_cast(float4, r[1]);
-            it[1] = __builtin_bit_cast(float4, r[2]);
-            it[2] = __builtin_bit_cast(float4, r[3]);
-            a = (int)h.x;
-            b = (int)h.y;
-        };
-        int lin = lin_of(cell);
-        int s0, s1;
-        float4 it[3];
-        load(lin, s0, s1, it);
-        for (;;) {
-            const int ix = cell & 0xff, iy = (cell >> 8) & 0xff, iz = cell >> 16;
-            int ncell;
-            vec3 ntm = tmx;
-            bool nvalid;
-            if (tmx.x <= tmx.y && tmx.x <= tmx.z) {
-                const int nx = d.x > 0.0f ? ix + 1 : ix - 1;
-                nvalid = !(nx < 0 || nx >= kp.grid_n[0]);
-                ncell = (cell & ~0xff) | (nx & 0xff);
-                ntm.x = ((kp.grid_g0[0] + (float)(d.x > 0.0f ? nx + 1 : nx) * kp.grid_h[0]) - o.x) * inv.x;
-            } else if (tmx.y <= tmx.z) {
-                const int ny = d.y > 0.0f ? iy + 1 : iy - 1;
-                nvalid = !(ny < 0 || ny >= kp.grid_n[1]);
-                ncell = (cell & ~0xff00) | (ny & 0xff) << 8;
-                ntm.y = ((kp.grid_g0[1] + (float)(d.y > 0.0f ? ny + 1 : ny) * kp.grid_h[1]) - o.y) * inv.y;
-            } else {
-                const int nz = d.z > 0.0f ? iz + 1 : iz - 1;
-                nvalid = !(nz < 0 || nz >= kp.grid_n[2]);
-                ncell = (cell & 0xffff) | (nz & 0xff) << 16;
-                ntm.z = ((kp.grid_g0[2] + (float)(d.z > 0.0f ? nz + 1 : nz) * kp.grid_h[2]) - o.z) * inv.z;
-            }
-            // the next record, unconditionally (this cell's again when there is none)
-            const int nlin = nvalid ? lin_of(ncell) : lin;
-            int n0, n1;
-            float4 nit[3];
-            load(nlin, n0, n1, nit);
-            if (COUNT) {
-                ++c_nodes;
-                c_tests += (uint32_t)(s1 - s0);
-            }
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                if (s0 + q < s1) accept(sphere_t(it[q].w, o - v3(it[q].x, it[q].y, it[q].z), d), s0 + q);
-            // items beyond the record (IPT_GRID_ITEMS loads in flight)
-            constexpr int X = IPT_GRID_ITEMS;
-            for (int k2 = s0 + 3; k2 < s1; k2 += X) {
-                float4 c4[X];
-#pragma unroll
-                for (int q = 0; q < X; ++q)
-                    c4[q] = *reinterpret_cast<const float4*>(kp.grid_items[k2 + q < s1 ? k2 + q : k2].c);
-#pragma unroll
-                for (int q = 0; q < X; ++q)
-                    if (k2 + q < s1) accept(sphere_t(c4[q].w, o - v3(c4[q].x, c4[q].y, c4[q].z), d), k2 + q);
-            }
-            --budget;
-            const float texit = fminf(fminf(tmx.x, tmx.y), tmx.z);
-            if (texit > (best * 1.0001f + 1e-5f + kp.bvh_tmargin + kp.grid_m) * 1.00001f + 1e-5f || !nvalid) {
-                cell = -1;
-                return;
-            }
-            cell = ncell;
-            tmx = ntm;
-            if (budget <= 0) return;
-            lin = nlin;
-            s0 = n0;
-            s1 = n1;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) it[q] = nit[q];
-        }
-    } else if constexpr (POS) {
-        // the next cell (it depends on tmx alone) and its item range are
-        // fetched before the current cell's items are tested, so the range
-        // load overlaps the item loads; the exit test (on best) then decides
-        // whether the walk moves there. Same cells, items and tests.
-        if (cell < 0 || budget <= 0) return;
-        auto lin_of = [&](int c) {
-            return (c & 0xff) + kp.grid_n[0] * (((c >> 8) & 0xff) + kp.grid_n[1] * (c >> 16));
-        };
-        int lin = lin_of(cell);
-        int s0 = kp.grid_start[lin], s1 = kp.grid_start[lin + 1];
-        for (;;) {
-#if IPT_PROF
-            if (prof_w) { IPT_PHASE(6); }  // one cell of the pipelined walk
-#endif
-            const int ix = cell & 0xff, iy = (cell >> 8) & 0xff, iz = cell >> 16;
-            int ncell;
-            vec3 ntm = tmx;
-            bool nvalid;
-            if (tmx.x <= tmx.y && tmx.x <= tmx.z) {
-                const int nx = d.x > 0.0f ? ix + 1 : ix - 1;
-                nvalid = !(nx < 0 || nx >= kp.grid_n[0]);
-                ncell = (cell & ~0xff) | (nx & 0xff);
-                ntm.x = ((kp.grid_g0[0] + (float)(d.x > 0.0f ? nx + 1 : nx) * kp.grid_h[0]) - o.x) * inv.x;
-            } else if (tmx.y <= tmx.z) {
-                const int ny = d.y > 0.0f ? iy + 1 : iy - 1;
-                nvalid = !(ny < 0 || ny >= kp.grid_n[1]);
-                ncell = (cell & ~0xff00) | (ny & 0xff) << 8;
-                ntm.y = ((kp.grid_g0[1] + (float)(d.y > 0.0f ? ny + 1 : ny) * kp.grid_h[1]) - o.y) * inv.y;
-            } else {
-                const int nz = d.z > 0.0f ? iz + 1 : iz - 1;
-                nvalid = !(nz < 0 || nz >= kp.grid_n[2]);
-                ncell = (cell & 0xffff) | (nz & 0xff) << 16;
-                ntm.z = ((kp.grid_g0[2] + (float)(d.z > 0.0f ? nz + 1 : nz) * kp.grid_h[2]) - o.z) * inv.z;
-            }
-            // unconditional load (the current cell's range when there is no next)
-            const int nlin = nvalid ? lin_of(ncell) : lin;
-            const int n0 = kp.grid_start[nlin], n1 = kp.grid_start[nlin + 1];
-            if (COUNT) {
-                ++c_nodes;
-                c_tests += (uint32_t)(s1 - s0);
-            }
-            auto test = [&](float4 c4, int k2) {
-                const float t = sphere_t(c4.w, o - v3(c4.x, c4.y, c4.z), d);
-                if (isfinite_(t) && gt_1em6(fabs_(t))) {
-                    if (t < best)
-                        bidx = k2;
-                    else if (t == best && bidx >= 0 && grid_item_index(kp, k2) < grid_item_index(kp, bidx))
-                        bidx = k2;
-                    best = t < best ? t : best;
-                }
-            };
-            constexpr int X = IPT_GRID_ITEMS;
-                for (int k2 = s0; k2 < s1; k2 += X) {
-                    float4 c4[X];
-#pragma unroll
-                    for (int q = 0; q < X; ++q)
-                        c4[q] = grid_item(kp, k2 + q < s1 ? k2 + q : k2);
-                    test(c4[0], k2);
-#pragma unroll
-                    for (int q = 1; q < X; ++q)
-                        if (k2 + q < s1) test(c4[q], k2 + q);
-                }
-            --budget;
-            const float texit = fminf(fminf(tmx.x, tmx.y), tmx.z);
-            if (texit > (best * 1.0001f + 1e-5f + kp.bvh_tmargin + kp.grid_m) * 1.00001f + 1e-5f || !nvalid) {
-                cell = -1;
-                return;
-            }
-            cell = ncell;
-            tmx = ntm;
-            if (budget <= 0) return;
-            lin = nlin;
-            s0 = n0;
-            s1 = n1;
-        }
-    }
     while (cell >= 0 && budget-- > 0) {
         const int ix = cell & 0xff, iy = (cell >> 8) & 0xff, iz = cell >> 16;
         const int lin = ix + kp.grid_n[0] * (iy + kp.grid_n[1] * iz);
@@ -610,8 +431,8 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// The resumable grid walk with the item tests spread over the whole wave
-// (IPT_GRID_WAVE). Per wave iteration every walking lane steps one cell: the
+// The resumable grid walk, with the item tests spread over the whole wave.
+// Per wave iteration every walking lane steps one cell: the
 // (lane, item) pairs of the cells the lanes stand on are numbered by a wave
 // prefix sum and tested 64 at a time, one pair per lane (the lane that owns
 // pair p is found by a ds_permute of the segment starts and a max-scan; its
@@ -620,25 +441,15 @@ __device__ __forceinline__ void wave_lds_sync() {
 // cell the positions are in original-index order (grid_build_spheres fills
 // each cell in index order) and accepted t are positive, so the slot ends as
 // the cell's (t, index) minimum; the owner merges it with `accept`, the
-// per-lane walk's rule (FractalSpheres.cpp:75-84: strict '<', lowest index on
+// scan's rule (FractalSpheres.cpp:75-84: strict '<', lowest index on
 // equal t, a plane never loses a tie). The tests run at full lane
 // utilisation instead of once per lane per item slot. Same cells, same tests
 // (sphere_t on the same operands), same exit decisions: the (t, index) minimum
 // does not depend on the order of the tests. Every lane of the wave calls it.
-// grid_start[lin] from global memory, or (IPT_GRID_LDS) from the packed copy
-// staged in LDS (gl): an 8-entry block's base plus the entry's byte offset
-__device__ __forceinline__ int grid_start_at(const KParams& kp, const int* gl, int lin) {
-    if constexpr (IPT_GRID_LDS != 0) {
-        const uint8_t* off = reinterpret_cast<const uint8_t*>(gl + kp.grid_packed_nb);
-        return gl[lin >> 3] + (int)off[lin];
-    }
-    return kp.grid_start[lin];
-}
-
 template <bool COUNT>
 __device__ __forceinline__ void sphere_grid_walk_wave(const KParams& kp, bool walking, vec3 o, vec3 d, int& cell,
                                                       vec3& tmx, float& best, int& bidx, int budget,
-                                                      unsigned long long* slots, int lane, const int* gl,
+                                                      unsigned long long* slots, int lane,
                                                       uint32_t& c_nodes, uint32_t& c_tests IPT_DIAG_PARAMS) {
     const vec3 inv = v3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
     auto lin_of = [&](int c) {
@@ -648,14 +459,12 @@ __device__ __forceinline__ void sphere_grid_walk_wave(const KParams& kp, bool wa
     int s0 = 0, s1 = 0;
     if (act) {
         const int lin = lin_of(cell);
-        s0 = grid_start_at(kp, gl, lin);
-        s1 = grid_start_at(kp, gl, lin + 1);
+        s0 = kp.grid_start[lin];
+        s1 = kp.grid_start[lin + 1];
     }
-    for (int it = 0;; ++it) {
-        // (after IPT_GRID_WAVE_FLOOR_IT iterations the wave stops once fewer than
-        // IPT_GRID_WAVE_FLOOR lanes walk; they resume in the next step)
+    for (;;) {
         const uint64_t am = __ballot(act);
-        if (!am || (it >= IPT_GRID_WAVE_FLOOR_IT && __popcll(am) < IPT_GRID_WAVE_FLOOR)) break;
+        if (!am) break;
 #if IPT_PROF
         // phase 6 (walk cell): one wave iteration, its walking lanes (every
         // lane of the wave runs this loop, so lane 0 counts)
@@ -689,8 +498,8 @@ __device__ __forceinline__ void sphere_grid_walk_wave(const KParams& kp, bool wa
             ncell = nvalid ? ncell : -1;
             // (no next cell: cell 0's range, unused)
             const int nlin = nvalid ? lin_of(ncell) : 0;
-            n0 = grid_start_at(kp, gl, nlin);
-            n1 = grid_start_at(kp, gl, nlin + 1);
+            n0 = kp.grid_start[nlin];
+            n1 = kp.grid_start[nlin + 1];
         }
         const int cnt = act ? s1 - s0 : 0;
         if (COUNT && act) {
@@ -732,18 +541,15 @@ __device__ __forceinline__ void sphere_grid_walk_wave(const KParams& kp, bool wa
                 q.o = v3(__shfl(o.x, sl), __shfl(o.y, sl), __shfl(o.z, sl));
                 q.d = v3(__shfl(d.x, sl), __shfl(d.y, sl), __shfl(d.z, sl));
                 q.k = p + __shfl(dk, sl);
-                if (IPT_GRID_WAVE_UNC)
-                    q.c4 = grid_item(kp, q.valid ? q.k : 0);
-                else if (q.valid)
-                    q.c4 = grid_item(kp, q.k);
+                q.c4 = grid_item(kp, q.valid ? q.k : 0);
             };
             auto test = [&](const Pair& q) {
-                // IPT_GRID_WAVE_UNC: every lane loads (item 0 for lanes without a
-                // pair) and the wave waits for the item here, outside the branch:
-                // otherwise a load left pending on the path that skips the test
-                // made the next round's load wait for every outstanding load,
-                // the next cell's range prefetch included (vmcnt(0))
-                if (IPT_GRID_WAVE_UNC) keep_alive(q.c4);
+                // every lane loads (item 0 for lanes without a pair) and the wave
+                // waits for the item here, outside the branch: otherwise a load left
+                // pending on the path that skips the test made the next round's load
+                // wait for every outstanding load, the next cell's range prefetch
+                // included (vmcnt(0))
+                keep_alive(q.c4);
                 if (q.valid) {
                     const float t = sphere_t(q.c4.w, q.o - v3(q.c4.x, q.c4.y, q.c4.z), q.d);
                     if (isfinite_(t) && gt_1em6(fabs_(t)))
@@ -753,16 +559,6 @@ __device__ __forceinline__ void sphere_grid_walk_wave(const KParams& kp, bool wa
                 }
             };
             int base = 0;
-            if constexpr (IPT_GRID_WAVE_PIPE) {
-                // the first two rounds' items fetched together
-                Pair q0, q1;
-                setup(0, q0);
-                const bool two = total > 64;
-                if (two) setup(64, q1);
-                test(q0);
-                if (two) test(q1);
-                base = 128;
-            }
             for (; base < total; base += 64) {
                 Pair q;
                 setup(base, q);
@@ -799,150 +595,6 @@ __device__ __forceinline__ void sphere_grid_walk_wave(const KParams& kp, bool wa
     }
 }
 
-// IPT_GRID_WAVE == 2: the same with two cells per lane per wave iteration --
-// the cell the lane stands on (A) and the next one (B), whose range was
-// fetched in the previous iteration; the two cells after them are located and
-// their ranges fetched while A's and B's items are tested -- and the slots
-// keyed by (t bits << 32 | original index) (the index is loaded with the
-// item), so bidx holds the original index and the minimum over two cells'
-// items is the scan's (t, index) rule directly. Exit tests after A and after
-// B as in the per-cell walk; B's items are tested even when the walk ends
-// after A, which is harmless (any sphere's t is a valid candidate of the
-// scan, and the exit bound only shrinks with best). Two cells of budget per
-// iteration.
-template <bool COUNT>
-__device__ __forceinline__ void sphere_grid_walk_wave2(const KParams& kp, bool walking, vec3 o, vec3 d, int& cell,
-                                                       vec3& tmx, float& best, int& bidx, int budget,
-                                                       unsigned long long* slots, uint8_t* own, int lane,
-                                                       uint32_t& c_nodes, uint32_t& c_tests) {
-    const vec3 inv = v3(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
-    auto lin_of = [&](int c) {
-        return (c & 0xff) + kp.grid_n[0] * (((c >> 8) & 0xff) + kp.grid_n[1] * (c >> 16));
-    };
-    // one DDA step from cell c with boundary t's tm (ties: x, then y, then z)
-    auto step = [&](int c, vec3 tm, int& nc, vec3& ntm, bool& nv) {
-        const int ix = c & 0xff, iy = (c >> 8) & 0xff, iz = c >> 16;
-        ntm = tm;
-        if (tm.x <= tm.y && tm.x <= tm.z) {
-            const int nx = d.x > 0.0f ? ix + 1 : ix - 1;
-            nv = !(nx < 0 || nx >= kp.grid_n[0]);
-            nc = (c & ~0xff) | (nx & 0xff);
-            ntm.x = ((kp.grid_g0[0] + (float)(d.x > 0.0f ? nx + 1 : nx) * kp.grid_h[0]) - o.x) * inv.x;
-        } else if (tm.y <= tm.z) {
-            const int ny = d.y > 0.0f ? iy + 1 : iy - 1;
-            nv = !(ny < 0 || ny >= kp.grid_n[1]);
-            nc = (c & ~0xff00) | (ny & 0xff) << 8;
-            ntm.y = ((kp.grid_g0[1] + (float)(d.y > 0.0f ? ny + 1 : ny) * kp.grid_h[1]) - o.y) * inv.y;
-        } else {
-            const int nz = d.z > 0.0f ? iz + 1 : iz - 1;
-            nv = !(nz < 0 || nz >= kp.grid_n[2]);
-            nc = (c & 0xffff) | (nz & 0xff) << 16;
-            ntm.z = ((kp.grid_g0[2] + (float)(d.z > 0.0f ? nz + 1 : nz) * kp.grid_h[2]) - o.z) * inv.z;
-        }
-    };
-    bool act = walking && cell >= 0 && budget > 0;
-    int s0 = 0, s1 = 0, cb = 0, a0 = 0, a1 = 0;
-    vec3 tmb = tmx;
-    bool bval = false;
-    if (act) {
-        const int l = lin_of(cell);
-        s0 = kp.grid_start[l];
-        s1 = kp.grid_start[l + 1];
-        step(cell, tmx, cb, tmb, bval);
-        if (bval) {
-            const int lb = lin_of(cb);
-            a0 = kp.grid_start[lb];
-            a1 = kp.grid_start[lb + 1];
-        }
-    }
-    while (__ballot(act)) {
-        // cells C and D after A, B and their ranges, in flight during the tests
-        int cc = 0, cd = 0, c0 = 0, c1 = 0, d0 = 0, d1 = 0;
-        vec3 tmc = tmb, tmd = tmb;
-        bool cval = false, dval = false;
-        if (act && bval) {
-            step(cb, tmb, cc, tmc, cval);
-            if (cval) {
-                const int lc = lin_of(cc);
-                c0 = kp.grid_start[lc];
-                c1 = kp.grid_start[lc + 1];
-                step(cc, tmc, cd, tmd, dval);
-                if (dval) {
-                    const int ld = lin_of(cd);
-                    d0 = kp.grid_start[ld];
-                    d1 = kp.grid_start[ld + 1];
-                }
-            }
-        }
-        const int cnta = act ? s1 - s0 : 0;
-        const int cnt = cnta + ((act && bval) ? a1 - a0 : 0);
-        if (COUNT && act) {
-            c_nodes += bval ? 2u : 1u;
-            c_tests += (uint32_t)cnt;
-        }
-        const int incl = wave_scan_add(cnt);
-        const int total = __builtin_amdgcn_readlane(incl, 63);
-        const int excl = incl - cnt;
-        if (total > 0) {
-            if (cnt > 0) slots[lane] = ~0ull;
-            // pair p of this lane: item p + da (p < ea, cell A) or p + db (cell B)
-            const int ea = excl + cnta, da = s0 - excl, db = a0 - ea;
-            for (int base = 0; base < total; base += 64) {
-                own[lane] = 0;
-                if (cnt > 0 && excl < base + 64 && incl > base) own[excl > base ? excl - base : 0] = (uint8_t)(lane + 1);
-                wave_lds_sync();
-                const int src = wave_scan_max((int)own[lane]) - 1;
-                const int p = base + lane;
-                const bool valid = p < total;
-                const int sl = valid ? src : lane;
-                const float ox = __shfl(o.x, sl), oy = __shfl(o.y, sl), oz = __shfl(o.z, sl);
-                const float dx = __shfl(d.x, sl), dy = __shfl(d.y, sl), dz = __shfl(d.z, sl);
-                const int eao = __shfl(ea, sl), dao = __shfl(da, sl), dbo = __shfl(db, sl);
-                if (valid) {
-                    const int k = p < eao ? p + dao : p + dbo;
-                    const float4 c4 = kp.grid_c4[k];
-                    const int idx = kp.grid_idx[k];
-                    const float t = sphere_t(c4.w, v3(ox, oy, oz) - v3(c4.x, c4.y, c4.z), v3(dx, dy, dz));
-                    if (isfinite_(t) && gt_1em6(fabs_(t)))
-                        __hip_atomic_fetch_min(slots + src,
-                                               (unsigned long long)__float_as_uint(t) << 32 | (uint32_t)idx,
-                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                }
-            }
-            wave_lds_sync();
-            if (cnt > 0) {
-                const unsigned long long key = slots[lane];
-                if (key != ~0ull) {
-                    const float t = __uint_as_float((uint32_t)(key >> 32));
-                    const int idx = (int)(uint32_t)key;
-                    if (t < best || (t == best && bidx >= 0 && idx < bidx)) bidx = idx;
-                    best = t < best ? t : best;
-                }
-            }
-        }
-        if (act) {
-            budget -= 2;
-            const float bound = (best * 1.0001f + 1e-5f + kp.bvh_tmargin + kp.grid_m) * 1.00001f + 1e-5f;
-            if (fminf(fminf(tmx.x, tmx.y), tmx.z) > bound || !bval || fminf(fminf(tmb.x, tmb.y), tmb.z) > bound ||
-                !cval) {
-                cell = -1;
-                act = false;
-            } else {
-                cell = cc;
-                tmx = tmc;
-                s0 = c0;
-                s1 = c1;
-                cb = cd;
-                tmb = tmd;
-                bval = dval;
-                a0 = d0;
-                a1 = d1;
-                act = budget > 0;
-            }
-        }
-    }
-}
-
 // Nearest geometry hit for both geometry kinds. prim: 0..4 plane, 5 the
 // r=0.5 sphere, 6+i extra sphere i (original index), -1 miss.
 template <bool COUNT, int GEOM, bool NEAREST>
@@ -953,9 +605,8 @@ __device__ __forceinline__ float trace_geometry(const KParams& kp, vec3 o, vec3 
     // (*hit: the box's hit point o + d*t where NEAREST, see resolve's kBoxHit)
     if (GEOM == IPT_GEOM_SPHERE_IN_BOX) {
         if (NEAREST)
-            return (IPT_BOXDIV && kp.box_inrange) ? trace_box_hit<true>(o, d, prim, hit)
-                                                  : trace_box_hit<false>(o, d, prim, hit);
-        return (IPT_BOXDIV && kp.box_inrange) ? trace_box<true>(o, d, prim) : trace_box<false>(o, d, prim);
+            return kp.box_inrange ? trace_box_hit<true>(o, d, prim, hit) : trace_box_hit<false>(o, d, prim, hit);
+        return kp.box_inrange ? trace_box<true>(o, d, prim) : trace_box<false>(o, d, prim);
     }
     if (GEOM == IPT_GEOM_FLOOR) {  // GeometryFloor.cpp:11-13
         const float t = box_plane_t(o.z, d.z, -1.0f, o, d);
@@ -1005,13 +656,13 @@ __device__ __forceinline__ float trace_geometry(const KParams& kp, vec3 o, vec3 
     int p = -1;
     float best = inf_();  // FractalSpheres: no walls
     if (GEOM == IPT_GEOM_SPHERES_IN_BOX)
-        best = (IPT_BOXDIV && kp.box_inrange) ? trace_box_planes_only<true>(o, d, &p) : trace_box_planes_only<false>(o, d, &p);
+        best = kp.box_inrange ? trace_box_planes_only<true>(o, d, &p) : trace_box_planes_only<false>(o, d, &p);
     int bidx = -1;
     if (kp.n_grid > 0) {
         int cell;
         vec3 tmx;
         sphere_grid_init(kp, o, d, cell, tmx);
-        sphere_grid_walk<COUNT>(kp, o, d, cell, tmx, best, bidx, 0x7fffffff, c_nodes, c_tests IPT_DIAG_NULL_ARGS);
+        sphere_grid_walk<COUNT>(kp, o, d, cell, tmx, best, bidx, 0x7fffffff, c_nodes, c_tests);
     } else if (kp.n_nodes > 0) {
         int i = 0;
         sphere_bvh_walk<COUNT>(kp, o, d, i, best, bidx, 0x7fffffff, c_nodes, c_tests);
@@ -1057,14 +708,11 @@ __host__ __device__ constexpr bool resumable_geom(int geom);
 // progressive calls 0.964 -> 0.985 of one call); C2 keeps 256 (its frame
 // columns' ds_read2st64 stride, -1.2 % at 64).
 __host__ __device__ constexpr int block_of(int lmode, int geom) {
-    return (lmode == 9 || lmode == 10) ? kLatticeBlock
-                                       : (resumable_geom(geom) ? (IPT_GRID_LDS ? IPT_GRID_LDS_BLOCK : IPT_RES_BLOCK) : kBlock);
+    return (lmode == 9 || lmode == 10) ? kLatticeBlock : (resumable_geom(geom) ? IPT_RES_BLOCK : kBlock);
 }
-// the wave-spread grid walk's per-lane LDS (IPT_GRID_WAVE): an 8-byte slot
+// the wave-spread grid walk's per-lane LDS: an 8-byte slot
 __host__ __device__ constexpr int walk_lds_words(int lmode, int geom) {
-    // (the two-cell walk keeps its 64-byte owner table per wave)
-    return (IPT_GRID_WAVE && resumable_geom(geom)) ? 2 * block_of(lmode, geom) + (IPT_GRID_WAVE == 2 ? block_of(lmode, geom) / 4 : 0)
-                                                   : 0;
+    return resumable_geom(geom) ? 2 * block_of(lmode, geom) : 0;
 }
 __host__ __device__ constexpr int frame_stride(int lmode, int geom) {
     return ((lmode == 1 || lmode == 5 || lmode == 6) && walk_lds_words(lmode, geom) == 0 && block_of(lmode, geom) >= 256)
@@ -1105,12 +753,12 @@ enum { kLightsOne = 1, kLightsLds = 2, kLightsGlobal = 3, kLightsAny = 4, kLight
 // 1024-thread workgroup per CU (block_of), chosen when the LDS fits (+5 % C5)
 __host__ __device__ constexpr bool grid_lights(int lm) { return lm >= kLightsGridA10 && lm <= kLightsGridA01L; }
 __host__ __device__ constexpr bool lattice_a10(int lm) { return lm == kLightsGridA10 || lm == kLightsGridA10L; }
-// the instances whose box trace takes the nearest-candidate planes (ipt_knobs.h
-// IPT_BOX_NEAREST): the box with one light or a light list. The lattice
+// the instances whose box trace takes the nearest-candidate planes
+// (trace_box_planes_nearest): the box with one light or a light list. The lattice
 // instances, at their SGPR limit, lose 0.2 % with it and the sphere-list
 // instances' walls gain nothing measurable: both keep the full form.
 __host__ __device__ constexpr bool box_nearest(int lm, int geom) {
-    return IPT_BOX_NEAREST && geom == IPT_GEOM_SPHERE_IN_BOX && !grid_lights(lm);
+    return geom == IPT_GEOM_SPHERE_IN_BOX && !grid_lights(lm);
 }
 __host__ __device__ constexpr bool lax_in_lds(int lm) { return lm == kLightsGridA10L || lm == kLightsGridA01L; }
 __host__ __device__ constexpr bool global_lights(int lm) { return lm == kLightsGlobal || grid_lights(lm); }
@@ -1151,14 +799,15 @@ struct LightSet {
 
 // GEOM (IPT_GEOM_*) is a template parameter so that the box instance carries
 // neither the sphere-list code nor its pointers (SGPR pressure).
-// Sphere-list instances carry the resumable walk's state (IPT_RESUME): they
+// Sphere-list instances carry the resumable walk's state (their walks are
+// bounded per step and resumed in later steps): they
 // are given 3 waves per SIMD of registers (their LDS allows 3 workgroups).
 __host__ __device__ constexpr bool resumable_geom(int geom) {
-    return IPT_RESUME && (geom == IPT_GEOM_SPHERES_IN_BOX || geom == IPT_GEOM_SPHERES);
+    return geom == IPT_GEOM_SPHERES_IN_BOX || geom == IPT_GEOM_SPHERES;
 }
 // many-light instances without a sphere list resume their light-BVH walk the same way
 __host__ __device__ constexpr bool resumable_lights(int lmode, int geom) {
-    return IPT_RESUME_LIGHTS && lmode == 3 /* kLightsGlobal */ && !resumable_geom(geom);
+    return lmode == 3 /* kLightsGlobal */ && !resumable_geom(geom);
 }
 __host__ __device__ constexpr int waves_per_simd(int geom, int lmode) {
     return resumable_geom(geom) ? IPT_RES_WAVES : (resumable_lights(lmode, geom) ? IPT_RESL_WAVES : IPT_WAVES_PER_SIMD);
@@ -1243,17 +892,13 @@ template <int MAXSUSP, bool COUNT, int LMODE, int GEOM>
 __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE)) void path_kernel(const KParams kp) {
     constexpr int kBlock = block_of(LMODE, GEOM);  // this instance's workgroup size
     extern __shared__ float lds[];
-    // IPT_GRID_WAVE (resumable sphere-list instances): a 64-bit test slot and a
-    // segment-start byte per lane in front of the stack
+    // resumable sphere-list instances: the wave walk's 64-bit test slot per
+    // lane in front of the stack
     unsigned long long* wslots = reinterpret_cast<unsigned long long*>(lds);
-    uint8_t* wown = reinterpret_cast<uint8_t*>(lds + 2 * kBlock);
     float* stk = lds + walk_lds_words(LMODE, GEOM);           // [MAXSUSP][F][kBlock]
     constexpr int kFrameStride = frame_stride(LMODE, GEOM);
     float* lfr = stk + MAXSUSP * kStackFields * kBlock;       // [12][kFrameStride] lane + wall frames
-    // IPT_GRID_LDS: the packed grid ranges after the frames
-    constexpr bool kGridLds = IPT_GRID_LDS && resumable_geom(GEOM);
-    int* grid_lds = reinterpret_cast<int*>(lfr + 12 * kFrameStride);
-    LightDev* lights_lds = reinterpret_cast<LightDev*>(lfr + 12 * kFrameStride + (kGridLds ? kp.grid_packed_words : 0));
+    LightDev* lights_lds = reinterpret_cast<LightDev*>(lfr + 12 * kFrameStride);
     float* weights_lds = reinterpret_cast<float*>(lights_lds) + kLdsLights * kLightWords;
     float* cdf_lds = weights_lds + (kLdsLights + 1);
     // kLightsGlobal: [weights | cdf | light BVH nodes] after the frames
@@ -1268,10 +913,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     int* cdf_lo_lds = reinterpret_cast<int*>(cdf_gl + kp.n_lights + 1);
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
-    const bool sharded = !(kp.n_shards <= 1 || kp.tile_rows <= 0);
     if (tid < 60) lfr[(tid % 12) * kFrameStride + kBlock + tid / 12] = reinterpret_cast<const float*>(kp.wall_frames)[tid];
-    if (kGridLds)
-        for (int i = tid; i < kp.grid_packed_words; i += kBlock) grid_lds[i] = kp.grid_packed[i];
     if (LMODE == kLightsLds) {
         const float* src = reinterpret_cast<const float*>(kp.lights);
         float* dst = reinterpret_cast<float*>(lights_lds);
@@ -1282,7 +924,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         }
     }
     if (global_lights(LMODE)) {
-        const bool int_cdf = IPT_PICK_INT_CDF && IPT_CDF_POW2 && kp.cdf_p2;
+        const bool int_cdf = kp.cdf_p2;
         for (int i = tid; i <= kp.n_lights; i += kBlock) {
             if (!kGridL) gl_lds[i] = kp.weights[i];
             cdf_gl[i] = int_cdf ? __uint_as_float(cdf_threshold24(kp.cdf[i])) : kp.cdf[i];
@@ -1309,8 +951,9 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     LS.cg = kp.cdf;
     if (one_light(LMODE)) {
         LS.one = kp.lights[0];
-        // held in VGPRs (+3.5 % C2; area and spow stay uniform)
-        if (IPT_LIGHT_HOLD && (IPT_RES_HOLD || !resumable_geom(GEOM))) {
+        // held in VGPRs by the non-resumable instances (+3.5 % C2; area and spow
+        // stay uniform; the sphere-list instances need the registers at 4 waves)
+        if (!resumable_geom(GEOM)) {
             vgpr_hold(LS.one.P); vgpr_hold(LS.one.x); vgpr_hold(LS.one.y);
             vgpr_hold(LS.one.n); vgpr_hold(LS.one.inv.c[0]); vgpr_hold(LS.one.inv.c[1]); vgpr_hold(LS.one.inv.c[2]);
         }
@@ -1322,36 +965,25 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     // this instance's light functions (axis-aligned single light: the reduced
     // forms of ipt_path.h, exact where observed)
     auto ltrace = [&](const LightDev& L, vec3 o, vec3 d, vec3* hp, vec3* hn) -> bool {
-        if constexpr (LMODE == kLightsOneA10) return light_trace_ax<1, 0, IPT_LIGHT_INR>(L, o, d, hp, hn);
-        else if constexpr (LMODE == kLightsOneA01) return light_trace_ax<0, 1, IPT_LIGHT_INR>(L, o, d, hp, hn);
-        else if constexpr (grid_lights(LMODE) && lattice_a10(LMODE)) return light_trace_ax<1, 0, IPT_LIGHT_INR>(L, o, d, hp, hn);
-        else if constexpr (grid_lights(LMODE)) return light_trace_ax<0, 1, IPT_LIGHT_INR>(L, o, d, hp, hn);
+        if constexpr (LMODE == kLightsOneA10) return light_trace_ax<1, 0, true>(L, o, d, hp, hn);
+        else if constexpr (LMODE == kLightsOneA01) return light_trace_ax<0, 1, true>(L, o, d, hp, hn);
+        else if constexpr (grid_lights(LMODE) && lattice_a10(LMODE)) return light_trace_ax<1, 0, true>(L, o, d, hp, hn);
+        else if constexpr (grid_lights(LMODE)) return light_trace_ax<0, 1, true>(L, o, d, hp, hn);
         else return light_trace<LMODE == kLightsAny>(L, o, d, hp, hn);
     };
     auto lpdf = [&](const LightDev& L, vec3 o, bool h, vec3 hp, vec3 hn) -> float {
-        if constexpr (LMODE == kLightsOneA10 || LMODE == kLightsOneA01) return light_pdf_ax<2, IPT_LIGHT_INR>(L, o, h, hp, hn);
-        else if constexpr (grid_lights(LMODE)) return light_pdf_ax<2, IPT_LIGHT_INR>(L, o, h, hp, hn);
+        if constexpr (LMODE == kLightsOneA10 || LMODE == kLightsOneA01) return light_pdf_ax<2, true>(L, o, h, hp, hn);
+        else if constexpr (grid_lights(LMODE)) return light_pdf_ax<2, true>(L, o, h, hp, hn);
         else return light_pdf(L, o, h, hp, hn);
     };
     auto lsample = [&](const LightDev& L, vec3 o, float a, float b) -> vec3 {
-        if constexpr (LMODE == kLightsOneA10) return light_sample_dir_ax<1, 0, IPT_LIGHT_INR>(L, o, a, b);
-        else if constexpr (LMODE == kLightsOneA01) return light_sample_dir_ax<0, 1, IPT_LIGHT_INR>(L, o, a, b);
-        else if constexpr (grid_lights(LMODE) && lattice_a10(LMODE)) return light_sample_dir_ax<1, 0, IPT_LIGHT_INR>(L, o, a, b);
-        else if constexpr (grid_lights(LMODE)) return light_sample_dir_ax<0, 1, IPT_LIGHT_INR>(L, o, a, b);
+        if constexpr (LMODE == kLightsOneA10) return light_sample_dir_ax<1, 0, true>(L, o, a, b);
+        else if constexpr (LMODE == kLightsOneA01) return light_sample_dir_ax<0, 1, true>(L, o, a, b);
+        else if constexpr (grid_lights(LMODE) && lattice_a10(LMODE)) return light_sample_dir_ax<1, 0, true>(L, o, a, b);
+        else if constexpr (grid_lights(LMODE)) return light_sample_dir_ax<0, 1, true>(L, o, a, b);
         else return light_sample_dir<LMODE == kLightsAny>(L, o, a, b);
     };
 
-    // the sphere grid walk's parameters (kRes instances), held in VGPRs (+5 % C3)
-    KParams kg = kp;
-    if (IPT_RES_HOLD && resumable_geom(GEOM)) {
-        for (int a = 0; a < 3; ++a) {
-            vgpr_hold(kg.grid_g0[a]);
-            vgpr_hold(kg.grid_h[a]);
-            vgpr_hold(kg.grid_n[a]);
-        }
-        vgpr_hold(kg.grid_m);
-        vgpr_hold(kg.bvh_tmargin);
-    }
     const int lane = tid & 63;
     const uint64_t lanemask_lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     const int nl = one_light(LMODE) ? 1 : kp.n_lights;  // a compile-time 1 for one light
@@ -1374,7 +1006,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     // the iteration's pick and draws (prologue) and CosineDdf factors (gathers)
     int pick = -1;
     float u1 = 0.0f, u2 = 0.0f, tr = 0.0f, cs_c = 0.0f, cs_s = 0.0f;
-    // IPT_FRAME_PF == 3: the frame-table entry (sin, cos) of the node the lane
+    // kFramePf: the frame-table entry (sin, cos) of the node the lane
     // builds a frame for in the next step, gathered at the end of this step,
     // with its `to` (pfok: `to` inside the table's range)
     float pfs = 0.0f, pfc = 0.0f;
@@ -1396,13 +1028,13 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     constexpr bool kBoxHit = !kRes && !kResL && GEOM == IPT_GEOM_SPHERE_IN_BOX && box_nearest(LMODE, GEOM);
     // the frame-entry prefetch pays where every lane iterates every step; in the
     // resumable instances (lanes parked in walks) it measured -5 % on C5
-    constexpr int kFramePf = (kRes || kResL) ? 0 : IPT_FRAME_PF;
+    constexpr bool kFramePf = !(kRes || kResL);
     // certain light-sample skips taken within the step (the prologue below):
     // the axis-aligned single-light instances, whose ranges are proven
-    constexpr bool kSkipAhead = IPT_SKIP_AHEAD && (one_light(LMODE) || grid_lights(LMODE)) && !kResL;
+    constexpr bool kSkipAhead = (one_light(LMODE) || grid_lights(LMODE)) && !kResL;
     // ... and the next iteration's certain skip taken at the end of the step,
     // before its pop (the instances that pop at the end of the step)
-    constexpr bool kPreSkip = kSkipAhead && IPT_PRE_SKIP && kFramePf == 3;
+    constexpr bool kPreSkip = kSkipAhead && kFramePf;
     bool tracing = false;  // a resumable walk (sphere list or light BVH) is in progress
     float xlmix = 0.0f;    // light walk: the running UnionDdf light sum
     vec3 xro = v3(0, 0, 0), xrd = v3(0, 0, 0), xli_pos = v3(0, 0, 0);
@@ -1469,14 +1101,14 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         IPT_STAMP_AT(1);  // refill
         if (active) { IPT_PHASE(0); }
         // ------------------------------- phase 1: finalize + pop (main.cpp:177-183)
-        // (IPT_FRAME_PF == 3: at the end of the previous step instead -- the
+        // (kFramePf: at the end of the previous step instead -- the
         // same operations on the same state, nothing changes it in between but
         // the refill of lanes without a path)
         auto pop_node = [&]() {
         // (a lane with a path is active, and a path is fresh only between the
         // refill and the new-path phase of one step: at the end-of-step pop
         // neither flag has to be read)
-        if (has_path && (kFramePf == 3 || !fresh) && !((kRes || kResL) && tracing) && ti >= (kp.n_rays >> tdepth)) {
+        if (has_path && (kFramePf || !fresh) && !((kRes || kResL) && tracing) && ti >= (kp.n_rays >> tdepth)) {
             // the node is done: unwind every suspended level whose node has run
             // all its iterations too (finm, set at push) in one pass -- only
             // their res/multiplier are read -- then resume the first level
@@ -1564,7 +1196,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             }
         }
         };
-        if (kFramePf != 3) pop_node();
+        if (!kFramePf) pop_node();
 
         IPT_STAMP_AT(2);  // finalize + pop
         // the current node's frame normal (frame build below)
@@ -1608,7 +1240,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         // (pre_w is read only behind pre_ok: left uninitialised, no per-step moves)
         uint32_t pre_w;
         bool pre_ok = false;
-        // IPT_LPF (lattice instances): the picked light's sample fields are
+        // lattice instances: the picked light's sample fields are
         // gathered with the CosineDdf gathers (whole wave, index 0 for lanes
         // without a light pick) instead of read in the direction phase
         vec3 lpP = v3(0, 0, 0);
@@ -1627,49 +1259,25 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     cs_s = sp;
                 }
             } else {
-                if constexpr (grid_lights(LMODE) && IPT_LPF && IPT_LIGHT_AX_REC) {
+                if constexpr (grid_lights(LMODE)) {
                     // the compact record's first 16 bytes: P.xy, x[XA], y[YA]
                     // (P.z, n.z: the lattice plane; lattice lights are diamonds)
                     const int pk = (ran && pick >= 0 && pick < nl) ? pick : 0;
-                    if (IPT_LPF_CALC && kp.lpf_calc) {
-                        // the same floats from the lattice's formula (no LDS
-                        // read on the pick -> light sample chain)
-                        lpP = v3(kp.lc_x0 + (float)(pk & ((1 << kp.lc_shift) - 1)) * kp.lc_dx,
-                                 kp.lc_y0 + (float)(pk >> kp.lc_shift) * kp.lc_dy, kp.lg_pn);
-                        lpx = kp.lc_ax;
-                        lpy = kp.lc_ay;
-                    } else {
-                        const float4 a = kLaxLds ? lax_lds[3 * pk] : kp.lax[3 * pk];
-                        lpP = v3(a.x, a.y, kp.lg_pn);
-                        lpx = a.z;
-                        lpy = a.w;
-                    }
+                    const float4 a = kLaxLds ? lax_lds[3 * pk] : kp.lax[3 * pk];
+                    lpP = v3(a.x, a.y, kp.lg_pn);
+                    lpx = a.z;
+                    lpy = a.w;
                     lpn = kp.lg_nn;
                     lptype = 0;
-                } else if constexpr (grid_lights(LMODE) && IPT_LPF) {
-                    constexpr int XA = lattice_a10(LMODE) ? 1 : 0, YA = 1 - XA;
-                    const LightDev& Ls = kp.lights[(ran && pick >= 0 && pick < nl) ? pick : 0];
-                    lpP = Ls.P;
-                    lpx = comp<XA>(Ls.x);
-                    lpy = comp<YA>(Ls.y);
-                    lpn = comp<2>(Ls.n);
-                    lptype = Ls.type;
                 }
                 // (cos phi, sin phi) computed (the table kernel's own code): one
                 // table line per cosine sample instead of two (computing r as
                 // well, or non-temporal gathers, measured slower: DESIGN.md 4.3)
                 tr = kp.cos_a[gcos ? gi_a : 0u];
-                if constexpr (IPT_COSB_TAB) {
-                    // (cos phi, sin phi) gathered from the exact table as well
-                    const float2 cb = kp.cos_b[gcos ? gi_b : 0u];
-                    cs_c = cb.x;
-                    cs_s = cb.y;
-                } else {
-                    float sp, cp;
-                    sincosf_small_(two_pi_times_u24(gi_b), &sp, &cp);
-                    cs_c = cp;
-                    cs_s = sp;
-                }
+                float sp, cp;
+                sincosf_small_(two_pi_times_u24(gi_b), &sp, &cp);
+                cs_c = cp;
+                cs_s = sp;
             }
         };
         auto prologue = [&]() {
@@ -1693,19 +1301,11 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             auto pick_w = [&](uint32_t wd) {
                 return (unsigned long long)wd < kp.pk_u0 ? 0 : ((unsigned long long)wd < kp.pk_u1 ? 1 : 2);
             };
-            constexpr bool kPickInt = IPT_PICK_INT && one_light(LMODE);
+            constexpr bool kPickInt = one_light(LMODE);
             // UnionDdf::sample's component: the first c with r < cdf[c] (ddf.cpp:142-153)
             auto pick_of = [&](float r) {
                 int c = 0;
-                if (one_light(LMODE)) {
-                    c = r < LS.c0 ? 0 : (r < LS.c1 ? 1 : 2);
-                } else if (global_lights(LMODE) && IPT_CDF_POW2 && kp.cdf_p2) {
-                    // (host-checked near-uniform cdf: ce - 1, ce or ce + 1)
-                    const int ce = min((int)(r * kp.cdf_p2s), nl);
-                    const float fa = LS.cdf(max(ce - 1, 0)), fb = LS.cdf(ce);
-                    c = (ce >= 1 && r < fa) ? ce - 1 : (r < fb ? ce : ce + 1);
-                    if (c >= nl) c = r < kp.cdf_end ? nl : nl + 1;
-                } else if (global_lights(LMODE) && kp.cdf_lo) {
+                if (global_lights(LMODE) && kp.cdf_lo) {
                     // the scan from the first index whose cdf exceeds r's bucket
                     // start floor(256 r)/256 (host table): every earlier entry is
                     // <= that start <= r, so the scan would pass it; a bucket holds
@@ -1755,7 +1355,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 if (c >= nl) c = g < kp.cdf_end_t ? nl : nl + 1;
                 return c;
             };
-            constexpr bool kPickIntCdf = IPT_PICK_INT_CDF && IPT_CDF_POW2 && global_lights(LMODE);
+            constexpr bool kPickIntCdf = global_lights(LMODE);
             auto pick_word = [&](uint32_t wd) {
                 if constexpr (kPickInt) return pick_w(wd);
                 if constexpr (kPickIntCdf)
@@ -1861,18 +1461,17 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             // the sphere-in-box node's normal comes from a point on the r = 0.5
             // sphere: every root and quotient of the frame is in the range-free
             // sequences' range (make_frame<true>)
-            if (IPT_FRAME_TAB && GEOM == IPT_GEOM_SPHERE_IN_BOX) {
+            if (GEOM == IPT_GEOM_SPHERE_IN_BOX) {
                 // (sphere-list scenes: measured slower with the table's
                 // gathers in their latency-bound walks)
                 vec3 to;
                 float fs = 0.0f, fc = 0.0f;
-                if (kFramePf == 3) {
+                if (kFramePf) {
                     // `to` and its frame-table entry, prepared at the end of
                     // the previous step (pfok: `to` inside the table's range)
                     // (the rare branch writes the prefetch's own variables --
                     // nothing reads them again before the next prefetch -- so
                     // the common path copies nothing)
-                    if constexpr (!IPT_FRAME_FB_PF) {
                     if (__builtin_expect(__any(!pfok), 0))
                         if (!pfok) {
                             pto = kFrameInrange ? normalize_inrange_(nrm) : normalize(nrm);
@@ -1880,7 +1479,6 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                             keep_alive(pfs);  // its wait stays in this rare branch
                             keep_alive(pfc);
                         }
-                    }
                     to = pto;
                     fs = pfs;
                     fc = pfc;
@@ -1906,10 +1504,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 // (its own range checks; a normalized `to`), exact fallback
                 const vec3 to = normalize(nrm);
                 float fs, fc;
-                if (IPT_FRAME_TAB && IPT_FRAME_TAB_LISTS && GEOM == IPT_GEOM_SPHERES_IN_BOX)
-                    frame_sc_lookup(kp.frame_sc, to, fs, fc);
-                else
-                    frame_angle_sc(to, &fs, &fc);
+                frame_angle_sc(to, &fs, &fc);
                 bool ok;
                 f = make_frame_sc_fast(to, fs, fc, ok);
                 if (__builtin_expect(__any(!ok), 0))
@@ -1944,51 +1539,28 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         // barrier B so that its camera ray is not live across the worker pass
         if (has_path && fresh) {
             IPT_PHASE(2);
-            if (IPT_RAYGEN) {
-                // raygen_kernel ran render_sample's per-sample work for this
-                // unit (jitter, drift code and flags, camera ray, Philox block 0)
-                // both records load together and are consumed here: no load of
-                // this (divergent) phase is left in flight for later waits
-                uint4 r0 = kp.rg[2 * unit], r1 = kp.rg[2 * unit + 1];
-                keep_alive(r0);
-                keep_alive(r1);
-                if (r0.w == 0u) {
-                    has_path = false;  // not ours / out of range: already stored
-                } else {
-                    tpos = kp.cam_pos;
-                    rd = v3(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
-                    w.a2 = r1.x;
-                    w.a3 = r1.y;
-                    rpass = r1.z;
-                    rpix = r1.w;
-                    blk = 0;
-                    need_b = true;  // block 1 is produced by the window refill of the next iteration
-                    k = 2;
-                    rdepth = 0;
-                    have_ray = true;
-                    if (COUNT) ++c_paths;
-                }
-            } else {
-            const RayGen g = new_path_setup(kp, unit, sharded, kp.cand_rows);
-            w.a0 = g.a0;
-            w.a1 = g.a1;
-            w.a2 = g.a2;
-            w.a3 = g.a3;
-            rpass = g.rpass;
-            rpix = g.rpix;
-            blk = 0;
-            need_b = true;
-            k = 2;
-            if (COUNT && g.drift) ++c_drift;
-            if (!g.valid) {
-                has_path = false;
+            // raygen_kernel ran render_sample's per-sample work for this
+            // unit (jitter, drift code and flags, camera ray, Philox block 0)
+            // both records load together and are consumed here: no load of
+            // this (divergent) phase is left in flight for later waits
+            uint4 r0 = kp.rg[2 * unit], r1 = kp.rg[2 * unit + 1];
+            keep_alive(r0);
+            keep_alive(r1);
+            if (r0.w == 0u) {
+                has_path = false;  // not ours / out of range: already stored
             } else {
                 tpos = kp.cam_pos;
-                rd = g.rd;
+                rd = v3(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
+                w.a2 = r1.x;
+                w.a3 = r1.y;
+                rpass = r1.z;
+                rpix = r1.w;
+                blk = 0;
+                need_b = true;  // block 1 is produced by the window refill of the next iteration
+                k = 2;
                 rdepth = 0;
                 have_ray = true;
                 if (COUNT) ++c_paths;
-            }
             }
         }
         // (a fresh lane has a path, so the phase above ran for it: cleared for
@@ -2015,8 +1587,8 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 // into the pick's select: two selects per component, not three
                 bool lok;
                 const vec3 ldir = LMODE == kLightsOneA10
-                                      ? light_sample_dir_ax_ok<1, 0, IPT_LIGHT_INR>(LS.one, tpos, u1, u2, &lok)
-                                      : light_sample_dir_ax_ok<0, 1, IPT_LIGHT_INR>(LS.one, tpos, u1, u2, &lok);
+                                      ? light_sample_dir_ax_ok<1, 0, true>(LS.one, tpos, u1, u2, &lok)
+                                      : light_sample_dir_ax_ok<0, 1, true>(LS.one, tpos, u1, u2, &lok);
                 const vec3 other = pick == nl ? cdir : zero;
                 dir_bf = pick < nl && lok ? ldir : other;
             } else {
@@ -2031,10 +1603,10 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 if (COUNT && pick < nl) ++c_lsamp;
             } else if (pick < nl) {
                 IPT_PHASE(7);
-                if constexpr (grid_lights(LMODE) && IPT_LPF) {
+                if constexpr (grid_lights(LMODE)) {
                     // the gathered fields are all light_sample_dir_ax reads
                     constexpr int XA = lattice_a10(LMODE) ? 1 : 0, YA = 1 - XA;
-                    dir = light_sample_dir_axf<XA, YA, IPT_LIGHT_INR>(lpP, lpx, lpy, lpn, lptype, tpos, u1, u2);
+                    dir = light_sample_dir_axf<XA, YA, true>(lpP, lpx, lpy, lpn, lptype, tpos, u1, u2);
                 } else
                 dir = lsample(LS.light(pick), tpos, u1, u2);
                 if (COUNT) ++c_lsamp;
@@ -2250,7 +1822,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             auto light_step_with = [&](const LightDev& L, float wl) {
                 vec3 hp, hn;
                 bool h;
-                if constexpr (grid_lights(LMODE) && IPT_LIGHT_INR) {
+                if constexpr (grid_lights(LMODE)) {
                     constexpr int XA = lattice_a10(LMODE) ? 1 : 0, YA = 1 - XA;
                     h = light_trace_ax_q<XA, YA>(L, lg_ndir, lg_t, lg_q, &hp, &hn);
                 } else {
@@ -2273,19 +1845,14 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 }
             };
             auto light_step = [&](int l) {
-                if constexpr (grid_lights(LMODE) && IPT_LIGHT_AX_REC) {
+                if constexpr (grid_lights(LMODE)) {
                     // the lattice light from its 48-byte record: exactly the
                     // fields light_trace_ax / light_pdf_ax read (ipt_path.h LightAx)
                     constexpr int XA = lattice_a10(LMODE) ? 1 : 0, YA = 1 - XA;
                     float4 a, b, c;
-                    if (IPT_LTR_CALC && kp.ltr_calc) {
-                        // the record's floats from the lattice's formulas; only
-                        // the weight is per light
-                        a = make_float4(kp.lc_x0 + (float)(l & ((1 << kp.lc_shift) - 1)) * kp.lc_dx,
-                                        kp.lc_y0 + (float)(l >> kp.lc_shift) * kp.lc_dy, kp.lc_ax, kp.lc_ay);
-                        b = make_float4(kp.lc_ix, kp.lc_iy, kp.lc_area, kp.lc_spow);
-                        c = make_float4(kLaxLds ? lax_lds[3 * l + 2].x : kp.lax[3 * l + 2].x, 0.0f, 0.0f, 0.0f);
-                    } else if constexpr (kLaxLds) {
+                    // (a plain `if` on the constant: the lambda then captures lax_lds in
+                    // every lattice instance, which keeps their register assignment)
+                    if (kLaxLds) {
                         a = lax_lds[3 * l]; b = lax_lds[3 * l + 1]; c = lax_lds[3 * l + 2];
                     } else {
                         const float4* r = kp.lax + 3 * l;
@@ -2327,7 +1894,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 // shared with the light tests below)
                 const float n_dir = kp.lg_nn * comp<2>(rd);
                 const float num = kp.lg_nn * (kp.lg_pn - comp<2>(ro));
-                const float t = IPT_LIGHT_INR ? div_inrange_(num, n_dir) : div_(num, n_dir);
+                const float t = div_inrange_(num, n_dir);
                 lg_ndir = n_dir;
                 lg_t = t;
                 lg_q = ro + rd * t;
@@ -2341,8 +1908,6 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     const int* cells = reinterpret_cast<const int*>(lnodes_lds);
                     auto cell = [&](int i, int j) {
                         const bool in = i >= 0 && i < kp.lg_nu && j >= 0 && j < kp.lg_nv;
-                        if (IPT_LTR_CALC && kp.lg_ident)
-                            return in ? (kp.lg_ident == 1 ? i + kp.lg_nu * j : j + kp.lg_nv * i) : -1;
                         return in ? cells[i + kp.lg_nu * j] : -1;
                     };
                     cand[0] = cell(i0, j0);
@@ -2422,10 +1987,10 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 xi = 0;
                 xbest = inf_();
                 if (GEOM == IPT_GEOM_SPHERES_IN_BOX)
-                    xbest = (IPT_BOXDIV && kp.box_inrange) ? trace_box_planes_only<true>(ro, rd, &xp)
-                                                           : trace_box_planes_only<false>(ro, rd, &xp);
+                    xbest = kp.box_inrange ? trace_box_planes_only<true>(ro, rd, &xp)
+                                           : trace_box_planes_only<false>(ro, rd, &xp);
                 xbidx = -2 - xp;
-                if (kp.n_grid > 0) sphere_grid_init(kg, ro, rd, xi, xtm);
+                if (kp.n_grid > 0) sphere_grid_init(kp, ro, rd, xi, xtm);
                 tracing = true;
             } else {
                 int prim = -1;
@@ -2442,19 +2007,14 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         IPT_STAMP_AT(11);  // resolve + push
         // (kRes) the walking ray's origin: the lane's node or the camera
         const vec3 xo = xis_iter ? tpos : kp.cam_pos;
-        if (kRes && IPT_GRID_WAVE && kp.n_grid > 0) {
+        if (kRes && kp.n_grid > 0) {
             // the whole wave walks (the item tests are spread over its lanes)
-            if (__ballot(tracing)) {
-                if constexpr (IPT_GRID_WAVE == 2)
-                    sphere_grid_walk_wave2<COUNT>(kg, tracing, xo, xrd, xi, xtm, xbest, xbidx, IPT_GRID_BUDGET,
-                                                  wslots + (tid & ~63), wown + (tid & ~63), lane, c_nodes, c_tests);
-                else
-                    sphere_grid_walk_wave<COUNT>(kg, tracing, xo, xrd, xi, xtm, xbest, xbidx, IPT_GRID_BUDGET,
-                                                 wslots + (tid & ~63), lane, grid_lds, c_nodes, c_tests IPT_DIAG_ARGS);
-            }
+            if (__ballot(tracing))
+                sphere_grid_walk_wave<COUNT>(kp, tracing, xo, xrd, xi, xtm, xbest, xbidx, IPT_GRID_BUDGET,
+                                             wslots + (tid & ~63), lane, c_nodes, c_tests IPT_DIAG_ARGS);
             if (tracing && xi < 0) {
                 tracing = false;
-                if (IPT_GRID_WAVE != 2 && xbidx >= 0) xbidx = grid_item_index(kg, xbidx);  // item position -> original index
+                if (xbidx >= 0) xbidx = grid_item_index(kp, xbidx);  // item position -> original index
 #if IPT_RAYLOG
                 if (!COUNT && kp.raylog) {
                     const unsigned long long k = atomicAdd(kp.raylog_n, 1ull);
@@ -2469,21 +2029,11 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 resolve(true, xbest, xbidx >= 0 ? 6 + xbidx : -2 - xbidx, xo, xrd, xis_iter ? tdepth + 1 : 0, xis_iter,
                         xmult, xhas_li, xli_y, xli_pow);
             }
-        } else if (kRes && tracing) {
+        } else if (kRes && tracing) {  // no grid: the sphere BVH
             IPT_PHASE(9);
-            bool done;
-            if (kp.n_grid > 0) {
-                sphere_grid_walk<COUNT, IPT_GRID_PIPE != 0>(kg, xo, xrd, xi, xtm, xbest, xbidx, IPT_GRID_BUDGET, c_nodes,
-                                                          c_tests IPT_DIAG_ARGS);
-                done = xi < 0;
-            } else {
-                sphere_bvh_walk<COUNT>(kp, xo, xrd, xi, xbest, xbidx, IPT_WALK_BUDGET, c_nodes, c_tests);
-                done = xi >= kp.n_nodes;
-            }
-            if (done) {
+            sphere_bvh_walk<COUNT>(kp, xo, xrd, xi, xbest, xbidx, IPT_WALK_BUDGET, c_nodes, c_tests);
+            if (xi >= kp.n_nodes) {
                 tracing = false;
-                if (IPT_GRID_PIPE && kp.n_grid > 0 && xbidx >= 0)
-                    xbidx = grid_item_index(kg, xbidx);  // item position -> original index
                 resolve(true, xbest, xbidx >= 0 ? 6 + xbidx : -2 - xbidx, xo, xrd, xis_iter ? tdepth + 1 : 0, xis_iter,
                         xmult, xhas_li, xli_y, xli_pow);
             }
@@ -2501,7 +2051,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             // same order, same counts.
             // (as selects: no exec-mask branch)
             const bool back = (tpos.z - kp.sa_pz) * kp.sa_nz < 0.0f;
-            const bool lpick = IPT_PICK_INT ? (unsigned long long)pre_w < kp.sa_u : u01(pre_w) < kp.sa_cl;
+            const bool lpick = (unsigned long long)pre_w < kp.sa_u;
             const bool take = iter_lane && pre_ok && back && ti < (kp.n_rays >> tdepth) && lpick;
             ti += take ? 1 : 0;
             k += take ? 3u : 0u;
@@ -2511,10 +2061,10 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 c_skip += take ? 1u : 0u;
             }
         }
-        if constexpr (kFramePf == 3) {
+        if constexpr (kFramePf) {
             pop_node();
             IPT_STAMP_AT(6);  // pop (end of step)
-            if constexpr (IPT_FRAME_TAB && kFrameInrange) {
+            if constexpr (kFrameInrange) {
                 // the frame the lane builds in the next step (a sphere node
                 // pushed in this step, or popped back to with its column
                 // overwritten): `to` and the table gather now, consumed there
@@ -2527,15 +2077,6 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                         pfs = e.x;
                         pfc = e.y;
                         pto = to;
-                    }
-                    if constexpr (IPT_FRAME_FB_PF) {
-                        // the out-of-table angle computed here as well, so that
-                        // the frame phase reads `to`, sin a, cos a unconditionally
-                        if (__builtin_expect(__any(!pfok), 0))
-                            if (!pfok) {
-                                frame_angle_sc(to, &pfs, &pfc);
-                                pto = to;
-                            }
                     }
                 }
             }
@@ -3263,28 +2804,22 @@ struct ipt_ctx {
     int n_grid = 0;
     size_t grid_n_items = 0;
     int* d_grid_start = nullptr;
-    int* d_grid_packed = nullptr;  // IPT_GRID_LDS (KParams::grid_packed)
-    int grid_packed_words = 0, grid_packed_nb = 0;
     BvhSphere* d_grid_items = nullptr;
     float4* d_grid_c4 = nullptr;  // [items] centre/radius, then [items] original indices
-    GridCell* d_grid_cells = nullptr;  // 64-byte cell records (IPT_GRID_INLINE)
     BvhNode* d_light_nodes = nullptr;
     int n_light_nodes = 0;
     int cdf_bsearch = 0;
     int cdf_p2 = 0, cdf_p2e = 0;
-    int lpf_calc = 0, lc_shift = 0;  // KParams::lpf_calc
-    int ltr_calc = 0, lg_ident = 0;  // KParams::ltr_calc, lg_ident
-    float lc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    float cdf_p2s = 0.0f, cdf_end = 0.0f;
+    float cdf_end = 0.0f;
     int* d_cdf_lo = nullptr;  // cdf bucket starts (global light modes), null when a bucket is crowded
     bool any_round_light = false;
     int light_axis = 0;  // axis_aligned_light() of a single AreaLight (kLightsOneA10/A01)
     LightGrid lgrid;     // lgrid.pattern != 0: coplanar light lattice (kLightsGridA10/A01)
     unsigned long long pk_u0 = 0, pk_u1 = 0, sa_u = 0;  // word thresholds (KParams)
     int sa_on = 0;       // the lights' sample points share the plane z = sa_pz, normal (0, 0, sa_nz) (skip-ahead)
-    float sa_pz = 0.0f, sa_nz = 0.0f, sa_cl = 0.0f;
+    float sa_pz = 0.0f, sa_nz = 0.0f;
     int* d_lgrid = nullptr;
-    LightAx* d_lax = nullptr;  // lattice lights' compact records (IPT_LIGHT_AX_REC)
+    LightAx* d_lax = nullptr;  // lattice lights' compact records
     int bpc_override = 0;
     int lnodes_lds = 1;  // stage the light BVH in LDS (IPT_LNODES_LDS=0: global memory)
     int light_grid_on = 1;  // coplanar light lattices by cell lookup (IPT_LIGHT_GRID=0: the light BVH)
@@ -3315,7 +2850,7 @@ struct ipt_ctx {
     float* d_cos_a = nullptr;   // CosineDdf tables (cos_table_kernel): r 64 MiB,
                                 // (cos phi, sin phi) 128 MiB
     float2* d_cos_b = nullptr;
-    float2* d_frame_sc = nullptr;  // frame_table_kernel (IPT_FRAME_TAB), 1 GiB
+    float2* d_frame_sc = nullptr;  // frame_table_kernel, 1 GiB
     float last_path_ms = 0.0f, last_acc_ms = 0.0f;
     int blocks_per_cu = 0;      // of the last path-kernel launch
     bool lattice_lds = true;    // IPT_LATTICE_LDS=0: the lattice instances with global records (tests)
@@ -3364,10 +2899,10 @@ int ensure_cos_tables(ipt_ctx* ctx, hipStream_t st) {
 
 // the geometries whose sphere-node frames read the frame-angle table
 constexpr bool frame_table_user(int geom) {
-    return geom == IPT_GEOM_SPHERE_IN_BOX || (IPT_FRAME_TAB_LISTS && geom == IPT_GEOM_SPHERES_IN_BOX);
+    return geom == IPT_GEOM_SPHERE_IN_BOX;
 }
 int ensure_frame_table(ipt_ctx* ctx, hipStream_t st) {
-    if (!IPT_FRAME_TAB || ctx->d_frame_sc) return IPT_OK;
+    if (ctx->d_frame_sc) return IPT_OK;
     DevBuf<float2> t;
     HIPCHECK(ctx, hipMalloc(&t.p, kFrameTabEntries * sizeof(float2)));
     hipLaunchKernelGGL(frame_table_kernel, dim3((unsigned)((kFrameTabEntries + 255) / 256)), dim3(256), 0, st, t.p);
@@ -3399,7 +2934,7 @@ int ensure_work(ipt_ctx* ctx, WorkSlot& S, size_t elems, size_t npix, int H, int
         S.d_codes = c.release();
         S.work_cap = elems;
     }
-    if (IPT_RAYGEN && rg_elems > S.rg_cap) {
+    if (rg_elems > S.rg_cap) {
         if (S.d_rg) hipFree(S.d_rg);
         S.d_rg = nullptr;
         S.rg_cap = 0;
@@ -3607,7 +3142,6 @@ size_t path_lds_bytes(const KParams& kp) {
     constexpr int kBlock = block_of(LMODE, GEOM);
     const size_t cells = (size_t)kp.lg_nu * kp.lg_nv;
     return ((size_t)MAXSUSP * kStackFields * kBlock + scene_lds_words(LMODE, GEOM) +
-            ((IPT_GRID_LDS && resumable_geom(GEOM)) ? (size_t)kp.grid_packed_words : 0) +
             (LMODE == kLightsGlobal ? global_light_lds_words(kp.n_lights, kp.lnodes_lds ? kp.n_light_nodes : 0) : 0) +
             (grid_lights(LMODE) ? global_light_lds_words(kp.n_lights, 0, true) +
                                       (lax_in_lds(LMODE) ? ((cells + 3) & ~(size_t)3) + 12 * (size_t)kp.n_lights : cells)
@@ -3618,8 +3152,6 @@ size_t path_lds_bytes(const KParams& kp) {
 template <int MAXSUSP, bool COUNT, int LMODE, int GEOM>
 int launch_path4(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     constexpr int kBlock = block_of(LMODE, GEOM);
-    if (IPT_GRID_LDS && resumable_geom(GEOM) && kp.n_grid > 0 && !kp.grid_packed)
-        return fail(ctx, IPT_E_UNSUPPORTED, "IPT_GRID_LDS build: the grid's ranges do not pack into bytes");
     const size_t lds = path_lds_bytes<MAXSUSP, LMODE, GEOM>(kp);
     const void* fn = (const void*)path_kernel<MAXSUSP, COUNT, LMODE, GEOM>;
     HIPCHECK(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -3668,12 +3200,12 @@ int launch_path2(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
         // the records-in-LDS instance wherever its LDS fits one workgroup per CU
         constexpr int G = IPT_GEOM_SPHERE_IN_BOX;
         if (ctx->lgrid.pattern == 1 && kp.geometry_kind == G) {
-            if (IPT_LAX_LDS && ctx->lattice_lds && path_lds_bytes<MAXSUSP, kLightsGridA10L, G>(kp) <= ctx->max_lds)
+            if (ctx->lattice_lds && path_lds_bytes<MAXSUSP, kLightsGridA10L, G>(kp) <= ctx->max_lds)
                 return launch_path4<MAXSUSP, COUNT, kLightsGridA10L, G>(ctx, kp, st);
             return launch_path4<MAXSUSP, COUNT, kLightsGridA10, G>(ctx, kp, st);
         }
         if (ctx->lgrid.pattern == 2 && kp.geometry_kind == G) {
-            if (IPT_LAX_LDS && ctx->lattice_lds && path_lds_bytes<MAXSUSP, kLightsGridA01L, G>(kp) <= ctx->max_lds)
+            if (ctx->lattice_lds && path_lds_bytes<MAXSUSP, kLightsGridA01L, G>(kp) <= ctx->max_lds)
                 return launch_path4<MAXSUSP, COUNT, kLightsGridA01L, G>(ctx, kp, st);
             return launch_path4<MAXSUSP, COUNT, kLightsGridA01, G>(ctx, kp, st);
         }
@@ -3727,7 +3259,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
     // single launch).
     // (a preview unit is its value and code, 5 B, plus ipt_preview_values'
     // outputs; it has no raygen record and its launches read no table)
-    constexpr size_t kRgBytes = IPT_RAYGEN ? 2 * sizeof(uint4) : 0;
+    constexpr size_t kRgBytes = 2 * sizeof(uint4);
     const size_t unit_bytes = sizeof(float) + 1 + (preview ? (host_kinds ? 1 : 0) + (host_hits ? 6 * sizeof(float) : 0) : kRgBytes);
     size_t budget = (size_t)1 << 29;
     {
@@ -3769,7 +3301,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         const size_t elems = (size_t)chunk * per_pass;
         const size_t rg_elems = preview ? 0 : elems, kinds_elems = host_kinds ? elems : 0, hits_elems = host_hits ? elems : 0;
         const bool grow = elems > S.work_cap || (size_t)W * H > S.flags_cap || n_cand > S.cand_cap_rows ||
-                          H > S.cand_cap_h || (IPT_RAYGEN && rg_elems > S.rg_cap) || kinds_elems > S.kinds_cap ||
+                          H > S.cand_cap_h || rg_elems > S.rg_cap || kinds_elems > S.kinds_cap ||
                           hits_elems > S.hits_cap;
         const int plan[5] = {H, p->tile_rows, p->n_shards, p->shard_id, plane_of(p)};
         const bool replan = !std::equal(plan, plan + 5, S.plan);
@@ -3873,13 +3405,9 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         }
         kp.grid_m = ctx->grid.m;
         kp.grid_start = ctx->d_grid_start;
-        kp.grid_packed = ctx->d_grid_packed;
-        kp.grid_packed_words = ctx->grid_packed_words;
-        kp.grid_packed_nb = ctx->grid_packed_nb;
         kp.grid_items = ctx->d_grid_items;
         kp.grid_c4 = ctx->d_grid_c4;
         kp.grid_idx = ctx->d_grid_c4 ? reinterpret_cast<const int*>(ctx->d_grid_c4 + ctx->grid_n_items) : nullptr;
-        kp.grid_cells = ctx->d_grid_cells;
         kp.bvh_prims = ctx->d_bvh_prims;
         kp.n_nodes = ctx->n_nodes;
         kp.light_nodes = ctx->d_light_nodes;
@@ -3890,23 +3418,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         kp.lnodes_lds = (ctx->lnodes_lds && ctx->n_light_nodes > 0 && ctx->n_light_nodes <= kLdsLightNodesMax) ? 1 : 0;
         kp.cdf_bsearch = ctx->cdf_bsearch;
         kp.cdf_p2 = ctx->cdf_p2;
-        kp.cdf_p2s = ctx->cdf_p2s;
-        kp.cdf_end = ctx->cdf_end;
         kp.cdf_p2e = ctx->cdf_p2e;
-        kp.lpf_calc = ctx->lpf_calc;
-        kp.lc_shift = ctx->lc_shift;
-        kp.lc_x0 = ctx->lc[0];
-        kp.lc_y0 = ctx->lc[1];
-        kp.lc_dx = ctx->lc[2];
-        kp.lc_dy = ctx->lc[3];
-        kp.lc_ax = ctx->lc[4];
-        kp.lc_ay = ctx->lc[5];
-        kp.ltr_calc = ctx->ltr_calc;
-        kp.lg_ident = ctx->lg_ident;
-        kp.lc_ix = ctx->lc[6];
-        kp.lc_iy = ctx->lc[7];
-        kp.lc_area = ctx->lc[8];
-        kp.lc_spow = ctx->lc[9];
         kp.cdf_end_t = (uint32_t)(word_threshold(ctx->cdf_end) >> 8);
         kp.cdf_lo = ctx->d_cdf_lo;
         kp.lgrid = ctx->d_lgrid;
@@ -3924,11 +3436,9 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         kp.sa_on = ctx->sa_on;
         kp.sa_pz = ctx->sa_pz;
         kp.sa_nz = ctx->sa_nz;
-        kp.sa_cl = ctx->sa_cl;
         kp.lg_pn = ctx->lgrid.pn;
         kp.lg_nn = ctx->lgrid.nn;
         kp.cos_a = ctx->d_cos_a;
-        kp.cos_b = ctx->d_cos_b;
         kp.frame_sc = ctx->d_frame_sc;
         kp.rg = S.d_rg;
         kp.count = count ? 1 : 0;
@@ -3951,10 +3461,8 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             rc = (count || po.kinds || po.hits) ? launch_preview<true>(ctx, kp, po, ss) : launch_preview<false>(ctx, kp, po, ss);
             if (rc) return rc;
         } else {
-        if (IPT_RAYGEN) {
-            hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((kp.total_units + 255) / 256)), dim3(256), 0, ss, kp);
-            HIPCHECK(ctx, hipGetLastError());
-        }
+        hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((kp.total_units + 255) / 256)), dim3(256), 0, ss, kp);
+        HIPCHECK(ctx, hipGetLastError());
         rc = susp <= 4 ? launch_path<4>(ctx, kp, ss, count) : launch_path<8>(ctx, kp, ss, count);
         if (rc) return rc;
         S.seq = kp.drain_seq;
@@ -4154,8 +3662,7 @@ void ipt_destroy(ipt_ctx* ctx) {
     ipt_internal::post_release(ctx);
     void* bufs[] = {ctx->d_cdf_lo, ctx->d_lgrid, ctx->d_lax, ctx->d_bvh_nodes, ctx->d_bvh_prims, ctx->d_light_nodes, ctx->d_lights, ctx->d_weights, ctx->d_cdf, ctx->d_wall, ctx->d_spheres,
                     ctx->d_counters, ctx->d_cos_a, ctx->d_cos_b, ctx->d_clk,
-                    ctx->d_grid_start, ctx->d_grid_items, ctx->d_grid_c4, ctx->d_grid_cells, ctx->d_frame_sc,
-                    ctx->d_grid_packed};
+                    ctx->d_grid_start, ctx->d_grid_items, ctx->d_grid_c4, ctx->d_frame_sc};
     for (void* b : bufs)
         if (b) hipFree(b);
     for (WorkSlot& S : ctx->slot) {
@@ -4238,7 +3745,7 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     // many spheres inside the box: a uniform grid; otherwise (and if the grid
     // cannot be built) the BVH
     SphereGrid grid;
-    bool use_grid = IPT_SPHERE_GRID && s->geometry_kind == IPT_GEOM_SPHERES_IN_BOX && s->n_spheres > 256 &&
+    bool use_grid = s->geometry_kind == IPT_GEOM_SPHERES_IN_BOX && s->n_spheres > 256 &&
                     grid_build_spheres(reinterpret_cast<const float*>(sph.data()), s->n_spheres, cam, B, grid);
     if (!use_grid && (s->geometry_kind == IPT_GEOM_SPHERES_IN_BOX || s->geometry_kind == IPT_GEOM_SPHERES) &&
         s->n_spheres > 16)
@@ -4269,7 +3776,7 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
         }
     }
     LightGrid lg;
-    const bool use_lgrid = IPT_LIGHT_GRID && ctx->light_grid_on && nl > kLdsLights && !any_round &&
+    const bool use_lgrid = ctx->light_grid_on && nl > kLdsLights && !any_round &&
                            s->geometry_kind == IPT_GEOM_SPHERE_IN_BOX && light_grid_build(L.data(), nl, lg);
     // (the lattice instances take the range-free light arithmetic: every
     // light's ranges proven as for the single light)
@@ -4280,7 +3787,7 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     // (the float compare the scan makes; nl+1 if none); kept when no bucket
     // spans more than 8 entries
     std::vector<int> cdf_lo(kCdfBuckets);
-    bool use_cdf_lo = IPT_CDF_LO && nl > kLdsLights && !any_round;
+    bool use_cdf_lo = nl > kLdsLights && !any_round;
     for (int b = 0; use_cdf_lo && b < kCdfBuckets; ++b) {
         const float start = (float)b / (float)kCdfBuckets;
         int c = 0;
@@ -4311,11 +3818,10 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
         if (count) HIPCHECK(ctx, hipMemcpy(buf.p, src, sizeof(T) * count, hipMemcpyHostToDevice));
         return IPT_OK;
     };
-    DevBuf<int> n_grid_start, n_lgrid, n_cdf_lo, n_grid_packed;
+    DevBuf<int> n_grid_start, n_lgrid, n_cdf_lo;
     DevBuf<LightAx> n_lax;
     DevBuf<BvhSphere> n_grid_items, n_bvh_prims;
     DevBuf<float4> n_grid_c4;
-    DevBuf<GridCell> n_grid_cells;
     DevBuf<BvhNode> n_light_nodes, n_bvh_nodes;
     DevBuf<LightDev> n_lights;
     DevBuf<float> n_weights, n_cdf;
@@ -4324,26 +3830,8 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     int rc = IPT_OK;
     if (use_grid && !rc) rc = upload(n_grid_start, grid.start.data(), grid.start.size());
     if (use_grid && !rc) rc = upload(n_grid_items, grid.items.data(), grid.items.size());
-    // IPT_GRID_LDS: grid.start as 8-entry block bases + byte offsets (every
-    // offset must fit a byte, else the instance is refused at render time)
-    std::vector<int> packed;
-    int packed_nb = 0;
-    if (IPT_GRID_LDS && use_grid) {
-        const size_t ne = grid.start.size();
-        packed_nb = (int)((ne + 7) / 8);
-        packed.assign((size_t)packed_nb + (ne + 3) / 4, 0);
-        uint8_t* off = reinterpret_cast<uint8_t*>(packed.data() + packed_nb);
-        bool fits = true;
-        for (size_t e = 0; e < ne; ++e) {
-            if (e % 8 == 0) packed[e / 8] = grid.start[e];
-            const int d = grid.start[e] - packed[e / 8];
-            fits &= d >= 0 && d <= 255;
-            off[e] = (uint8_t)d;
-        }
-        if (!fits) packed.clear();
-        if (!packed.empty() && !rc) rc = upload(n_grid_packed, packed.data(), packed.size());
-    }
-    if (IPT_GRID_C4 && use_grid && !rc) {
+    // the wave walk's items: [items] centre/radius, then [items] original indices
+    if (use_grid && !rc) {
         const size_t ni = grid.items.size();
         std::vector<float4> c4(ni + (ni + 3) / 4);
         int* idx = reinterpret_cast<int*>(c4.data() + ni);
@@ -4354,66 +3842,12 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
         }
         rc = upload(n_grid_c4, c4.data(), c4.size());
     }
-    std::vector<GridCell> gcells;
-    if (IPT_GRID_INLINE && use_grid) grid_cells_build(grid, gcells);
-    if (IPT_GRID_INLINE && use_grid && !rc) rc = upload(n_grid_cells, gcells.data(), gcells.size());
     if (!lnodes.empty() && !rc) rc = upload(n_light_nodes, lnodes.data(), lnodes.size());
     if (lg.pattern && !rc) rc = upload(n_lgrid, lg.cells.data(), lg.cells.size());
     std::vector<LightAx> laxr;
     if (lg.pattern)
         for (int i = 0; i < nl; ++i) laxr.push_back(light_ax_record(L[i], lg.pattern, wts[i]));
     if (lg.pattern && !rc) rc = upload(n_lax, laxr.data(), laxr.size());
-    // IPT_LPF_CALC: is every lattice light's sample record the formula of its
-    // index (a power-of-two row length, one origin, one pitch per axis)? The
-    // exact float operations of the kernel are replayed here for every light.
-    int lpf_calc = 0, lc_shift = 0, ltr_calc = 0, lg_ident = 0;
-    float lcv[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (IPT_LPF_CALC && lg.pattern && nl >= 2) {
-        int row = 1;
-        while (row < nl && laxr[row].py == laxr[0].py) ++row;
-        const bool p2 = row >= 2 && (row & (row - 1)) == 0 && nl % row == 0;
-        if (p2) {
-            lc_shift = 0;
-            while ((1 << lc_shift) < row) ++lc_shift;
-            const float cand[2] = {laxr[0].xa, laxr[0].ya};
-            for (int cx = 0; cx < 2 && !lpf_calc; ++cx)
-                for (int cy = 0; cy < 2 && !lpf_calc; ++cy) {
-                    const float x0 = laxr[0].px, y0 = laxr[0].py, dx = cand[cx], dy = cand[cy];
-                    bool ok = true;
-                    for (int i = 0; ok && i < nl; ++i) {
-                        volatile float fx = (float)(i & (row - 1)) * dx;  // (no contraction, as the kernel)
-                        volatile float fy = (float)(i >> lc_shift) * dy;
-                        const float px = x0 + fx, py = y0 + fy;
-                        ok = f2u(px) == f2u(laxr[i].px) && f2u(py) == f2u(laxr[i].py) &&
-                             f2u(laxr[i].xa) == f2u(laxr[0].xa) && f2u(laxr[i].ya) == f2u(laxr[0].ya);
-                    }
-                    if (ok) {
-                        lpf_calc = 1;
-                        lcv[0] = x0; lcv[1] = y0; lcv[2] = dx; lcv[3] = dy;
-                        lcv[4] = laxr[0].xa; lcv[5] = laxr[0].ya;
-                    }
-                }
-        }
-        // the light tests' records: the rest uniform, the cells an index formula
-        if (IPT_LTR_CALC && lpf_calc) {
-            bool same = true;
-            for (int i = 1; same && i < nl; ++i)
-                same = f2u(laxr[i].ix) == f2u(laxr[0].ix) && f2u(laxr[i].iy) == f2u(laxr[0].iy) &&
-                       f2u(laxr[i].area) == f2u(laxr[0].area) && f2u(laxr[i].spow) == f2u(laxr[0].spow);
-            if (same) {
-                ltr_calc = 1;
-                lcv[6] = laxr[0].ix; lcv[7] = laxr[0].iy; lcv[8] = laxr[0].area; lcv[9] = laxr[0].spow;
-            }
-            bool id1 = (int)lg.cells.size() == lg.nu * lg.nv, id2 = id1;
-            for (int j = 0; (id1 || id2) && j < lg.nv; ++j)
-                for (int i = 0; i < lg.nu; ++i) {
-                    const int c = lg.cells[i + lg.nu * j];
-                    id1 = id1 && c == i + lg.nu * j;
-                    id2 = id2 && c == j + lg.nv * i;
-                }
-            lg_ident = id1 ? 1 : (id2 ? 2 : 0);
-        }
-    }
     if (use_cdf_lo && !rc) rc = upload(n_cdf_lo, cdf_lo.data(), cdf_lo.size());
     if (!bnodes.empty() && !rc) rc = upload(n_bvh_nodes, bnodes.data(), bnodes.size());
     if (!bnodes.empty() && !rc) rc = upload(n_bvh_prims, bprims.data(), bprims.size());
@@ -4424,17 +3858,13 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     if (!rc) rc = upload(n_spheres, sph.data(), sph.size());
     if (rc) return rc;  // the temporaries free themselves; the context keeps no scene
     void* old[] = {ctx->d_lights, ctx->d_weights, ctx->d_cdf, ctx->d_spheres, ctx->d_bvh_nodes, ctx->d_bvh_prims,
-                   ctx->d_light_nodes, ctx->d_grid_start, ctx->d_grid_items, ctx->d_grid_c4, ctx->d_grid_cells, ctx->d_wall, ctx->d_lgrid, ctx->d_lax,
-                   ctx->d_cdf_lo, ctx->d_grid_packed};
+                   ctx->d_light_nodes, ctx->d_grid_start, ctx->d_grid_items, ctx->d_grid_c4, ctx->d_wall, ctx->d_lgrid, ctx->d_lax,
+                   ctx->d_cdf_lo};
     for (void* b : old)
         if (b) hipFree(b);
     ctx->d_grid_start = n_grid_start.release();
-    ctx->d_grid_packed = n_grid_packed.release();
-    ctx->grid_packed_words = (int)packed.size();
-    ctx->grid_packed_nb = packed_nb;
     ctx->d_grid_items = n_grid_items.release();
     ctx->d_grid_c4 = n_grid_c4.release();
-    ctx->d_grid_cells = n_grid_cells.release();
     ctx->n_grid = 0;
     if (use_grid) {
         ctx->n_grid = (int)(grid.start.size() - 1);
@@ -4449,11 +3879,6 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     ctx->d_lgrid = n_lgrid.release();
     ctx->d_lax = n_lax.release();
     ctx->d_cdf_lo = n_cdf_lo.release();
-    ctx->lpf_calc = lpf_calc;
-    ctx->lc_shift = lc_shift;
-    ctx->ltr_calc = ltr_calc;
-    ctx->lg_ident = lg_ident;
-    std::copy(lcv, lcv + 10, ctx->lc);
     lg.cells.clear();
     ctx->lgrid = lg;
     ctx->cdf_bsearch = cdf_mono ? 1 : 0;
@@ -4467,7 +3892,7 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     // Past the lights (ce >= nl) the scan's answer is ce's clamp to nl - 1, then
     // cdf[nl]. The kernel reads cdf[ce-1] and cdf[ce] only.
     ctx->cdf_p2 = 0;
-    for (int e = 1; IPT_CDF_POW2 && cdf_mono && nl > kLdsLights && !any_round && e <= 20 && !ctx->cdf_p2; ++e) {
+    for (int e = 1; cdf_mono && nl > kLdsLights && !any_round && e <= 20 && !ctx->cdf_p2; ++e) {
         const double w = std::ldexp(1.0, -e);
         bool ok = (double)nl * w <= 1.0;
         for (int i = 0; ok && i < nl; ++i) ok = std::fabs((double)cdf[i] - (double)(i + 1) * w) < 0.25 * w;
@@ -4476,13 +3901,12 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
             // exactly uniform on the draw's 24-bit integer: every light's
             // ceil(cdf[i] 2^24) is (i+1) 2^(24-e) (C5's 256 equal emitters),
             // so the integer pick reads no cdf entry at all (KParams::cdf_p2 2)
-            if (IPT_PICK_INT_CDF && IPT_CDF_EXACT && e <= 24) {
+            if (e <= 24) {
                 bool exact = true;
                 for (int i = 0; exact && i < nl; ++i)
                     exact = (word_threshold(cdf[i]) >> 8) == ((unsigned long long)(i + 1) << (24 - e));
                 if (exact) ctx->cdf_p2 = 2;
             }
-            ctx->cdf_p2s = std::ldexp(1.0f, e);
             ctx->cdf_p2e = e;
             ctx->cdf_end = cdf[nl];
         }
@@ -4490,7 +3914,7 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     ctx->any_round_light = any_round;
     // the axis-aligned single-light instances also take the range-free roots
     // and quotients: only where their ranges are proven (sphere-in-box scenes)
-    ctx->light_axis = (nl == 1 && !any_round && IPT_LIGHT_AXIS) ? axis_aligned_light(L[0]) : 0;
+    ctx->light_axis = (nl == 1 && !any_round) ? axis_aligned_light(L[0]) : 0;
     if (ctx->light_axis && !(s->geometry_kind == IPT_GEOM_SPHERE_IN_BOX && light_ranges_box(L[0], 2, cam)))
         ctx->light_axis = 0;
     // skip-ahead plane: one area light (or a lattice, whose lights share P.z
@@ -4507,15 +3931,16 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
                  zero(L[i].n.y) && !zero(L[i].n.z) && std::isfinite(L[i].n.z) && std::fabs(L[i].P.z) >= 0x1p-32f &&
                  std::fabs(L[i].P.z) <= 0x1p32f &&
                  f2u(L[i].P.z) == f2u(L[0].P.z) && f2u(L[i].n.z) == f2u(L[0].n.z);
+        float sa_cl = 0.0f;
         if (ok) {
             ctx->sa_on = 1;
             ctx->sa_pz = L[0].P.z;
             ctx->sa_nz = L[0].n.z;
             // UnionDdf::sample picks a light (c < nl) iff r < cdf[c] for some
             // c < nl, i.e. iff r < cdf[nl - 1] on a non-decreasing cdf
-            ctx->sa_cl = (nl == 1 || cdf_mono) ? cdf[nl - 1] : 0.0f;
+            sa_cl = (nl == 1 || cdf_mono) ? cdf[nl - 1] : 0.0f;
         }
-        ctx->sa_u = word_threshold(ctx->sa_on ? ctx->sa_cl : 0.0f);
+        ctx->sa_u = word_threshold(sa_cl);
     }
     ctx->d_bvh_nodes = n_bvh_nodes.release();
     ctx->d_bvh_prims = n_bvh_prims.release();
@@ -4857,7 +4282,6 @@ int ipt_math_selfcheck(ipt_ctx* ctx, int fn, uint64_t lo_bits, uint64_t hi_bits,
         return IPT_E_INVALID;
     hipSetDevice(ctx->device);
     if (fn == 14 || fn == 15) {
-        if (!IPT_FRAME_TAB) return fail(ctx, IPT_E_INVALID, "ipt_math_selfcheck: built without the frame table");
         const int rc = ensure_frame_table(ctx, ctx->stream);
         if (rc) return rc;
     }

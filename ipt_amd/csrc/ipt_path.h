@@ -278,7 +278,7 @@ IPT_HD float trace_box_planes_only(vec3 o, vec3 d, int* prim) {
 IPT_HD float max3_nn_(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
 // trace_box_planes_only with the hit point of the NEAREST candidate alone
-// (IPT_BOX_NEAREST). U_a is plane a's t after the rejections that need no hit
+// (the instances of box_nearest, ipt_kernels.hip). U_a is plane a's t after the rejections that need no hit
 // point (|d_a| < 1e-6, t < 1e-6, the y plane for d.y <= 0), m the scan's
 // winner over U ("nearer, or as near with a lower index") and p = o + d*U_m:
 //   * U_m = inf: every plane misses in the form above too;

@@ -4,10 +4,14 @@ ipt_kernels.hip + ipt_post.hip), to show that a source clean-up (removing
 dead A/B switches, diagnostics) leaves every kernel instruction-for-
 instruction unchanged.
 
-usage: isa_hash.py OUT.json [extra hipcc flags...]
+usage: isa_hash.py OUT.json [--mask-kernarg-offsets] [extra hipcc flags...]
 Compiles with __graft_entry__.HIPCC_FLAGS (device only, -S), splits the
 assembly per function and hashes its instruction lines (comments, labels'
 numbering and metadata directives dropped).
+
+--mask-kernarg-offsets replaces the offset immediate of every s_load_dword*
+line before hashing: a change of KParams' layout moves the kernel-argument
+loads' offsets and nothing else, and the masked hashes show that.
 """
 import hashlib
 import json
@@ -23,6 +27,8 @@ import __graft_entry__ as ge  # noqa: E402
 
 out_json = sys.argv[1]
 extra = sys.argv[2:]
+mask = "--mask-kernarg-offsets" in extra
+extra = [f for f in extra if f != "--mask-kernarg-offsets"]
 flags = [f for f in ge.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
 hashes = {}
 with tempfile.TemporaryDirectory() as td:
@@ -46,6 +52,8 @@ with tempfile.TemporaryDirectory() as td:
                 if not t.strip() or t.lstrip().startswith("."):
                     continue
                 t = re.sub(r"\.LBB\d+_\d+", ".LBB", t)
+                if mask and t.split()[0].startswith("s_load_dword"):
+                    t = re.sub(r",\s*(0x[0-9a-fA-F]+|\d+)\s*$", ", OFF", t)
                 body.append(t + "\n")
 json.dump(hashes, open(out_json, "w"), indent=1, sort_keys=True)
 print(f"{len(hashes)} functions -> {out_json}")

@@ -77,8 +77,8 @@ __global__ __launch_bounds__(256, WPS) void walk_split_kernel(KParams kp, const 
                     o = v3(rr.o[0], rr.o[1], rr.o[2]);
                     d = v3(rr.d[0], rr.d[1], rr.d[2]);
                     int xp = -1;
-                    best = (IPT_BOXDIV && kp.box_inrange) ? trace_box_planes_only<true>(o, d, &xp)
-                                                          : trace_box_planes_only<false>(o, d, &xp);
+                    best = kp.box_inrange ? trace_box_planes_only<true>(o, d, &xp)
+                                          : trace_box_planes_only<false>(o, d, &xp);
                     bidx = -2 - xp;
                     sphere_grid_init(kp, o, d, cell, tmx);
                     tracing = true;
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256, WPS) void walk_split_kernel(KParams kp, const 
             pool = pnext < n;  // (chunks are claimed in increasing order)
         }
         if (!__ballot(tracing)) break;
-        sphere_grid_walk_wave<COUNT>(kp, tracing, o, d, cell, tmx, best, bidx, budget, slots, lane, nullptr,
+        sphere_grid_walk_wave<COUNT>(kp, tracing, o, d, cell, tmx, best, bidx, budget, slots, lane,
                                      c_nodes, c_tests IPT_DIAG_NULL_ARGS);
         if (tracing && cell < 0) {
             tracing = false;
@@ -130,7 +130,6 @@ static int run_walk(ipt_ctx* ctx, unsigned long long n, int wgs_per_cu, int budg
     kp.grid_items = ctx->d_grid_items;
     kp.grid_c4 = ctx->d_grid_c4;
     kp.grid_idx = ctx->d_grid_c4 ? reinterpret_cast<const int*>(ctx->d_grid_c4 + ctx->grid_n_items) : nullptr;
-    kp.grid_cells = ctx->d_grid_cells;
     if (kp.n_grid <= 0) return -3;
     unsigned long long *next = nullptr, *out = nullptr;
     if (hipMalloc(&next, 8) != hipSuccess || hipMalloc(&out, 32) != hipSuccess) return -1;

@@ -1,4 +1,4 @@
-// Host check of trace_box_planes_nearest (ipt_path.h, IPT_BOX_NEAREST): the
+// Host check of trace_box_planes_nearest (ipt_path.h): the
 // nearest-candidate form against trace_box_planes_only, bit for bit on t and
 // prim, and its hit point against o + d*t wherever prim >= 0, for both INRANGE
 // forms. argv[1] = number of random rays per form (default 20 M). Rays:

@@ -1,5 +1,5 @@
 """Host check of the box planes' nearest-candidate form
-(ipt_path.h trace_box_planes_nearest, IPT_BOX_NEAREST): bit-identical t and
+(ipt_path.h trace_box_planes_nearest): bit-identical t and
 prim to trace_box_planes_only, and the returned hit point bit-identical to
 o + d*t, on 20 M rays per INRANGE form (tests/native/box_planes_check.cpp lists
 the ray classes). Every outcome class of the new form -- no candidate, the

@@ -76,3 +76,23 @@ def test_product_build_keeps_uniform_regions_structurized():
     root = Path(ge.__file__).resolve().parent
     for sh in ("variants.sh", "variants_full.sh", "regs.sh", "prof_phases.sh"):
         assert "structurizecfg" not in (root / "scripts" / sh).read_text(), sh
+
+
+def test_knobs_guard_names_every_parameter():
+    """ipt_knobs.h refuses an overridden parameter unless the build defines
+    IPT_AB_BUILD. The guard is a hand-written list: a parameter defined under
+    #ifndef but missing from it could be overridden by a stray -D without a
+    word, and a name left in it after its parameter is gone guards nothing.
+    The two sets are the same."""
+    import re
+    import __graft_entry__ as ge
+    from pathlib import Path
+    txt = (Path(ge.__file__).resolve().parent / "ipt_amd" / "csrc" / "ipt_knobs.h").read_text()
+    defined = re.findall(r"^#ifndef\s+(IPT_\w+)\s*\n#define\s+(IPT_\w+)", txt, re.M)
+    assert defined and all(a == b for a, b in defined)
+    assert len(defined) == len(re.findall(r"^#ifndef\s", txt, re.M))
+    guard = re.search(r"#if !defined\(IPT_AB_BUILD\)(.*?)\n#error", txt.replace("\\\n", " "), re.S)
+    assert guard
+    guarded = re.findall(r"defined\((IPT_\w+)\)", guard.group(1))
+    assert len(guarded) == len(set(guarded))
+    assert set(guarded) == {a for a, _ in defined}

@@ -1,4 +1,4 @@
-"""The box planes' nearest-candidate form (IPT_BOX_NEAREST, ipt_path.h
+"""The box planes' nearest-candidate form (ipt_path.h
 trace_box_planes_nearest) and the hit point the box trace hands to resolve, in
 the path kernel, against the oracle. The host half
 (tests/test_box_planes_host.py) compares the function itself with the full

@@ -615,7 +615,7 @@ def _jittered_powers(desc, rel, seed=3):
 
 @pytest.mark.parametrize("case", ["lattice_equal", "lattice_jitter", "random_jitter", "lattice_uneven"])
 def test_near_uniform_cdf_pick(gpu_ctx, oracle, case):
-    """The many-light pick from floor(r 2^e) and two cdf entries (IPT_CDF_POW2):
+    """The many-light pick from floor(r 2^e) and two cdf entries (a near-uniform cdf):
     nearly equal powers (the 256-emitter lattice's own rounding, or powers
     jittered by 1e-4 so that entries sit on both sides of (i+1) 2^-e), on the
     lattice and on the light-BVH instance; and powers too uneven for it (the
