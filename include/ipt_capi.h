@@ -245,7 +245,10 @@ const char* ipt_last_error(ipt_ctx* ctx); /* ctx may be NULL (creation errors) *
  * global memory, IPT_LIGHT_GRID=0 disables the light-lattice lookup (the light
  * BVH is used instead), IPT_LATTICE_LDS=0 keeps the lattice lights' records
  * in global memory (256-thread workgroups instead of one 1024-thread
- * workgroup per CU), IPT_BLOCKS_PER_CU caps the path kernel's residency. */
+ * workgroup per CU), IPT_BOX_GENERIC=1 launches the box scenes' generic
+ * path-kernel instance (the box planes' range form for origins beyond 2^39)
+ * whatever the scene's range, IPT_BLOCKS_PER_CU caps the path kernel's
+ * residency. */
 int ipt_create(int hip_device, ipt_ctx** out);
 void ipt_destroy(ipt_ctx* ctx);
 

@@ -152,7 +152,8 @@ struct KParams {
     const int* __restrict__ cdf_lo;       // [kCdfBuckets] or null: first c with cdf[c] > b/256
     double inv_per_pass, inv_w;           // 1/(n_cand*W), 1/W (exact 32-bit unit decomposition)
     uint32_t per_pass32;                  // n_cand*W (< 2^32)
-    int box_inrange;                      // camera and sphere list within 2^39 (box_plane_t<true>)
+    int box_inrange;                      // camera and sphere list within 2^39 (box_plane_t<true>): the sphere-list
+                                          // and preview kernels (the box path instances: BOXIN)
     const float* __restrict__ cos_a;      // [2^24] CosineDdf table by u1's 24 bits: sin(acos(sqrt(u1)))
     const float2* __restrict__ cos_b;     // (unread)
     const float2* __restrict__ frame_sc;  // frame_table_kernel: RotateDdf angle (sin, cos) by to.z
@@ -597,16 +598,28 @@ __device__ __forceinline__ void sphere_grid_walk_wave(const KParams& kp, bool wa
 
 // Nearest geometry hit for both geometry kinds. prim: 0..4 plane, 5 the
 // r=0.5 sphere, 6+i extra sphere i (original index), -1 miss.
-template <bool COUNT, int GEOM, bool NEAREST>
+// RANGE: the box planes' range form. In range, every ray origin (camera,
+// wall/floor hits, listed spheres) lies within 2^39, so the planes' divisions
+// take the range-free sequence. The path kernel's box instances fix the form at
+// compile time (one copy of the trace per instance); kRangeRuntime selects on
+// kp.box_inrange (the preview kernel).
+enum { kRangeRuntime = -1, kRangeGeneric = 0, kRangeIn = 1 };
+template <bool COUNT, int GEOM, bool NEAREST, int RANGE = kRangeRuntime>
 __device__ __forceinline__ float trace_geometry(const KParams& kp, vec3 o, vec3 d, int* prim, vec3* hit,
                                                 uint32_t& c_nodes, uint32_t& c_tests) {
-    // kp.box_inrange: every ray origin (camera, wall/floor hits, listed spheres)
-    // lies within 2^39, so the planes' divisions take the range-free sequence
     // (*hit: the box's hit point o + d*t where NEAREST, see resolve's kBoxHit)
     if (GEOM == IPT_GEOM_SPHERE_IN_BOX) {
-        if (NEAREST)
-            return kp.box_inrange ? trace_box_hit<true>(o, d, prim, hit) : trace_box_hit<false>(o, d, prim, hit);
-        return kp.box_inrange ? trace_box<true>(o, d, prim) : trace_box<false>(o, d, prim);
+        if constexpr (RANGE == kRangeIn) {
+            if (NEAREST) return trace_box_hit<true>(o, d, prim, hit);
+            return trace_box<true>(o, d, prim);
+        } else if constexpr (RANGE == kRangeGeneric) {
+            static_assert(!NEAREST || GEOM != IPT_GEOM_SPHERE_IN_BOX, "the generic box instances take the full form");
+            return trace_box<false>(o, d, prim);
+        } else {
+            if (NEAREST)
+                return kp.box_inrange ? trace_box_hit<true>(o, d, prim, hit) : trace_box_hit<false>(o, d, prim, hit);
+            return kp.box_inrange ? trace_box<true>(o, d, prim) : trace_box<false>(o, d, prim);
+        }
     }
     if (GEOM == IPT_GEOM_FLOOR) {  // GeometryFloor.cpp:11-13
         const float t = box_plane_t(o.z, d.z, -1.0f, o, d);
@@ -754,11 +767,18 @@ enum { kLightsOne = 1, kLightsLds = 2, kLightsGlobal = 3, kLightsAny = 4, kLight
 __host__ __device__ constexpr bool grid_lights(int lm) { return lm >= kLightsGridA10 && lm <= kLightsGridA01L; }
 __host__ __device__ constexpr bool lattice_a10(int lm) { return lm == kLightsGridA10 || lm == kLightsGridA10L; }
 // the instances whose box trace takes the nearest-candidate planes
-// (trace_box_planes_nearest): the box with one light or a light list. The lattice
-// instances, at their SGPR limit, lose 0.2 % with it and the sphere-list
-// instances' walls gain nothing measurable: both keep the full form.
-__host__ __device__ constexpr bool box_nearest(int lm, int geom) {
-    return geom == IPT_GEOM_SPHERE_IN_BOX && !grid_lights(lm);
+// (trace_box_planes_nearest): every in-range box instance (path_kernel's
+// BOXIN), the lattice instances included since the range form is fixed per
+// instance and the full form behind the vote is compiled once (+0.65 % C5,
+// DESIGN.md 4.12; with both range forms in the step they lost 0.2 %, 4.10).
+// The generic box instances keep the full form (kNearest), and so do the
+// sphere-list instances' walls, which gain nothing measurable (4.10).
+__host__ __device__ constexpr bool box_nearest(int geom) { return geom == IPT_GEOM_SPHERE_IN_BOX; }
+// the box instances that exist with the step's per-launch choices fixed
+// (path_kernel's FIXED): the axis-aligned single light (sample_scenes[0]'s
+// instance, +0.8 % C2) and the light lattices (+1.1 % C5)
+__host__ __device__ constexpr bool step_fixed_mode(int lm) {
+    return lm == kLightsOneA10 || lm == kLightsOneA01 || grid_lights(lm);
 }
 __host__ __device__ constexpr bool lax_in_lds(int lm) { return lm == kLightsGridA10L || lm == kLightsGridA01L; }
 __host__ __device__ constexpr bool global_lights(int lm) { return lm == kLightsGlobal || grid_lights(lm); }
@@ -888,8 +908,23 @@ __global__ __launch_bounds__(256) void raygen_kernel(const KParams kp) {
     }
 }
 
-template <int MAXSUSP, bool COUNT, int LMODE, int GEOM>
+// BOXIN (sphere-in-box instances; false in the others, which do not read it):
+// the box planes' range form, a property of the scene (box_inrange, set at
+// upload). true compiles the in-range trace alone, false the generic full-form
+// trace alone, correct for every input.
+// FIXED (step_fixed_mode's in-range box instances): two more choices of the
+// launch that the step otherwise makes once per step -- n_rays is a power of
+// two (the pop's unwind keeps its exact scaling form alone) and the lights'
+// skip-ahead plane exists (kp.sa_on: the skip-ahead and the pre-skip lose
+// their guard). Both are read from the launch's parameters by the dispatch
+// (launch_path4), so a launch without them takes the FIXED = false instance.
+template <int MAXSUSP, bool COUNT, int LMODE, int GEOM, bool BOXIN, bool FIXED>
 __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE)) void path_kernel(const KParams kp) {
+    static_assert(!BOXIN || GEOM == IPT_GEOM_SPHERE_IN_BOX, "BOXIN is the box instances' parameter");
+    static_assert(!FIXED || (BOXIN && step_fixed_mode(LMODE)), "FIXED: in-range box instances with a skip-ahead plane");
+    constexpr int kRange = GEOM == IPT_GEOM_SPHERE_IN_BOX ? (BOXIN ? kRangeIn : kRangeGeneric) : kRangeRuntime;
+    // the generic box instances keep the full-form trace (small, rarely run)
+    constexpr bool kNearest = box_nearest(GEOM) && kRange != kRangeGeneric;
     constexpr int kBlock = block_of(LMODE, GEOM);  // this instance's workgroup size
     extern __shared__ float lds[];
     // resumable sphere-list instances: the wave walk's 64-bit test slot per
@@ -1025,7 +1060,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     constexpr bool kRes = resumable_geom(GEOM);
     constexpr bool kResL = resumable_lights(LMODE, GEOM);
     // the box instances' direct trace hands its hit point to resolve (box_hitp)
-    constexpr bool kBoxHit = !kRes && !kResL && GEOM == IPT_GEOM_SPHERE_IN_BOX && box_nearest(LMODE, GEOM);
+    constexpr bool kBoxHit = !kRes && !kResL && GEOM == IPT_GEOM_SPHERE_IN_BOX && kNearest;
     // the frame-entry prefetch pays where every lane iterates every step; in the
     // resumable instances (lanes parked in walks) it measured -5 % on C5
     constexpr bool kFramePf = !(kRes || kResL);
@@ -1148,7 +1183,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             // sat in spilled scalar registers, a v_readlane per use.
             uint32_t nr = (uint32_t)kp.n_rays;
             asm volatile("" : "+s"(nr));
-            const bool n_pow2 = nr != 0u && (nr & (nr - 1u)) == 0u;
+            const bool n_pow2 = FIXED || (nr != 0u && (nr & (nr - 1u)) == 0u);
             const uint32_t p2_exp = 96u + (uint32_t)__clz((int)nr);  // 127 - log2 n_rays
             float v;
             auto unwind = [&](auto p2) {
@@ -1172,7 +1207,9 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     if (isfinite_(r)) v = kP2 ? r * __uint_as_float(sc) : r / (float)(kp.n_rays >> l);
                 }
             };
-            if (n_pow2)
+            if constexpr (FIXED)
+                unwind(std::true_type{});
+            else if (n_pow2)
                 unwind(std::true_type{});
             else
                 unwind(std::false_type{});
@@ -1390,7 +1427,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 // and is zero only when o.z == P.z; an underflowed product is
                 // +-0, i.e. not taken (conservative)
                 const bool back = (tpos.z - kp.sa_pz) * kp.sa_nz < 0.0f;
-                if (kp.sa_on && c < nl && back && j <= 1u && ti + 1 < (kp.n_rays >> tdepth)) {
+                if ((FIXED || kp.sa_on) && c < nl && back && j <= 1u && ti + 1 < (kp.n_rays >> tdepth)) {
                     ++ti;
                     if (COUNT) { ++c_iter; ++c_lsamp; ++c_skip; }
                     k += 3;
@@ -1421,7 +1458,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     r1 = odd ? e2 : e1;
                     r2 = odd ? e3 : e2;
                     pre_w = odd ? e4 : e3;
-                    pre_ok = jj <= 3u && kp.sa_on;
+                    pre_ok = jj <= 3u && (FIXED || kp.sa_on);
                 } else {
                     const bool hi = kSkipAhead && jj >= 4u;
                     r1 = hi ? w.b1 : sel4(jj & 3u, w.a1, w.a2, w.a3, w.b0);
@@ -1799,7 +1836,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     if (xrdepth < kp.depth_max) {
                         IPT_PHASE(9);
                         vec3 hitp;
-                        t = trace_geometry<COUNT, GEOM, box_nearest(LMODE, GEOM)>(kp, xro, xrd, &prim, &hitp, c_nodes, c_tests);
+                        t = trace_geometry<COUNT, GEOM, kNearest, kRange>(kp, xro, xrd, &prim, &hitp, c_nodes, c_tests);
                     }
                     const vec3 eb = xli_pos - xro;
                     resolve(xrdepth < kp.depth_max, t, prim, xro, xrd, xrdepth, xis_iter, mult, xhas_li, dot(eb, eb),
@@ -1997,7 +2034,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 float t = inf_();
                 if (rdepth < kp.depth_max) {
                     IPT_PHASE(9);
-                    t = trace_geometry<COUNT, GEOM, box_nearest(LMODE, GEOM)>(kp, ro, rd, &prim, &box_hitp, c_nodes, c_tests);
+                    t = trace_geometry<COUNT, GEOM, kNearest, kRange>(kp, ro, rd, &prim, &box_hitp, c_nodes, c_tests);
                     IPT_STAMP_AT(10);  // mixture value + geometry trace
                 }
                 const vec3 eb = li_pos - ro;
@@ -2853,6 +2890,7 @@ struct ipt_ctx {
     float2* d_frame_sc = nullptr;  // frame_table_kernel, 1 GiB
     float last_path_ms = 0.0f, last_acc_ms = 0.0f;
     int blocks_per_cu = 0;      // of the last path-kernel launch
+    bool box_generic = false;   // IPT_BOX_GENERIC=1: the box instances' generic range form (tests)
     bool lattice_lds = true;    // IPT_LATTICE_LDS=0: the lattice instances with global records (tests)
     size_t max_lds = 160 * 1024;  // the device's LDS per workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock)
     ipt_internal::PostScratch post;  // ipt_display_device's scratch and completion event (ipt_post.hip)
@@ -3149,11 +3187,11 @@ size_t path_lds_bytes(const KParams& kp) {
            sizeof(float);
 }
 
-template <int MAXSUSP, bool COUNT, int LMODE, int GEOM>
-int launch_path4(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
+template <int MAXSUSP, bool COUNT, int LMODE, int GEOM, bool BOXIN, bool FIXED>
+int launch_path5(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     constexpr int kBlock = block_of(LMODE, GEOM);
     const size_t lds = path_lds_bytes<MAXSUSP, LMODE, GEOM>(kp);
-    const void* fn = (const void*)path_kernel<MAXSUSP, COUNT, LMODE, GEOM>;
+    const void* fn = (const void*)path_kernel<MAXSUSP, COUNT, LMODE, GEOM, BOXIN, FIXED>;
     HIPCHECK(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // persistent grid: every block the CUs can hold at once (a work queue, no
     // inter-block waits, so an over-reported residency only queues blocks)
@@ -3163,9 +3201,27 @@ int launch_path4(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     if (ctx->bpc_override > 0) bpc = std::min(bpc, ctx->bpc_override);  // IPT_BLOCKS_PER_CU (profiling)
     ctx->blocks_per_cu = bpc;
     dim3 grid(ctx->n_cu * bpc), block(kBlock);
-    hipLaunchKernelGGL((path_kernel<MAXSUSP, COUNT, LMODE, GEOM>), grid, block, lds, st, kp);
+    hipLaunchKernelGGL((path_kernel<MAXSUSP, COUNT, LMODE, GEOM, BOXIN, FIXED>), grid, block, lds, st, kp);
     HIPCHECK(ctx, hipGetLastError());
     return IPT_OK;
+}
+// the box instances' range form (path_kernel's BOXIN): in range unless the
+// scene is not (box_inrange) or IPT_BOX_GENERIC=1 forces the generic instance;
+// and, in range, the instance with the step's per-launch choices fixed (FIXED)
+// where the launch has them: n_rays a power of two, a skip-ahead plane
+template <int MAXSUSP, bool COUNT, int LMODE, int GEOM>
+int launch_path4(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
+    if constexpr (GEOM == IPT_GEOM_SPHERE_IN_BOX) {
+        if (ctx->box_inrange && !ctx->box_generic) {
+            if constexpr (step_fixed_mode(LMODE)) {
+                const uint32_t nr = (uint32_t)kp.n_rays;
+                if (kp.sa_on && nr != 0u && (nr & (nr - 1u)) == 0u)
+                    return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, true>(ctx, kp, st);
+            }
+            return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, false>(ctx, kp, st);
+        }
+    }
+    return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, false, false>(ctx, kp, st);
 }
 // -DIPT_AB_BUILD -DIPT_C2_ONLY=1: experiment builds (scripts/variants.sh)
 // instantiate the sample_scenes[0] kernel alone (ipt_knobs.h).
@@ -3576,6 +3632,7 @@ int ipt_create(int hip_device, ipt_ctx** out) {
     if (const char* e = std::getenv("IPT_LNODES_LDS")) ctx->lnodes_lds = std::atoi(e) != 0;
     if (const char* e = std::getenv("IPT_LIGHT_GRID")) ctx->light_grid_on = std::atoi(e) != 0;
     if (const char* e = std::getenv("IPT_LATTICE_LDS")) ctx->lattice_lds = std::atoi(e) != 0;
+    if (const char* e = std::getenv("IPT_BOX_GENERIC")) ctx->box_generic = std::atoi(e) != 0;
     if (hipSetDevice(hip_device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx;
         return fail(nullptr, IPT_E_DEVICE, "stream creation failed");

@@ -11,7 +11,22 @@ Cold blocks are counted apart: the out-of-table frame angle (f64 division /
 rsq), the non-power-of-two res/n divisions of the pop, the sqrt tie of
 longer_sq in resolve, and every block reachable only through them.
 
-usage: step_budget.py listing.s [--instance Lb0E] [--blocks]
+The `cycles` column weighs the counts by what a wave64 instruction of each
+class costs the SIMD's issue (scripts/ubench_valu.hip, measured on the MI355X:
+profiles/round1_ubench_valu.jsonl and round1_ubench_path.jsonl, the
+cycles_per_wave_op of v_add_f32 / v_fma_f32, "u32*u32->u64 + xor", v_rcp_f32,
+v_mul_f64 / v_fma_f64): a plain VALU instruction 2.5 cycles, v_mad_u64_u32 (the
+Philox multiplies) 7.8, a transcendental (rcp, rsq, sqrt, exp, log, sin, cos)
+8, an f64 instruction 4.2 (the f64 transcendentals of the cold blocks count
+as transcendentals). SALU, LDS and memory instructions are not in it: the
+column prices the VALU pipe alone, so it ranks VALU-for-VALU rewrites; a trade
+between VALU and scalar instructions or branches, which take the wave's issue
+slot too, still needs an A/B.
+
+usage: step_budget.py listing.s [--instance REGEX] [--blocks]
+--instance: a regular expression searched in the mangled kernel names; the
+default is the product (COUNT = false) 4-level box instance, in range where
+the range form is an instance parameter.
 """
 import re
 import sys
@@ -25,12 +40,14 @@ SEG = {  # opening mark -> the segment it opens (ipt_kernels.hip, IPT_STAMP_AT)
 ORDER = [7, 0, 1, 2, 3, 4, 5, 8, 9, 10, 11, 6]
 TRANS = ("v_rcp", "v_rsq", "v_sqrt", "v_exp", "v_log", "v_sin", "v_cos")
 LANE = ("v_readlane", "v_writelane", "v_readfirstlane", "ds_bpermute", "ds_permute", "v_permlane")
+# cycles per wave64 instruction (profiles/round1_ubench_valu.jsonl)
+CYC_PLAIN, CYC_MAD64, CYC_TRANS, CYC_F64 = 2.5, 7.8, 8.0, 4.2
 COLD_F64 = ("v_rsq_f64", "v_div_scale_f64", "v_rcp_f64", "v_div_fmas_f64", "v_div_fixup_f64")
 
 
 def body_of(txt, inst):
     for m in re.finditer(r"\n(_Z\S*path_kernel\S*):[^\n]*\n(.*?)\n\.Lfunc_end", txt, re.S):
-        if inst in m.group(1):
+        if re.search(inst, m.group(1)):
             return m.group(2)
     raise SystemExit(f"no path_kernel instance matching {inst}")
 
@@ -135,6 +152,14 @@ def count(ops):
         o = s.split()[0]
         if o.startswith("v_"):
             c["valu"] += 1
+            if o.startswith(TRANS):
+                c["cycles"] += CYC_TRANS
+            elif o.startswith("v_mad_u64_u32") or o.startswith("v_mad_i64_i32"):
+                c["cycles"] += CYC_MAD64
+            elif "f64" in o:
+                c["cycles"] += CYC_F64
+            else:
+                c["cycles"] += CYC_PLAIN
             if o.startswith("v_mov") or o.startswith("v_accvgpr"):
                 c["mov"] += 1
             elif o.startswith("v_cndmask"):
@@ -160,12 +185,16 @@ def count(ops):
     return c
 
 
-COLS = ("valu", "mov", "cnd", "lane", "trans", "f64", "salu", "br", "sx", "nop", "lds", "vmem")
+COLS = ("cycles", "valu", "mov", "cnd", "lane", "trans", "f64", "salu", "br", "sx", "nop", "lds", "vmem")
+
+
+def fmt(v):
+    return f"{v:7.0f}"
 
 
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    inst = "Lb0E"
+    inst = r"path_kernelILi4ELb0ELi\d+ELi0E(Lb1E){0,2}EEvNS"
     if "--instance" in sys.argv:
         inst = sys.argv[sys.argv.index("--instance") + 1]
         args.remove(inst)
@@ -190,18 +219,19 @@ def main():
     names = [SEG[s] for s in ORDER] + ["pop: levels past the first two (loop)"]
     names += sorted(k for k in rows if k not in names and not k.startswith(("COLD", "setup")))
     hot = defaultdict(int)
-    print(f"{'segment':52s}" + "".join(f"{c:>6s}" for c in COLS))
+    print(f"{'segment':52s}" + "".join(f"{c:>7s}" for c in COLS))
     for n in names:
         if n in rows:
-            print(f"{n:52s}" + "".join(f"{rows[n][c]:6d}" for c in COLS))
+            print(f"{n:52s}" + "".join(fmt(rows[n][c]) for c in COLS))
             if not n.startswith("pop: levels"):
                 for c in COLS:
                     hot[c] += rows[n][c]
-    print(f"{'HOT STEP (every wave-step; without the pop loop)':52s}" + "".join(f"{hot[c]:6d}" for c in COLS))
+    print(f"{'HOT STEP (every wave-step; without the pop loop)':52s}" + "".join(fmt(hot[c]) for c in COLS))
     for n in sorted(rows):
         if n.startswith(("COLD", "setup")):
-            print(f"{n:52s}" + "".join(f"{rows[n][c]:6d}" for c in COLS))
-    print("columns: valu = all VALU, of which mov (v_mov), cnd (v_cndmask), lane (read/writelane), trans, f64;")
+            print(f"{n:52s}" + "".join(fmt(rows[n][c]) for c in COLS))
+    print("columns: cycles = VALU issue cycles per wave (plain 2.5, v_mad_u64_u32 7.8, trans 8, f64 4.2);")
+    print("         valu = all VALU, of which mov (v_mov), cnd (v_cndmask), lane (read/writelane), trans, f64;")
     print("         salu = all SALU, of which br (branches), sx (saveexec), nop (s_nop); lds; vmem")
 
 
