@@ -780,6 +780,10 @@ __host__ __device__ constexpr bool box_nearest(int geom) { return geom == IPT_GE
 __host__ __device__ constexpr bool step_fixed_mode(int lm) {
     return lm == kLightsOneA10 || lm == kLightsOneA01 || grid_lights(lm);
 }
+// path_kernel's FIXED: 0, kFixedPow2, or the tree shape K = log2 n_rays (the
+// one compiled K: n_rays 16, every configuration of bench.py but C3)
+constexpr int kFixedPow2 = -1;
+constexpr int kTreeK = 4;
 __host__ __device__ constexpr bool lax_in_lds(int lm) { return lm == kLightsGridA10L || lm == kLightsGridA01L; }
 __host__ __device__ constexpr bool global_lights(int lm) { return lm == kLightsGlobal || grid_lights(lm); }
 // kLightsOneA10 / A01: the single light is an axis-aligned AreaLight
@@ -917,11 +921,24 @@ __global__ __launch_bounds__(256) void raygen_kernel(const KParams kp) {
 // two (the pop's unwind keeps its exact scaling form alone) and the lights'
 // skip-ahead plane exists (kp.sa_on: the skip-ahead and the pre-skip lose
 // their guard). Both are read from the launch's parameters by the dispatch
-// (launch_path4), so a launch without them takes the FIXED = false instance.
-template <int MAXSUSP, bool COUNT, int LMODE, int GEOM, bool BOXIN, bool FIXED>
+// (launch_path4), so a launch without them takes the FIXED = 0 instance.
+// FIXED = K > 0 (kTreeK; the 4-level instances): the tree's shape is the
+// launch's as well -- n_rays == 2^K, hence meta_shift, and depth_max > K + 1:
+// no node deeper than K is pushed (n_rays >> d == 0 beyond), so no ray has
+// rdepth > K + 1 and every ray is traced. The step then reads neither
+// kp.n_rays, kp.meta_shift nor kp.depth_max. kFixedPow2 is the form above
+// (any power of two, any depth_max).
+template <int MAXSUSP, bool COUNT, int LMODE, int GEOM, bool BOXIN, int FIXED>
 __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE)) void path_kernel(const KParams kp) {
     static_assert(!BOXIN || GEOM == IPT_GEOM_SPHERE_IN_BOX, "BOXIN is the box instances' parameter");
     static_assert(!FIXED || (BOXIN && step_fixed_mode(LMODE)), "FIXED: in-range box instances with a skip-ahead plane");
+    static_assert(FIXED >= kFixedPow2 && FIXED <= MAXSUSP, "FIXED = K: K suspended levels");
+    constexpr bool kFixed = FIXED != 0;
+    constexpr int kK = FIXED > 0 ? FIXED : 0;
+    // the launch's tree shape, constants in the FIXED = K instances (written as
+    // conditional expressions on kK at each use: the other instances keep
+    // their code, and their register assignment, as it was)
+    constexpr int kTreeRays = 1 << kK, kTreeMetaShift = kTreeRays > 255 ? 16 : 8;
     constexpr int kRange = GEOM == IPT_GEOM_SPHERE_IN_BOX ? (BOXIN ? kRangeIn : kRangeGeneric) : kRangeRuntime;
     // the generic box instances keep the full-form trace (small, rarely run)
     constexpr bool kNearest = box_nearest(GEOM) && kRange != kRangeGeneric;
@@ -1143,7 +1160,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         // (a lane with a path is active, and a path is fresh only between the
         // refill and the new-path phase of one step: at the end-of-step pop
         // neither flag has to be read)
-        if (has_path && (kFramePf || !fresh) && !((kRes || kResL) && tracing) && ti >= (kp.n_rays >> tdepth)) {
+        if (has_path && (kFramePf || !fresh) && !((kRes || kResL) && tracing) && ti >= ((kK > 0 ? kTreeRays : kp.n_rays) >> tdepth)) {
             // the node is done: unwind every suspended level whose node has run
             // all its iterations too (finm, set at push) in one pass -- only
             // their res/multiplier are read -- then resume the first level
@@ -1181,9 +1198,10 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             // same product. The choice and the exponent come from n_rays
             // inside the step (scalar instructions): as loop invariants they
             // sat in spilled scalar registers, a v_readlane per use.
-            uint32_t nr = (uint32_t)kp.n_rays;
-            asm volatile("" : "+s"(nr));
-            const bool n_pow2 = FIXED || (nr != 0u && (nr & (nr - 1u)) == 0u);
+            // (FIXED = K: the exponent is a constant)
+            uint32_t nr = kK > 0 ? 1u << kK : (uint32_t)kp.n_rays;
+            if constexpr (kK == 0) asm volatile("" : "+s"(nr));
+            const bool n_pow2 = kFixed || (nr != 0u && (nr & (nr - 1u)) == 0u);
             const uint32_t p2_exp = 96u + (uint32_t)__clz((int)nr);  // 127 - log2 n_rays
             float v;
             auto unwind = [&](auto p2) {
@@ -1207,7 +1225,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     if (isfinite_(r)) v = kP2 ? r * __uint_as_float(sc) : r / (float)(kp.n_rays >> l);
                 }
             };
-            if constexpr (FIXED)
+            if constexpr (kFixed)
                 unwind(std::true_type{});
             else if (n_pow2)
                 unwind(std::true_type{});
@@ -1219,8 +1237,8 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 tres = s3 + (s4 * 1.0f) * v;  // res += multiplier*albedo*ray_power
                 // (unsigned: with n_rays > 255 a kind of 6 + sphere index >= 32768
                 // sets bit 31 of the word, which must not sign-extend)
-                tkind = (int)((uint32_t)meta >> kp.meta_shift);
-                ti = (int)__builtin_amdgcn_ubfe((uint32_t)meta, 0u, (uint32_t)kp.meta_shift);  // meta_shift <= 31
+                tkind = (int)((uint32_t)meta >> (kK > 0 ? kTreeMetaShift : kp.meta_shift));
+                ti = (int)__builtin_amdgcn_ubfe((uint32_t)meta, 0u, (uint32_t)(kK > 0 ? kTreeMetaShift : kp.meta_shift));  // meta_shift <= 31
                 need_frame = tkind >= 5 && fdepth != stop;
                 tdepth = stop;
                 // (the resumed node's position and depth land in the lane's
@@ -1427,7 +1445,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 // and is zero only when o.z == P.z; an underflowed product is
                 // +-0, i.e. not taken (conservative)
                 const bool back = (tpos.z - kp.sa_pz) * kp.sa_nz < 0.0f;
-                if ((FIXED || kp.sa_on) && c < nl && back && j <= 1u && ti + 1 < (kp.n_rays >> tdepth)) {
+                if ((kFixed || kp.sa_on) && c < nl && back && j <= 1u && ti + 1 < ((kK > 0 ? kTreeRays : kp.n_rays) >> tdepth)) {
                     ++ti;
                     if (COUNT) { ++c_iter; ++c_lsamp; ++c_skip; }
                     k += 3;
@@ -1458,7 +1476,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     r1 = odd ? e2 : e1;
                     r2 = odd ? e3 : e2;
                     pre_w = odd ? e4 : e3;
-                    pre_ok = jj <= 3u && (FIXED || kp.sa_on);
+                    pre_ok = jj <= 3u && (kFixed || kp.sa_on);
                 } else {
                     const bool hi = kSkipAhead && jj >= 4u;
                     r1 = hi ? w.b1 : sel4(jj & 3u, w.a1, w.a2, w.a3, w.b0);
@@ -1707,7 +1725,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 if (__builtin_expect(__any(tie), 0))
                     if (tie) lg = sqrt_(x) > sqrt_(y);
                 const bool li_wins = has_li && (!has_si || lg);
-                const int nchild = kp.n_rays >> depth;
+                const int nchild = (kK > 0 ? kTreeRays : kp.n_rays) >> depth;
                 const float zero = 0.0f;
                 // 0/0 for an expanded node without children: the NaN that
                 // poisons the parent (main.cpp:181)
@@ -1721,14 +1739,14 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 IPT_PHASE(10);
                 if (iter) {
                     const uint32_t lbit = 1u << tdepth;
-                    finm = (finm & ~lbit) | (ti >= (kp.n_rays >> tdepth) ? lbit : 0u);
+                    finm = (finm & ~lbit) | (ti >= ((kK > 0 ? kTreeRays : kp.n_rays) >> tdepth) ? lbit : 0u);
                     lds_float* b = (lds_float*)(stk + tid) + __umul24((uint32_t)tdepth, (uint32_t)(kStackFields * kBlock));  // (32-bit LDS address)
                     b[0 * kBlock] = tpos.x;
                     b[1 * kBlock] = tpos.y;
                     b[2 * kBlock] = tpos.z;
                     b[3 * kBlock] = tres;
                     b[4 * kBlock] = mult;
-                    b[5 * kBlock] = __uint_as_float((uint32_t)ti | ((uint32_t)tkind << kp.meta_shift));
+                    b[5 * kBlock] = __uint_as_float((uint32_t)ti | ((uint32_t)tkind << (kK > 0 ? kTreeMetaShift : kp.meta_shift)));
                 }
                 tpos = si_pos;
                 tkind = prim;
@@ -1914,7 +1932,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             };
             // the reference's event count: every light traced once for the
             // pdf (iterations) and once for traceRayToLight (depth < max)
-            if (COUNT) c_ltr += (uint32_t)nl * ((is_iter ? 1u : 0u) + ((rdepth < kp.depth_max) ? 1u : 0u));
+            if (COUNT) c_ltr += (uint32_t)nl * ((is_iter ? 1u : 0u) + ((kK > 0 || rdepth < kp.depth_max) ? 1u : 0u));
             if constexpr (grid_lights(LMODE)) {
                 // the ray's point on the lights' plane and its cell(s): every
                 // light whose exact test can pass lies in a cell within
@@ -2032,13 +2050,13 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             } else {
                 int prim = -1;
                 float t = inf_();
-                if (rdepth < kp.depth_max) {
+                if (kK > 0 || rdepth < kp.depth_max) {
                     IPT_PHASE(9);
                     t = trace_geometry<COUNT, GEOM, kNearest, kRange>(kp, ro, rd, &prim, &box_hitp, c_nodes, c_tests);
                     IPT_STAMP_AT(10);  // mixture value + geometry trace
                 }
                 const vec3 eb = li_pos - ro;
-                resolve(rdepth < kp.depth_max, t, prim, ro, rd, rdepth, is_iter, mult, has_li, dot(eb, eb), li_pow);
+                resolve(kK > 0 || rdepth < kp.depth_max, t, prim, ro, rd, rdepth, is_iter, mult, has_li, dot(eb, eb), li_pow);
             }
         }
         IPT_STAMP_AT(11);  // resolve + push
@@ -2089,7 +2107,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             // (as selects: no exec-mask branch)
             const bool back = (tpos.z - kp.sa_pz) * kp.sa_nz < 0.0f;
             const bool lpick = (unsigned long long)pre_w < kp.sa_u;
-            const bool take = iter_lane && pre_ok && back && ti < (kp.n_rays >> tdepth) && lpick;
+            const bool take = iter_lane && pre_ok && back && ti < ((kK > 0 ? kTreeRays : kp.n_rays) >> tdepth) && lpick;
             ti += take ? 1 : 0;
             k += take ? 3u : 0u;
             if (COUNT) {
@@ -3187,7 +3205,7 @@ size_t path_lds_bytes(const KParams& kp) {
            sizeof(float);
 }
 
-template <int MAXSUSP, bool COUNT, int LMODE, int GEOM, bool BOXIN, bool FIXED>
+template <int MAXSUSP, bool COUNT, int LMODE, int GEOM, bool BOXIN, int FIXED>
 int launch_path5(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     constexpr int kBlock = block_of(LMODE, GEOM);
     const size_t lds = path_lds_bytes<MAXSUSP, LMODE, GEOM>(kp);
@@ -3215,13 +3233,19 @@ int launch_path4(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
         if (ctx->box_inrange && !ctx->box_generic) {
             if constexpr (step_fixed_mode(LMODE)) {
                 const uint32_t nr = (uint32_t)kp.n_rays;
-                if (kp.sa_on && nr != 0u && (nr & (nr - 1u)) == 0u)
-                    return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, true>(ctx, kp, st);
+                if (kp.sa_on && nr != 0u && (nr & (nr - 1u)) == 0u) {
+                    // the tree shape as well: n_rays == 2^K and depth_max > K + 1 (then
+                    // the stack has K levels: the 4-level instances)
+                    if constexpr (MAXSUSP == kTreeK)
+                        if (nr == (1u << kTreeK) && kp.depth_max > kTreeK + 1)
+                            return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, kTreeK>(ctx, kp, st);
+                    return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, kFixedPow2>(ctx, kp, st);
+                }
             }
-            return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, false>(ctx, kp, st);
+            return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, 0>(ctx, kp, st);
         }
     }
-    return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, false, false>(ctx, kp, st);
+    return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, false, 0>(ctx, kp, st);
 }
 // -DIPT_AB_BUILD -DIPT_C2_ONLY=1: experiment builds (scripts/variants.sh)
 // instantiate the sample_scenes[0] kernel alone (ipt_knobs.h).

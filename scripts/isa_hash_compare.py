@@ -13,7 +13,7 @@ import re
 import sys
 from collections import defaultdict
 
-PK = re.compile(r"path_kernelILi(\d+)ELb(\d)ELi(\d+)ELi(\d+)E((?:L[bi]\d+E)*)E")
+PK = re.compile(r"path_kernelILi(\d+)ELb(\d)ELi(\d+)ELi(\d+)E((?:L[bi]n?\d+E)*)E")  # (n: a negative value)
 
 
 def split(hashes):
