@@ -629,6 +629,37 @@ int ipt_math_device(ipt_ctx* ctx, int fn, const float* in, float* out, int64_t n
 int ipt_math_selfcheck(ipt_ctx* ctx, int fn, uint64_t lo_bits, uint64_t hi_bits, uint64_t* mismatches,
                        uint32_t* first_bad);
 
+/* ---- the render plane's replay on chosen samples (ABI 7 addition), for tests --
+   The probe of accumulate_kernel: what a render does after its path kernel,
+   with the caller's samples in place of traced ones (one entry point added; no
+   layout change). values and codes are host buffers [spp][H][W], whole frames,
+   exactly as ipt_render_values returns them (codes relative to the nominal
+   destination of the call's plane); dev_img is a device image as
+   ipt_render_device takes it (sums and pixel_max may be NULL, the plane may be
+   preloaded). Synchronous: the image is complete on return. `hip_stream` as
+   ipt_render_device's (NULL = the context's own stream).
+   Read from p: width, height, spp, tile_rows, n_shards, shard_id and
+   IPT_FLAG_GUI_PLANE; no scene is needed. The call runs the render's own code
+   behind the path kernel -- the shard plan (ipt_shard_plan), the candidate-row
+   layout, the per-launch drift flags, the chunking into launches, the one
+   accumulate_kernel launch per chunk -- with a small marking kernel in the
+   place of raygen and path kernel: it moves each sample into the candidate
+   layout, flags the nominal and the destination pixel of every code other
+   than 0x05, and stores value 0 and code 0xfe where the destination row
+   belongs to another shard, as a render does.
+   Refused on the host, before any device buffer is touched or anything is
+   launched: a NULL pointer, a non-positive size, a negative spp, a shard_id
+   outside the plan, a code >= 0x10 or with a field of 3 (0xfe and 0xff, the
+   library's own markers, among them), a code whose destination (ix + dx,
+   nominal row + dy) lies outside [0, W) x [0, H) under the call's row map:
+   IPT_E_INVALID; any flag other than IPT_FLAG_GUI_PLANE, or more than
+   IPT_REPLAY_MAX_SAMPLES = 2^24 samples (spp * width * height; the call
+   stages them on the device, 5 B each): IPT_E_UNSUPPORTED. spp == 0 is a
+   no-op. */
+#define IPT_REPLAY_MAX_SAMPLES (1 << 24)
+int ipt_replay_samples(ipt_ctx* ctx, const ipt_params* p, const float* values, const uint8_t* codes,
+                       ipt_image* dev_img, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

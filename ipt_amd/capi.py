@@ -36,6 +36,7 @@ IPT_LIGHT_SPHERE, IPT_LIGHT_POINT, IPT_LIGHT_OUTER_SPHERE = 2, 3, 4
 IPT_FLAG_COUNTERS = 1
 IPT_FLAG_GUI_PLANE = 2  # Gui::addRay's row map instead of GridRenderPlane::addRay's (ABI 7)
 IPT_FLAG_PREVIEW = 4  # ray_power_preview instead of ray_power_recursive (ABI 7 addition)
+IPT_REPLAY_MAX_SAMPLES = 1 << 24  # ipt_replay_samples: spp * width * height per call (ABI 7 addition)
 
 F3 = C.c_float * 3
 
@@ -111,7 +112,7 @@ EXPORTED_SYMBOLS = (
     "ipt_display_device", "ipt_display", "ipt_powf_host", "ipt_powf_device",
     "ipt_display_stats_device", "ipt_display_stats",
     "ipt_smooth_device", "ipt_pgm_device", "ipt_pgm", "ipt_logf_host", "ipt_logf_device",
-    "ipt_preview_values",
+    "ipt_preview_values", "ipt_replay_samples",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -198,6 +199,9 @@ def load(path: str | os.PathLike | None = None):
         lib.ipt_logf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     if hasattr(lib, "ipt_preview_values"):  # ABI 7 addition
         lib.ipt_preview_values.argtypes = [C.c_void_p, C.POINTER(Params)] + [C.c_void_p] * 4
+    if hasattr(lib, "ipt_replay_samples"):  # ABI 7 addition
+        lib.ipt_replay_samples.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Image),
+                                           C.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -355,6 +359,23 @@ class Context:
         im = Image()
         im.pixels, im.counters, im.sums, im.pixel_max = pixels_ptr, counters_ptr, sums_ptr, max_ptr
         _check(self.lib, self.h, self.lib.ipt_render_device_async(self.h, C.byref(p), C.byref(im), stream))
+
+    def replay_samples(self, p: Params, values, codes, pixels_ptr, counters_ptr, sums_ptr=None, max_ptr=None,
+                       stream=None):
+        """The render plane's replay of the caller's samples (ipt_replay_samples):
+        values float32 and codes uint8, [spp][H][W] as render_values returns
+        them, into a device image. Synchronous. None for values or codes is
+        passed on as NULL; the library checks everything else."""
+        v = None if values is None else np.ascontiguousarray(values, np.float32)
+        c = None if codes is None else np.ascontiguousarray(codes, np.uint8)
+        for a in (v, c):
+            if a is not None and a.size < p.spp * p.width * p.height:
+                raise ValueError("fewer samples than spp * width * height")
+        im = Image()
+        im.pixels, im.counters, im.sums, im.pixel_max = pixels_ptr, counters_ptr, sums_ptr, max_ptr
+        _check(self.lib, self.h, self.lib.ipt_replay_samples(
+            self.h, C.byref(p), None if v is None else v.ctypes.data, None if c is None else c.ctypes.data,
+            C.byref(im), stream))
 
     def wait(self):
         _check(self.lib, self.h, self.lib.ipt_render_wait(self.h))

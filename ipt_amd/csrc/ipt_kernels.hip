@@ -2433,6 +2433,41 @@ __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int 
     if (ap.pixel_max) ap.pixel_max[d] = m;
 }
 
+// ipt_replay_samples' sample source: the caller's whole-frame samples
+// [spp][H][W] of this launch's passes, on the device.
+struct ReplaySrc {
+    const float* values;
+    const uint8_t* codes;
+};
+// One thread per work unit, in raygen_kernel's place (and no path kernel): what
+// new_path_setup does with a code, restated for a code that is given instead
+// of computed -- the sample goes to its unit of the candidate layout, a code
+// other than 0x05 flags its nominal pixel and its destination, a destination
+// row of another shard leaves value 0 and code 0xfe. The host has checked
+// every code (ipt_replay_samples): its destination lies inside the frame.
+__global__ __launch_bounds__(256) void replay_mark_kernel(const KParams kp, const ReplaySrc src) {
+    const unsigned long long unit = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (unit >= kp.total_units) return;
+    const bool sharded = !(kp.n_shards <= 1 || kp.tile_rows <= 0);
+    const uint32_t u32 = (uint32_t)unit;
+    const uint32_t s = udiv_exact(u32, kp.per_pass32, kp.inv_per_pass);
+    const uint32_t rem = u32 - s * kp.per_pass32;
+    const int cand = (int)udiv_exact(rem, (uint32_t)kp.W, kp.inv_w);
+    const int ix = (int)(rem - (uint32_t)cand * (uint32_t)kp.W);
+    const int iy = sharded ? kp.cand_rows[cand] : cand;
+    const size_t at = ((size_t)s * kp.H + iy) * kp.W + ix;
+    const uint8_t code = src.codes[at];
+    const int yn = kp.plane == kPlaneGui ? gui_nominal_row(iy, kp.H) : nominal_row(iy, kp.H);
+    const int xi = ix + (code & 3) - 1, yi = yn + ((code >> 2) & 3) - 1;
+    if (code != 0x05) {
+        kp.flags[(size_t)yn * kp.W + ix] = 1;
+        kp.flags[(size_t)yi * kp.W + xi] = 1;
+    }
+    const bool mine = owned_row(kp, yi);
+    kp.values[unit] = mine ? src.values[at] : 0.0f;
+    kp.codes[unit] = mine ? code : (uint8_t)0xfe;
+}
+
 // ----------------------------------------------------------- math probes
 // Division pairs for the fast-division proof (fn 9): every 32-bit pattern b
 // maps to a numerator with b's sign and mantissa and a biased exponent in
@@ -3317,10 +3352,15 @@ int launch_preview(ipt_ctx* ctx, const KParams& kp, const PreviewOut& po, hipStr
 
 // preview: ray_power_preview's launches (IPT_FLAG_PREVIEW, or forced by
 // ipt_preview_values, whose host_kinds / host_hits may each be null)
+// replay: ipt_replay_samples' source, the caller's samples of the call's passes
+// [spp][H][W] on the device: replay_mark_kernel takes the place of the raygen
+// and path launches (no table, no raygen record, no tail gate, as a preview
+// launch), everything else is the call's as rendered
 int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t st,
                   float* host_values, uint8_t* host_codes, bool preview = false, uint8_t* host_kinds = nullptr,
-                  float* host_hits = nullptr) {
+                  float* host_hits = nullptr, const ReplaySrc* replay = nullptr) {
     preview = preview || (p->flags & IPT_FLAG_PREVIEW) != 0;
+    const bool traced = !preview && !replay;  // the full estimator's launches
     std::vector<int> rows, of_row;
     candidate_rows(p, rows, of_row);
     const int n_cand = (int)rows.size();
@@ -3340,14 +3380,14 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
     // (a preview unit is its value and code, 5 B, plus ipt_preview_values'
     // outputs; it has no raygen record and its launches read no table)
     constexpr size_t kRgBytes = 2 * sizeof(uint4);
-    const size_t unit_bytes = sizeof(float) + 1 + (preview ? (host_kinds ? 1 : 0) + (host_hits ? 6 * sizeof(float) : 0) : kRgBytes);
+    const size_t unit_bytes = sizeof(float) + 1 + (!traced ? (host_kinds ? 1 : 0) + (host_hits ? 6 * sizeof(float) : 0) : kRgBytes);
     size_t budget = (size_t)1 << 29;
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             size_t avail = free_b + (ctx->slot[0].work_cap + ctx->slot[1].work_cap) * (sizeof(float) + 1) +
-                           (preview ? 0 : (ctx->slot[0].rg_cap + ctx->slot[1].rg_cap) * kRgBytes);
-            const size_t tables = preview ? 0 :
+                           (!traced ? 0 : (ctx->slot[0].rg_cap + ctx->slot[1].rg_cap) * kRgBytes);
+            const size_t tables = !traced ? 0 :
                                   (ctx->d_cos_a ? 0 : ((size_t)3 << 26)) +
                                   (ctx->d_frame_sc || !frame_table_user(ctx->geometry_kind)
                                        ? 0 : kFrameTabEntries * sizeof(float2));
@@ -3362,13 +3402,13 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
     while (chunk > 1 && (size_t)chunk * per_pass > budget) --chunk;
     // (the preview reads neither table: a context that only renders previews
     // never builds them)
-    int rc = preview ? IPT_OK : ensure_cos_tables(ctx, st);
+    int rc = !traced ? IPT_OK : ensure_cos_tables(ctx, st);
     if (rc) return rc;
-    if (!preview && frame_table_user(ctx->geometry_kind)) {  // path_kernel's frame builds
+    if (traced && frame_table_user(ctx->geometry_kind)) {  // path_kernel's frame builds
         rc = ensure_frame_table(ctx, st);
         if (rc) return rc;
     }
-    const int susp = preview ? 0 : needed_susp(p);  // <= 8 (validate)
+    const int susp = !traced ? 0 : needed_susp(p);  // <= 8 (validate)
     const bool count = (p->flags & IPT_FLAG_COUNTERS) != 0;
     for (int s0 = 0; s0 < p->spp; s0 += chunk) {
         const int ns = std::min(chunk, p->spp - s0);
@@ -3379,7 +3419,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         WorkSlot& S = ctx->slot[ctx->next_slot];
         ctx->next_slot ^= 1u;
         const size_t elems = (size_t)chunk * per_pass;
-        const size_t rg_elems = preview ? 0 : elems, kinds_elems = host_kinds ? elems : 0, hits_elems = host_hits ? elems : 0;
+        const size_t rg_elems = !traced ? 0 : elems, kinds_elems = host_kinds ? elems : 0, hits_elems = host_hits ? elems : 0;
         const bool grow = elems > S.work_cap || (size_t)W * H > S.flags_cap || n_cand > S.cand_cap_rows ||
                           H > S.cand_cap_h || rg_elems > S.rg_cap || kinds_elems > S.kinds_cap ||
                           hits_elems > S.hits_cap;
@@ -3404,7 +3444,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         // (a preview launch has no tail to overlap and takes no gate; a preview
         // predecessor leaves P.seq at that of P's last full launch, which
         // precedes it in P's stream)
-        if (!preview && P.used && !P.idle) {
+        if (traced && P.used && !P.idle) {
             if (ctx->gate_on_pool)
                 HIPCHECK(ctx, hipStreamWaitValue64(S.st, P.d_drained, P.seq, hipStreamWaitValueGte, ~0ull));
             else
@@ -3535,7 +3575,11 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         HIPCHECK(ctx, hipMemsetAsync(S.d_unit, 0, sizeof(unsigned long long), ss));
         HIPCHECK(ctx, hipMemsetAsync(S.d_flags, 0, (size_t)W * H, ss));
         HIPCHECK(ctx, hipEventRecord(tm.t0, ss));
-        if (preview) {
+        if (replay) {
+            const ReplaySrc src{replay->values + (size_t)s0 * W * H, replay->codes + (size_t)s0 * W * H};
+            hipLaunchKernelGGL(replay_mark_kernel, dim3((unsigned)((kp.total_units + 255) / 256)), dim3(256), 0, ss, kp, src);
+            HIPCHECK(ctx, hipGetLastError());
+        } else if (preview) {
             // one fused kernel; the counting / AOV instance only where asked
             const PreviewOut po{host_kinds ? S.d_kinds : nullptr, host_hits ? S.d_hits : nullptr};
             rc = (count || po.kinds || po.hits) ? launch_preview<true>(ctx, kp, po, ss) : launch_preview<false>(ctx, kp, po, ss);
@@ -4197,6 +4241,60 @@ int ipt_preview_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t
     if (rc) return rc;
     if (rw) return rw;
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return IPT_OK;
+}
+
+int ipt_replay_samples(ipt_ctx* ctx, const ipt_params* p, const float* values, const uint8_t* codes,
+                       ipt_image* img, void* hip_stream) {
+    // everything is refused here, on the host, before a device buffer is
+    // touched: replay_mark_kernel writes flags at a code's destination
+    if (!ctx) return IPT_E_INVALID;
+    if (!p) return fail(ctx, IPT_E_INVALID, "params is NULL");
+    if (!values || !codes) return fail(ctx, IPT_E_INVALID, "values/codes are NULL");
+    if (!img || !img->pixels || !img->counters) return fail(ctx, IPT_E_INVALID, "image pixels/counters are NULL");
+    if (p->width <= 0 || p->height <= 0 || p->width > 65536 || p->height > 65536)
+        return fail(ctx, IPT_E_INVALID, "width/height out of range");
+    if (p->spp < 0) return fail(ctx, IPT_E_INVALID, "negative spp");
+    if (p->n_shards > 1 && (p->shard_id < 0 || p->shard_id >= p->n_shards))
+        return fail(ctx, IPT_E_INVALID, "shard_id out of range");
+    if (p->flags & ~(uint32_t)IPT_FLAG_GUI_PLANE)
+        return fail(ctx, IPT_E_UNSUPPORTED, "ipt_replay_samples takes IPT_FLAG_GUI_PLANE alone");
+    const int W = p->width, H = p->height;
+    const int64_t n = (int64_t)p->spp * W * H;  // (< 2^63: 2^31 * 2^16 * 2^16)
+    if (n > (int64_t)IPT_REPLAY_MAX_SAMPLES)
+        return fail(ctx, IPT_E_UNSUPPORTED, "more than IPT_REPLAY_MAX_SAMPLES samples in one call");
+    if (n == 0) return IPT_OK;
+    const bool gui = plane_of(p) == kPlaneGui;
+    for (int s = 0; s < p->spp; ++s)
+        for (int iy = 0; iy < H; ++iy) {
+            const int yn = gui ? ipt::gui_nominal_row(iy, H) : ipt::nominal_row(iy, H);
+            const uint8_t* row = codes + ((size_t)s * H + iy) * W;
+            for (int ix = 0; ix < W; ++ix) {
+                const uint8_t c = row[ix];
+                const int fx = c & 3, fy = (c >> 2) & 3;
+                if (c >= 0x10 || fx == 3 || fy == 3)
+                    return fail(ctx, IPT_E_INVALID, "not a drift code (0xfe and 0xff are the library's own)");
+                const int xi = ix + fx - 1, yi = yn + fy - 1;
+                if (xi < 0 || xi >= W || yi < 0 || yi >= H)
+                    return fail(ctx, IPT_E_INVALID, "a code's destination lies outside the frame");
+            }
+        }
+    hipSetDevice(ctx->device);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    DevBuf<float> dv;
+    DevBuf<uint8_t> dc;
+    HIPCHECK(ctx, hipMalloc(&dv.p, (size_t)n * sizeof(float)));
+    HIPCHECK(ctx, hipMalloc(&dc.p, (size_t)n));
+    HIPCHECK(ctx, hipMemcpy(dv.p, values, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHECK(ctx, hipMemcpy(dc.p, codes, (size_t)n, hipMemcpyHostToDevice));
+    const ReplaySrc src{dv.p, dc.p};
+    const int rc = render_chunks(ctx, p, img, st, nullptr, nullptr, false, nullptr, nullptr, &src);
+    // (nothing queued may still read the source when it is freed)
+    const int rw = drain(ctx);
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc) return rc;
+    if (rw) return rw;
+    HIPCHECK(ctx, e);
     return IPT_OK;
 }
 

@@ -69,7 +69,9 @@ ORDER_SENSITIVE = (0x0, 0x1, 0x2, 0x6)
 # +1) twice. 0x8 (dx = -1, dy = +1) turned up once in a codes-only scan of the
 # squares of side 2047, 2039, 2001, 1999, 1920 and 1531, passes 0..255, seeds
 # 20241223, 1, 2, 3 and 0xC0FFEE (2.9e10 samples: 0xa 93 times); 0x0 and 0x2
-# (dy = -1 with dx = -1 or +1) did not, and nothing in the suite reaches them.
+# (dy = -1 with dx = -1 or +1) did not: no render in the suite reaches them.
+# The replay probe does (ipt_replay_samples on tests/replay_cases.py's chosen
+# samples: every code, densely, and one code at a time).
 # Each case renders its one pass at the shallowest tree for which the oracle's
 # value at the diagonal sample is non-zero:
 # (code, side, seed, spp_offset, source ix, source iy, n_rays, depth_max, value)
@@ -79,7 +81,7 @@ DIAGONAL = (
     (0xa, 2048, DEFAULT_SEED, 90, 1596, 1361, 1, 2, 0.010200029239058495),
     (0x8, 1531, 1, 223, 817, 939, 2, 2, 0.3901532292366028),
 )
-DIAGONAL_UNREACHED = (0x0, 0x2)
+DIAGONAL_UNREACHED = (0x0, 0x2)  # by a render; replay_cases.DIAG_DOWN reaches them
 
 # sharded plans (tile_rows, n_shards) and the passes each is rendered with.
 # CROSS pins the drifted samples whose nominal and actual destination rows
@@ -223,20 +225,21 @@ SMALL_SPPS = (7, 8, 9, 16, 17)
 BIG_MAX = np.float32(1e30)  # above every running mean of the box scene
 
 
-def preload_kinds(spp):
+def preload_kinds(spp, per_pass=3):
     """The preloaded values by array. The last counter leaves room for three
     samples per pass (a pixel's nominal one, row 0's second one, a drifted
     one; test_drift_cpu.py checks the frames' own maxima) below the uint32
-    wrap (ipt_capi.h, ipt_image)."""
+    wrap (ipt_capi.h, ipt_image); per_pass: for more than three
+    (replay_cases.py's injected samples)."""
     return {
-        "counters": (0, 1, 2 ** 24 - 1, 2 ** 24, 2 ** 24 + 1, 2 ** 31, 0xfffffffe - spp * 3),
+        "counters": (0, 1, 2 ** 24 - 1, 2 ** 24, 2 ** 24 + 1, 2 ** 31, 0xfffffffe - spp * per_pass),
         "pixels": ("random", "negative", "-0", "subnormal", "+inf", "nan"),
         "pixel_max": ("zero", "big", "-1", "nan"),
         "sums": ("random", "+inf"),
     }
 
 
-def preload(W, H, spp, hot=None, seed=7):
+def preload(W, H, spp, hot=None, seed=7, per_pass=3):
     """(plane, kind index per pixel and array): a seeded mix of
     preload_kinds(spp). `hot` (pixel indices, e.g. the destinations of the
     drifted samples) count through the kinds of the four arrays as the digits
@@ -249,7 +252,7 @@ def preload(W, H, spp, hot=None, seed=7):
     only propagates its operands."""
     rng = np.random.default_rng(seed)
     n = W * H
-    kinds = preload_kinds(spp)
+    kinds = preload_kinds(spp, per_pass)
     pick = {k: rng.integers(0, len(v), n) for k, v in kinds.items()}
     if hot is not None:
         hot = np.unique(hot)

@@ -67,7 +67,18 @@ def test_diagonal_sample(oracle, case):
 
 
 def test_diagonal_codes_accounted_for():
+    """0x0 and 0x2 are still unreached by a render; the replay probe's cases
+    (tests/replay_cases.py) reach them, and every other drift code."""
+    import replay_cases as rc
+
     assert {c[0] for c in dc.DIAGONAL} | set(dc.DIAGONAL_UNREACHED) == {0x0, 0x2, 0x8, 0xa}
+    assert not {c[0] for c in dc.DIAGONAL} & set(dc.DIAGONAL_UNREACHED)
+    assert set(rc.DIAG_DOWN) == set(dc.DIAGONAL_UNREACHED)
+    assert set(rc.DRIFT_CODES) == {dx | dy << 2 for dx in range(3) for dy in range(3)} - {0x05}
+    for plane in rc.PLANES:
+        for code in dc.DIAGONAL_UNREACHED:
+            _, c = rc.single_code(code, *rc.SINGLE_FRAME, rc.SINGLE_SPP, plane)
+            assert int((c == code).sum()) >= c.size // 3
 
 
 @pytest.mark.parametrize("frame", dc.THIN + (dc.SMALL,), ids=lambda f: "%dx%d" % f)
