@@ -12,7 +12,8 @@
  * Conventions: plain pointers and sizes, no exceptions, every call returns
  * IPT_OK (0) or a negative IPT_E_* code, the message of the last failure is
  * available from ipt_last_error(). Calls are synchronous unless they take a
- * stream argument and say otherwise (ipt_render_device_async, ipt_display_device,
+ * stream argument and say otherwise (ipt_render_device_async,
+ * ipt_render_masked_device_async, ipt_adapt_device, ipt_display_device,
  * ipt_display_stats_device, ipt_smooth_device and ipt_pgm_device return once
  * their work is queued). One context per HIP device; contexts are independent, a
  * single context is not reentrant. There is NO CPU fallback: without a usable
@@ -300,6 +301,97 @@ int ipt_render_device(ipt_ctx* ctx, const ipt_params* p, ipt_image* dev_img, voi
    ROCPROF_ADVANCED_THREAD_TRACE), or with IPT_NO_TAIL_OVERLAP=1, a launch
    waits for its predecessor's end instead (same images). */
 int ipt_render_device_async(ipt_ctx* ctx, const ipt_params* p, ipt_image* dev_img, void* hip_stream);
+/* ---- adaptive sampling (ABI 7 additions) ---------------------------------------
+   Masked renders, a second-moment plane and the kernel that turns both into
+   the next mask, so that a progressive loop stops spending paths where the
+   picture has converged (entry points and one struct added; no layout change).
+   Without a mask and without an m2 plane every launch is
+   ipt_render_device_async's.
+
+   ipt_render_masked_device_async: ipt_render_device_async with
+     dev_mask  [H][W] bytes, may be NULL (all active). Indexed by a sample's
+               NOMINAL destination pixel (ix, yn), yn = max(H-2-iy, 0), or
+               H-1-iy with IPT_FLAG_GUI_PLANE; under the Grid map mask[0][ix]
+               therefore governs source rows H-2 and H-1 alike. Byte 0: the
+               source sample is not traced (value 0, code 0xfe, no drift flag,
+               counted neither in ipt_counters.paths nor .drifted). Any other
+               byte: the sample is exactly the unmasked render's -- the pass
+               index stays spp_offset + s whatever the mask. A traced sample
+               that drifts is added where it lands, whatever the mask says
+               there, as addRay would. Always the whole frame, also with
+               n_shards > 1.
+     dev_m2    [H][W] floats, may be NULL: the caller-owned second-moment
+               plane, zero-initialised together with the image. For every
+               sample v the replay adds to a pixel, in the replay's order, in
+               f32 and with no contraction:
+                 p_old = pixel;  addRay (unchanged);
+                 m2 += (v - p_old) * (v - p_new)      (sub, sub, mul, add)
+   The path kernel is untouched: a masked sample is a work unit that raygen
+   marks invalid and the path kernel drops at its refill; nothing is compacted.
+   Ordering: raygen reads the mask, caller memory, so before its first launch
+   on each work-slot stream the call makes that stream wait for `hip_stream`
+   as it stands at the call; the mask may be overwritten by work queued on
+   `hip_stream` after the call. A masked call thereby gives up the tail overlap
+   with what is queued before it on that stream (its launches start after it,
+   not in its predecessor's tail); calls without a mask take no new wait.
+   Composes with IPT_FLAG_GUI_PLANE, IPT_FLAG_PREVIEW, IPT_FLAG_COUNTERS,
+   sharding, preloaded planes, sums / pixel_max NULL or not, chunked launches
+   and queued mixes with unmasked calls. Validation is ipt_render_device_async's,
+   plus: the mask or m2 sharing a byte with an image buffer or with each
+   other: IPT_E_INVALID, before anything is launched. */
+int ipt_render_masked_device_async(ipt_ctx* ctx, const ipt_params* p, ipt_image* dev_img,
+                                   const uint8_t* dev_mask /* [H][W], may be NULL */,
+                                   float* dev_m2 /* [H][W], may be NULL */, void* hip_stream);
+/* The same, synchronous (as ipt_render_device). */
+int ipt_render_masked_device(ipt_ctx* ctx, const ipt_params* p, ipt_image* dev_img, const uint8_t* dev_mask,
+                             float* dev_m2, void* hip_stream);
+
+/* ipt_adapt_device: the next mask. Per pixel d, in f32, operation for operation:
+     c = counters[d]
+     if (c < min_count)  active, class "starved" (counted in active as well)
+     else nf = (float)c;  e2 = m2[d] / (nf * (nf - 1.0f));
+          thr = rel_tol * fabsf(pixels[d]) + abs_tol;  t2 = thr * thr;
+          active = e2 > t2;     a NaN on either side: inactive, class "nan"
+     mask[d] = active ? 1 : 0
+   e2 is the squared standard error of the mean. Pixels without a nominal
+   source -- under the Grid map with H >= 2, row H-1 -- get mask 0 and are
+   counted in no class (a loop that ends on "no active pixel" would otherwise
+   never end); with IPT_FLAG_GUI_PLANE in `flags` there is no such row.
+   dev_stats (4 uint32, may be NULL) = {active, starved, nan, 0}: integer sums,
+   deterministic; the call zeroes them itself, in stream order.
+   Stream and wait rules are ipt_display_device's: queued on `hip_stream` (NULL
+   = the context's stream), no value crosses to the host, a call on another
+   stream waits on the previous display / adapt call's event, ipt_render_wait,
+   ipt_upload_scene and ipt_destroy wait for it. No scratch.
+   Errors, all raised before a buffer is written: a NULL that is not optional,
+   a non-positive size, min_count < 2, a negative or NaN tolerance, an output
+   overlapping an input or the other output: IPT_E_INVALID; flags other than
+   IPT_FLAG_GUI_PLANE or more than 2^31 pixels: IPT_E_UNSUPPORTED. */
+typedef struct ipt_adapt_params {
+    int32_t width, height;
+    uint32_t min_count; /* >= 2: pixels with fewer samples stay active */
+    float rel_tol, abs_tol;
+    uint32_t flags;     /* 0 or IPT_FLAG_GUI_PLANE: the plane's row map */
+} ipt_adapt_params;
+int ipt_adapt_device(ipt_ctx* ctx, const ipt_adapt_params* ap, const float* dev_pixels,
+                     const uint32_t* dev_counters, const float* dev_m2, uint8_t* dev_mask,
+                     uint32_t* dev_stats /* 4, may be NULL */, void* hip_stream);
+
+/* The loop on host buffers, synchronous, whole frame: renders up to p->spp
+   passes (from p->spp_offset) in rounds of round_spp, round 0 unmasked, each
+   round followed by ipt_adapt_device; reads the 16 B of stats after each round
+   and stops when active == 0 or the passes are used up. host_img is continued
+   as ipt_render continues it (zero-initialise before the first call); host_m2
+   (may be NULL: zeros in, not returned) likewise; host_mask (may be NULL) gets
+   the last mask. stats = {active, starved, nan} of the last round and, in
+   stats[3], the passes used. ap's size and IPT_FLAG_GUI_PLANE must be p's:
+   IPT_E_INVALID otherwise, as for a NULL ap / host_img / stats or round_spp
+   < 1. p->n_shards > 1: IPT_E_UNSUPPORTED -- multi-GPU adaptive rendering
+   (a mask per shard, agreed between devices) is out of scope here; a sharded
+   caller drives ipt_render_masked_device_async and ipt_adapt_device itself. */
+int ipt_render_adaptive(ipt_ctx* ctx, const ipt_params* p, const ipt_adapt_params* ap, int32_t round_spp,
+                        ipt_image* host_img, float* host_m2, uint8_t* host_mask, uint32_t* stats);
+
 /* Waits for every queued render; ipt_last_kernel_ms then holds the times of
    the launches since the previous wait (a synchronous render call waits). */
 int ipt_render_wait(ipt_ctx* ctx);

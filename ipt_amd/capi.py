@@ -87,6 +87,11 @@ class PgmParams(C.Structure):  # ABI 7 additions
                 ("contrast", C.c_float), ("gamma", C.c_float), ("max_value", C.c_float), ("flags", C.c_uint32)]
 
 
+class AdaptParams(C.Structure):  # ABI 7 additions (adaptive sampling)
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("min_count", C.c_uint32),
+                ("rel_tol", C.c_float), ("abs_tol", C.c_float), ("flags", C.c_uint32)]
+
+
 ABI_VERSION = 7  # include/ipt_capi.h IPT_ABI_VERSION
 ABI_LAYOUT_COMPATIBLE = (3, 4, 5, 6, 7)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
 
@@ -113,6 +118,7 @@ EXPORTED_SYMBOLS = (
     "ipt_display_stats_device", "ipt_display_stats",
     "ipt_smooth_device", "ipt_pgm_device", "ipt_pgm", "ipt_logf_host", "ipt_logf_device",
     "ipt_preview_values", "ipt_replay_samples",
+    "ipt_render_masked_device_async", "ipt_render_masked_device", "ipt_adapt_device", "ipt_render_adaptive",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -202,6 +208,13 @@ def load(path: str | os.PathLike | None = None):
     if hasattr(lib, "ipt_replay_samples"):  # ABI 7 addition
         lib.ipt_replay_samples.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Image),
                                            C.c_void_p]
+    if hasattr(lib, "ipt_adapt_device"):  # ABI 7 additions (adaptive sampling)
+        lib.ipt_render_masked_device_async.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Image), C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]
+        lib.ipt_render_masked_device.argtypes = lib.ipt_render_masked_device_async.argtypes
+        lib.ipt_adapt_device.argtypes = [C.c_void_p, C.POINTER(AdaptParams)] + [C.c_void_p] * 6
+        lib.ipt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptParams), C.c_int32,
+                                            C.POINTER(Image), C.c_void_p, C.c_void_p, C.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -271,6 +284,14 @@ def make_pgm_params(width, height, smooth_side=0, max_side=0, contrast=500.0, ga
     p = PgmParams()
     p.width, p.height, p.smooth_side, p.max_side = width, height, smooth_side, max_side
     p.contrast, p.gamma, p.max_value, p.flags = contrast, gamma, max_value, flags
+    return p
+
+
+def make_adapt_params(width, height, min_count=8, rel_tol=0.05, abs_tol=1e-3, flags=0) -> AdaptParams:
+    """ipt_adapt_device's parameters; flags: 0 or IPT_FLAG_GUI_PLANE (the plane's row map)."""
+    p = AdaptParams()
+    p.width, p.height, p.min_count, p.flags = width, height, min_count, flags
+    p.rel_tol, p.abs_tol = rel_tol, abs_tol
     return p
 
 
@@ -376,6 +397,47 @@ class Context:
         _check(self.lib, self.h, self.lib.ipt_replay_samples(
             self.h, C.byref(p), None if v is None else v.ctypes.data, None if c is None else c.ctypes.data,
             C.byref(im), stream))
+
+    def render_masked_device(self, p: Params, pixels_ptr, counters_ptr, sums_ptr=None, max_ptr=None,
+                             mask_ptr=None, m2_ptr=None, stream=None):
+        """ipt_render_masked_device: render_device with a per-pixel sample mask
+        (uint8 [H][W] by nominal destination, None = all active) and a
+        second-moment plane (float32 [H][W], None = not kept)."""
+        im = Image()
+        im.pixels, im.counters, im.sums, im.pixel_max = pixels_ptr, counters_ptr, sums_ptr, max_ptr
+        _check(self.lib, self.h, self.lib.ipt_render_masked_device(self.h, C.byref(p), C.byref(im), mask_ptr, m2_ptr,
+                                                                   stream))
+
+    def render_masked_device_async(self, p: Params, pixels_ptr, counters_ptr, sums_ptr=None, max_ptr=None,
+                                   mask_ptr=None, m2_ptr=None, stream=None):
+        """Queue the masked render (ipt_render_masked_device_async); complete on
+        `stream`'s order or after wait()."""
+        im = Image()
+        im.pixels, im.counters, im.sums, im.pixel_max = pixels_ptr, counters_ptr, sums_ptr, max_ptr
+        _check(self.lib, self.h, self.lib.ipt_render_masked_device_async(self.h, C.byref(p), C.byref(im), mask_ptr,
+                                                                         m2_ptr, stream))
+
+    def adapt_device(self, ap: AdaptParams, pixels_ptr, counters_ptr, m2_ptr, mask_ptr, stats_ptr=None, stream=None):
+        """Queue ipt_adapt_device: the next mask (uint8 at mask_ptr) from the
+        plane, and {active, starved, nan, 0} (uint32) at stats_ptr."""
+        _check(self.lib, self.h, self.lib.ipt_adapt_device(self.h, C.byref(ap), pixels_ptr, counters_ptr, m2_ptr,
+                                                           mask_ptr, stats_ptr, stream))
+
+    def render_adaptive(self, p: Params, ap: AdaptParams, round_spp: int, img: dict, m2=None, mask=None):
+        """The adaptive loop on host buffers (ipt_render_adaptive): up to p.spp
+        passes in rounds of round_spp into img = {pixels, counters, sums?,
+        pixel_max?}; m2 (float32) and mask (uint8) numpy arrays or None.
+        Returns {active, starved, nan, passes}."""
+        im = Image()
+        im.pixels = img["pixels"].ctypes.data
+        im.counters = img["counters"].ctypes.data
+        im.sums = img["sums"].ctypes.data if img.get("sums") is not None else None
+        im.pixel_max = img["pixel_max"].ctypes.data if img.get("pixel_max") is not None else None
+        st = np.zeros(4, np.uint32)
+        _check(self.lib, self.h, self.lib.ipt_render_adaptive(
+            self.h, C.byref(p), C.byref(ap), round_spp, C.byref(im), None if m2 is None else m2.ctypes.data,
+            None if mask is None else mask.ctypes.data, st.ctypes.data))
+        return {"active": int(st[0]), "starved": int(st[1]), "nan": int(st[2]), "passes": int(st[3])}
 
     def wait(self):
         _check(self.lib, self.h, self.lib.ipt_render_wait(self.h))

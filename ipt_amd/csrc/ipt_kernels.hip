@@ -15,7 +15,10 @@
 //                      all passes in render_sample order — coalesced reads of
 //                      the radiance buffer, HBM-bound. Its kPlaneGui instance
 //                      replays Gui::addRay's row map instead (gui.cpp:165-182,
-//                      IPT_FLAG_GUI_PLANE).
+//                      IPT_FLAG_GUI_PLANE). Its ADAPT instances serve masked
+//                      renders (ipt_render_masked_device): pixels the mask
+//                      switched off are left alone and every added sample
+//                      updates the second-moment plane m2.
 // Build: see __graft_entry__.py (hipcc --offload-arch=gfx950 -O3
 //        -ffp-contract=off, no fast-math).
 #include <hip/hip_runtime.h>
@@ -160,6 +163,10 @@ struct KParams {
     const uint4* __restrict__ rg;         // [total_units][2] raygen_kernel records
     int count;                            // raygen_kernel: accumulate the drift counter
     int plane;                            // new_path_setup: kPlaneGrid / kPlaneGui (IPT_FLAG_GUI_PLANE)
+    // new_path_setup: the caller's sample mask [H][W] by nominal destination
+    // pixel, or null (ipt_render_masked_device). Appended: no other field moves,
+    // and path_kernel, which never reads it, keeps its instructions
+    const uint8_t* __restrict__ mask;
 };
 // The render plane's index map: GridRenderPlane::addRay's or Gui::addRay's.
 enum { kPlaneGrid = 0, kPlaneGui = 1 };
@@ -875,17 +882,21 @@ __device__ __forceinline__ RayGen new_path_setup(const KParams& kp, unsigned lon
     uint8_t code = 0xff;
     if (dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1 && xi < kp.W && yi < kp.H)
         code = (uint8_t)((dx + 1) | ((dy + 1) << 2));
-    g.drift = code != 0x05 && code != 0xff;
+    // the caller's mask, by the sample's nominal destination (ix, yn): byte 0
+    // means the sample is not traced -- no flags, no drift count, value 0 and
+    // code 0xfe, which the replay's code-checking branch skips
+    const bool masked = kp.mask && kp.mask[(size_t)yn * kp.W + ix] == 0;
+    g.drift = code != 0x05 && code != 0xff && !masked;
     if (g.drift) {
         kp.flags[(size_t)yn * kp.W + ix] = 1;
         kp.flags[(size_t)yi * kp.W + xi] = 1;
     }
-    g.valid = !(code == 0xff || !owned_row(kp, yi));
+    g.valid = !(code == 0xff || masked || !owned_row(kp, yi));
     g.rd = v3(0, 0, 0);
     if (!g.valid) {
-        // not ours (halo row of another shard) or out of range
+        // not ours (halo row of another shard), out of range or masked
         kp.values[unit] = 0.0f;
-        kp.codes[unit] = code == 0xff ? code : (uint8_t)0xfe;
+        kp.codes[unit] = (code == 0xff && !masked) ? code : (uint8_t)0xfe;
     } else {
         kp.codes[unit] = code;
         g.rd = camera_dir(kp.cam_right, kp.cam_up, kp.cam_dir, x, y);
@@ -2293,6 +2304,17 @@ struct AParams {
     // wall clock (atomic min / max; the host presets them), for its duration
     unsigned long long* clk;
 };
+// The ADAPT instances' parameters (ipt_render_masked_device): AParams and,
+// appended after clk, the caller's mask [H][W] and second-moment plane [H][W],
+// either may be null. A type of its own, so that the unmasked instances keep
+// AParams' size and with it the offsets of the kernel's hidden arguments: they
+// stay the parent's instruction for instruction, immediates included.
+struct AParamsAdapt : AParams {
+    const uint8_t* mask;
+    float* m2;
+};
+template <bool ADAPT>
+using AParamsOf = std::conditional_t<ADAPT, AParamsAdapt, AParams>;
 
 __device__ __forceinline__ void add_ray(float v, float& p, uint32_t& c, float& s, float& m) {
     // GridRenderPlane::addRay (GridRenderPlane.cpp:68-73)
@@ -2302,24 +2324,47 @@ __device__ __forceinline__ void add_ray(float v, float& p, uint32_t& c, float& s
     if (p > m) m = p;
 }
 
+// add_ray and, in the ADAPT instances, Welford's second moment of the sample
+// against the running mean before and after it: sub, sub, mul, add in f32
+template <bool ADAPT>
+__device__ __forceinline__ void add_ray_m2(float v, float& p, uint32_t& c, float& s, float& m, float& m2) {
+    if (ADAPT) {
+        const float p_old = p;
+        add_ray(v, p, c, s, m);
+        m2 += (v - p_old) * (v - p);
+    } else {
+        add_ray(v, p, c, s, m);
+    }
+}
+
 // PLANE: kPlaneGrid replays GridRenderPlane::addRay's row map (source rows
 // H-2 and H-1 both land in row 0), kPlaneGui Gui::addRay's (source row s lands
 // in row H-1-s); the running mean is the same.
-template <int PLANE>
-__device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int yi);
-template <int PLANE>
-__global__ __launch_bounds__(256) void accumulate_kernel(AParams ap) {
+// ADAPT (a launch with a mask or an m2 plane): a pixel without a flag whose
+// mask byte is 0 has no sample this launch and returns at once (the unflagged
+// branches read `values` without looking at codes and would add the 0 stored
+// for a masked sample); every added sample also updates m2. The ADAPT = false
+// instances are the unmasked replay, instruction for instruction.
+template <int PLANE, bool ADAPT>
+__device__ __forceinline__ void accumulate_pixel(const AParamsOf<ADAPT>& ap, int xi, int yi);
+template <int PLANE, bool ADAPT>
+__global__ __launch_bounds__(256) void accumulate_kernel(AParamsOf<ADAPT> ap) {
     const int xi = blockIdx.x * blockDim.x + threadIdx.x;
     const int yi = blockIdx.y;
     if (threadIdx.x == 0) atomicMin(&ap.clk[0], (unsigned long long)wall_clock64());
     if (xi < ap.W && (ap.n_shards <= 1 || ap.tile_rows <= 0 || ((yi / ap.tile_rows) % ap.n_shards) == ap.shard_id))
-        accumulate_pixel<PLANE>(ap, xi, yi);
+        accumulate_pixel<PLANE, ADAPT>(ap, xi, yi);
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(&ap.clk[1], (unsigned long long)wall_clock64());
 }
-template <int PLANE>
-__device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int yi) {
+template <int PLANE, bool ADAPT>
+__device__ __forceinline__ void accumulate_pixel(const AParamsOf<ADAPT>& ap, int xi, int yi) {
     const size_t d = (size_t)yi * ap.W + xi;
+    float m2 = 0.0f;
+    if constexpr (ADAPT) {
+        if (ap.mask && ap.flags[d] == 0 && ap.mask[d] == 0) return;
+        if (ap.m2) m2 = ap.m2[d];
+    }
     float p = ap.pixels[d];
     uint32_t c = ap.counters[d];
     float s = ap.sums ? ap.sums[d] : 0.0f;
@@ -2338,9 +2383,9 @@ __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int 
 #pragma unroll
                 for (int q = 0; q < 8; ++q) a0[q] = v0p[(size_t)(sp + q) * pass_stride];
 #pragma unroll
-                for (int q = 0; q < 8; ++q) add_ray(a0[q], p, c, s, m);
+                for (int q = 0; q < 8; ++q) add_ray_m2<ADAPT>(a0[q], p, c, s, m, m2);
             }
-            for (; sp < ap.spp; ++sp) add_ray(v0p[(size_t)sp * pass_stride], p, c, s, m);
+            for (; sp < ap.spp; ++sp) add_ray_m2<ADAPT>(v0p[(size_t)sp * pass_stride], p, c, s, m, m2);
         }
     } else if (PLANE == kPlaneGui) {
         // source rows whose nominal row H-1-iy is yi+1, yi, yi-1: ascending
@@ -2359,7 +2404,7 @@ __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int 
                     const uint8_t code = ap.codes[idx];
                     if (code >= 0x10) continue;
                     const int dx = (code & 3) - 1, dy = ((code >> 2) & 3) - 1;
-                    if (ix + dx == xi && yn + dy == yi) add_ray(ap.values[idx], p, c, s, m);
+                    if (ix + dx == xi && yn + dy == yi) add_ray_m2<ADAPT>(ap.values[idx], p, c, s, m, m2);
                 }
             }
         }
@@ -2385,14 +2430,14 @@ __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int 
             }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                if (t0) add_ray(a0[q], p, c, s, m);
-                if (t1) add_ray(a1[q], p, c, s, m);
+                if (t0) add_ray_m2<ADAPT>(a0[q], p, c, s, m, m2);
+                if (t1) add_ray_m2<ADAPT>(a1[q], p, c, s, m, m2);
             }
         }
         for (; sp < ap.spp; ++sp) {
             const size_t base = (size_t)sp * pass_stride;
-            if (t0) add_ray(v0p[base], p, c, s, m);
-            if (t1) add_ray(v1p[base], p, c, s, m);
+            if (t0) add_ray_m2<ADAPT>(v0p[base], p, c, s, m, m2);
+            if (t1) add_ray_m2<ADAPT>(v1p[base], p, c, s, m, m2);
         }
     } else {
         int rows[4];
@@ -2422,7 +2467,7 @@ __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int 
                     const uint8_t code = ap.codes[idx];
                     if (code >= 0x10) continue;
                     const int dx = (code & 3) - 1, dy = ((code >> 2) & 3) - 1;
-                    if (ix + dx == xi && yn + dy == yi) add_ray(ap.values[idx], p, c, s, m);
+                    if (ix + dx == xi && yn + dy == yi) add_ray_m2<ADAPT>(ap.values[idx], p, c, s, m, m2);
                 }
             }
         }
@@ -2431,6 +2476,9 @@ __device__ __forceinline__ void accumulate_pixel(const AParams& ap, int xi, int 
     ap.counters[d] = c;
     if (ap.sums) ap.sums[d] = s;
     if (ap.pixel_max) ap.pixel_max[d] = m;
+    if constexpr (ADAPT) {
+        if (ap.m2) ap.m2[d] = m2;
+    }
 }
 
 // ipt_replay_samples' sample source: the caller's whole-frame samples
@@ -2827,6 +2875,7 @@ struct WorkSlot {
     hipStream_t st = nullptr;
     hipEvent_t done = nullptr;  // after the last reader of the slot's buffers (accumulate or host copies)
     hipEvent_t path_end = nullptr;  // after its last path kernel
+    hipEvent_t mask_ready = nullptr;  // a masked call's point on the caller's stream (created on first use)
     unsigned long long total = 0;   // work units of its last launch
     bool used = false;
     bool idle = true;  // its last launch is known complete (a drain since): nothing to wait for
@@ -2838,6 +2887,11 @@ static unsigned long long* g_raylog_n = nullptr;
 static unsigned long long g_raylog_cap = 0;
 static unsigned g_raylog_every = 1;
 #endif
+
+struct AdaptArgs {
+    const uint8_t* mask;  // [H][W] or null
+    float* m2;            // [H][W] or null
+};
 
 struct ChunkTiming {
     hipEvent_t t0 = nullptr, t1 = nullptr;  // raygen start, path-kernel end (slot stream)
@@ -3352,13 +3406,17 @@ int launch_preview(ipt_ctx* ctx, const KParams& kp, const PreviewOut& po, hipStr
 
 // preview: ray_power_preview's launches (IPT_FLAG_PREVIEW, or forced by
 // ipt_preview_values, whose host_kinds / host_hits may each be null)
+// adapt: ipt_render_masked_device's mask and m2 plane (either may be null):
+// raygen / the preview kernel read the mask, the replay's ADAPT instance runs;
+// with a mask, each slot stream the call uses first waits for the caller's
+// stream as it stands at the call (the mask is caller memory, written there)
 // replay: ipt_replay_samples' source, the caller's samples of the call's passes
 // [spp][H][W] on the device: replay_mark_kernel takes the place of the raygen
 // and path launches (no table, no raygen record, no tail gate, as a preview
 // launch), everything else is the call's as rendered
 int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t st,
                   float* host_values, uint8_t* host_codes, bool preview = false, uint8_t* host_kinds = nullptr,
-                  float* host_hits = nullptr, const ReplaySrc* replay = nullptr) {
+                  float* host_hits = nullptr, const ReplaySrc* replay = nullptr, const AdaptArgs* adapt = nullptr) {
     preview = preview || (p->flags & IPT_FLAG_PREVIEW) != 0;
     const bool traced = !preview && !replay;  // the full estimator's launches
     std::vector<int> rows, of_row;
@@ -3410,6 +3468,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
     }
     const int susp = !traced ? 0 : needed_susp(p);  // <= 8 (validate)
     const bool count = (p->flags & IPT_FLAG_COUNTERS) != 0;
+    bool mask_waited[2] = {false, false};
     for (int s0 = 0; s0 < p->spp; s0 += chunk) {
         const int ns = std::min(chunk, p->spp - s0);
         // this launch's slot; its previous launch and that launch's readers
@@ -3563,6 +3622,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         kp.rg = S.d_rg;
         kp.count = count ? 1 : 0;
         kp.plane = plane_of(p);
+        kp.mask = adapt ? adapt->mask : nullptr;
         // the slot stream: t0..t1 is the path's per-sample work, raygen_kernel
         // (render_sample's jitter, camera ray, Philox block 0; ~0.2 % of a C2
         // launch) and path_kernel
@@ -3572,6 +3632,14 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         S.used = true;
         S.idle = false;
         S.total = 0;  // (until its kernel is queued: a successor must not wait on a launch that failed)
+        if (kp.mask && !mask_waited[sidx]) {
+            // raygen reads caller memory: this slot stream's launches of the
+            // call run after what the caller's stream holds at the call
+            if (!S.mask_ready) HIPCHECK(ctx, hipEventCreateWithFlags(&S.mask_ready, hipEventDisableTiming));
+            HIPCHECK(ctx, hipEventRecord(S.mask_ready, st));
+            HIPCHECK(ctx, hipStreamWaitEvent(ss, S.mask_ready, 0));
+            mask_waited[sidx] = true;
+        }
         HIPCHECK(ctx, hipMemsetAsync(S.d_unit, 0, sizeof(unsigned long long), ss));
         HIPCHECK(ctx, hipMemsetAsync(S.d_flags, 0, (size_t)W * H, ss));
         HIPCHECK(ctx, hipEventRecord(tm.t0, ss));
@@ -3636,10 +3704,19 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             ap.pixel_max = img->pixel_max;
             ap.clk = clk ? clk : ctx->d_clk_dummy;
             dim3 grid((W + 255) / 256, H), block(256);
-            if (kp.plane == kPlaneGui)
-                hipLaunchKernelGGL(accumulate_kernel<kPlaneGui>, grid, block, 0, st, ap);
+            if (adapt) {
+                AParamsAdapt aa{};
+                static_cast<AParams&>(aa) = ap;
+                aa.mask = adapt->mask;
+                aa.m2 = adapt->m2;
+                if (kp.plane == kPlaneGui)
+                    hipLaunchKernelGGL((accumulate_kernel<kPlaneGui, true>), grid, block, 0, st, aa);
+                else
+                    hipLaunchKernelGGL((accumulate_kernel<kPlaneGrid, true>), grid, block, 0, st, aa);
+            } else if (kp.plane == kPlaneGui)
+                hipLaunchKernelGGL((accumulate_kernel<kPlaneGui, false>), grid, block, 0, st, ap);
             else
-                hipLaunchKernelGGL(accumulate_kernel<kPlaneGrid>, grid, block, 0, st, ap);
+                hipLaunchKernelGGL((accumulate_kernel<kPlaneGrid, false>), grid, block, 0, st, ap);
             HIPCHECK(ctx, hipGetLastError());
             HIPCHECK(ctx, hipEventRecord(tm.a1, st));
             HIPCHECK(ctx, hipEventRecord(S.done, st));
@@ -3796,6 +3873,7 @@ void ipt_destroy(ipt_ctx* ctx) {
             if (b) hipFree(b);
         if (S.done) hipEventDestroy(S.done);
         if (S.path_end) hipEventDestroy(S.path_end);
+        if (S.mask_ready) hipEventDestroy(S.mask_ready);
         if (S.st) hipStreamDestroy(S.st);
     }
     for (hipEvent_t e : ctx->ev_pool) hipEventDestroy(e);
@@ -4102,6 +4180,102 @@ int ipt_render_device_async(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, v
     hipSetDevice(ctx->device);
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     return render_chunks(ctx, p, img, st, nullptr, nullptr);
+}
+
+int ipt_render_masked_device_async(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, const uint8_t* dev_mask,
+                                   float* dev_m2, void* hip_stream) {
+    int rc = validate(ctx, p);
+    if (rc) return rc;
+    if (!img || !img->pixels || !img->counters) return fail(ctx, IPT_E_INVALID, "image pixels/counters are NULL");
+    {
+        // the mask and m2 may not share a byte with an image buffer (or each other)
+        const size_t n = (size_t)p->width * p->height;
+        const void* buf[6] = {dev_mask, dev_m2, img->pixels, img->counters, img->sums, img->pixel_max};
+        const size_t len[6] = {n, n * 4, n * 4, n * 4, n * 4, n * 4};
+        for (int a = 0; a < 2; ++a)
+            for (int b = a + 1; b < 6; ++b) {
+                const uintptr_t x = (uintptr_t)buf[a], y = (uintptr_t)buf[b];
+                if (buf[a] && buf[b] && x < y + len[b] && y < x + len[a])
+                    return fail(ctx, IPT_E_INVALID, "ipt_render_masked_device: the mask or m2 overlaps another buffer");
+            }
+    }
+    hipSetDevice(ctx->device);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    if (!dev_mask && !dev_m2) return render_chunks(ctx, p, img, st, nullptr, nullptr);  // the unmasked launches
+    const AdaptArgs adapt{dev_mask, dev_m2};
+    return render_chunks(ctx, p, img, st, nullptr, nullptr, false, nullptr, nullptr, nullptr, &adapt);
+}
+
+int ipt_render_masked_device(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, const uint8_t* dev_mask, float* dev_m2,
+                             void* hip_stream) {
+    const int rc = ipt_render_masked_device_async(ctx, p, img, dev_mask, dev_m2, hip_stream);
+    const int rw = ctx ? drain(ctx) : IPT_OK;
+    return rc ? rc : rw;
+}
+
+int ipt_render_adaptive(ipt_ctx* ctx, const ipt_params* p, const ipt_adapt_params* ap, int32_t round_spp,
+                        ipt_image* himg, float* host_m2, uint8_t* host_mask, uint32_t* stats) {
+    int rc = validate(ctx, p);
+    if (rc) return rc;
+    if (!ap || !stats || round_spp < 1) return fail(ctx, IPT_E_INVALID, "ipt_render_adaptive: ap/stats NULL or round_spp < 1");
+    if (!himg || !himg->pixels || !himg->counters) return fail(ctx, IPT_E_INVALID, "image pixels/counters are NULL");
+    if (ap->width != p->width || ap->height != p->height ||
+        ((ap->flags ^ p->flags) & (uint32_t)IPT_FLAG_GUI_PLANE) != 0)
+        return fail(ctx, IPT_E_INVALID, "ipt_render_adaptive: ap's size and plane flag must be p's");
+    if (p->n_shards > 1) return fail(ctx, IPT_E_UNSUPPORTED, "ipt_render_adaptive renders whole frames on one device");
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t n = (size_t)p->width * p->height;
+    DevBuf<float> dpx, dsum, dmax, dm2;
+    DevBuf<uint32_t> dcnt, dstats;
+    DevBuf<uint8_t> dmask;
+    HIPCHECK(ctx, hipMalloc(&dpx.p, n * 4));
+    HIPCHECK(ctx, hipMalloc(&dcnt.p, n * 4));
+    if (himg->sums) HIPCHECK(ctx, hipMalloc(&dsum.p, n * 4));
+    if (himg->pixel_max) HIPCHECK(ctx, hipMalloc(&dmax.p, n * 4));
+    HIPCHECK(ctx, hipMalloc(&dm2.p, n * 4));
+    HIPCHECK(ctx, hipMalloc(&dmask.p, n));
+    HIPCHECK(ctx, hipMalloc(&dstats.p, 4 * sizeof(uint32_t)));
+    HIPCHECK(ctx, hipMemcpy(dpx.p, himg->pixels, n * 4, hipMemcpyHostToDevice));
+    HIPCHECK(ctx, hipMemcpy(dcnt.p, himg->counters, n * 4, hipMemcpyHostToDevice));
+    if (himg->sums) HIPCHECK(ctx, hipMemcpy(dsum.p, himg->sums, n * 4, hipMemcpyHostToDevice));
+    if (himg->pixel_max) HIPCHECK(ctx, hipMemcpy(dmax.p, himg->pixel_max, n * 4, hipMemcpyHostToDevice));
+    if (host_m2)
+        HIPCHECK(ctx, hipMemcpy(dm2.p, host_m2, n * 4, hipMemcpyHostToDevice));
+    else
+        HIPCHECK(ctx, hipMemset(dm2.p, 0, n * 4));
+    HIPCHECK(ctx, hipMemset(dmask.p, 1, n));
+    ipt_image dimg{dpx.p, dcnt.p, dsum.p, dmax.p};
+    uint32_t hs[4] = {0, 0, 0, 0};
+    int done = 0;
+    // (an error below returns after the drain: the buffers are freed on return)
+    for (int round = 0; done < p->spp && rc == IPT_OK; ++round) {
+        ipt_params q = *p;
+        q.spp = std::min<int>(round_spp, p->spp - done);
+        q.spp_offset = p->spp_offset + done;
+        rc = ipt_render_masked_device_async(ctx, &q, &dimg, round ? dmask.p : nullptr, dm2.p, st);
+        if (!rc) rc = ipt_adapt_device(ctx, ap, dpx.p, dcnt.p, dm2.p, dmask.p, dstats.p, st);
+        if (!rc && hipMemcpyAsync(hs, dstats.p, sizeof hs, hipMemcpyDeviceToHost, st) != hipSuccess)
+            rc = fail(ctx, IPT_E_DEVICE, "ipt_render_adaptive: stats copy failed");
+        if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(ctx, IPT_E_DEVICE, "ipt_render_adaptive: round failed");
+        if (rc) break;
+        done += q.spp;
+        if (hs[0] == 0) break;
+    }
+    const int rw = drain(ctx);
+    if (rc) return rc;
+    if (rw) return rw;
+    HIPCHECK(ctx, hipMemcpy(himg->pixels, dpx.p, n * 4, hipMemcpyDeviceToHost));
+    HIPCHECK(ctx, hipMemcpy(himg->counters, dcnt.p, n * 4, hipMemcpyDeviceToHost));
+    if (himg->sums) HIPCHECK(ctx, hipMemcpy(himg->sums, dsum.p, n * 4, hipMemcpyDeviceToHost));
+    if (himg->pixel_max) HIPCHECK(ctx, hipMemcpy(himg->pixel_max, dmax.p, n * 4, hipMemcpyDeviceToHost));
+    if (host_m2) HIPCHECK(ctx, hipMemcpy(host_m2, dm2.p, n * 4, hipMemcpyDeviceToHost));
+    if (host_mask) HIPCHECK(ctx, hipMemcpy(host_mask, dmask.p, n, hipMemcpyDeviceToHost));
+    stats[0] = hs[0];
+    stats[1] = hs[1];
+    stats[2] = hs[2];
+    stats[3] = (uint32_t)done;
+    return IPT_OK;
 }
 
 int ipt_render_wait(ipt_ctx* ctx) {

@@ -624,6 +624,44 @@ __global__ __launch_bounds__(kPostBlock) void logf_kernel(const float* __restric
     if (i < n) out[i] = logf_(x[i]);
 }
 
+// ipt_adapt_device: the next sample mask from the plane's mean, counter and
+// second moment, one thread per pixel, in f32 and with no contraction. Pixels
+// from no_source on (the Grid map's row H-1, which no sample has as its
+// nominal destination) get mask 0 and are counted nowhere. stats = {active,
+// starved, nan, 0}: integer adds, one per wave and class, so the sums do not
+// depend on the order of the waves.
+__global__ __launch_bounds__(kPostBlock) void adapt_kernel(const float* __restrict__ pixels,
+                                                           const uint32_t* __restrict__ counters,
+                                                           const float* __restrict__ m2, uint8_t* __restrict__ mask,
+                                                           long long n, long long no_source, uint32_t min_count,
+                                                           float rel_tol, float abs_tol, uint32_t* stats) {
+    const long long i = (long long)blockIdx.x * kPostBlock + threadIdx.x;
+    bool active = false, starved = false, nan = false;
+    if (i < n) {
+        if (i < no_source) {
+            const uint32_t c = counters[i];
+            if (c < min_count) {
+                active = starved = true;
+            } else {
+                const float nf = (float)c;
+                const float e2 = div_(m2[i], nf * (nf - 1.0f));
+                const float thr = rel_tol * fabsf(pixels[i]) + abs_tol;
+                const float t2 = thr * thr;
+                active = e2 > t2;
+                nan = e2 != e2 || t2 != t2;
+            }
+        }
+        mask[i] = active ? 1 : 0;
+    }
+    if (stats) {
+        const bool cls[3] = {active, starved, nan};
+        for (int k = 0; k < 3; ++k) {
+            const unsigned int c = (unsigned int)__popcll(__ballot(cls[k]));
+            if ((threadIdx.x & 63) == 0 && c) atomicAdd(&stats[k], c);
+        }
+    }
+}
+
 // powf_'s stated domain for y (ipt_math.h)
 bool powf_y_ok(float y) { return isfinite_(y) && y > 0.0f && y != std::trunc(y); }
 
@@ -1117,6 +1155,45 @@ int ipt_pgm_device(ipt_ctx* ctx, const ipt_pgm_params* p, const float* dev_pixel
         hipLaunchKernelGGL(n_val_kernel, dim3(quads), dim3(kPostBlock), 0, st, plane, dev_gray8, n, p->contrast,
                            p->gamma, (const PgmScalars*)ps);
     return pgm_queued(ctx, st);
+}
+
+int ipt_adapt_device(ipt_ctx* ctx, const ipt_adapt_params* p, const float* dev_pixels, const uint32_t* dev_counters,
+                     const float* dev_m2, uint8_t* dev_mask, uint32_t* dev_stats, void* hip_stream) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!p || !dev_pixels || !dev_counters || !dev_m2 || !dev_mask || p->width <= 0 || p->height <= 0 ||
+        p->min_count < 2 || !(p->rel_tol >= 0.0f) || !(p->abs_tol >= 0.0f))
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID,
+                                      "ipt_adapt_device: bad arguments (min_count >= 2, tolerances >= 0)");
+    if ((p->flags & ~(uint32_t)IPT_FLAG_GUI_PLANE) != 0 || (long long)p->width * p->height > (1ll << 31))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
+                                      "ipt_adapt_device: IPT_FLAG_GUI_PLANE alone, at most 2^31 pixels");
+    const long long n = (long long)p->width * p->height;
+    {
+        const void* in[3] = {dev_pixels, dev_counters, dev_m2};
+        for (int a = 0; a < 3; ++a)
+            if (overlap_(in[a], (size_t)n * 4, dev_mask, (size_t)n) || overlap_(in[a], (size_t)n * 4, dev_stats, 16))
+                return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_adapt_device: an output overlaps an input");
+        if (overlap_(dev_mask, (size_t)n, dev_stats, 16))
+            return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_adapt_device: the outputs overlap");
+    }
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    // (no scratch of its own: the event alone, so that the context's waits cover the call)
+    if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
+    // the Grid map's row H-1 (H >= 2) is no sample's nominal destination
+    const bool gui = (p->flags & IPT_FLAG_GUI_PLANE) != 0;
+    const long long no_source = (!gui && p->height >= 2) ? (long long)(p->height - 1) * p->width : n;
+    if (dev_stats) POSTCHECK(ctx, hipMemsetAsync(dev_stats, 0, 4 * sizeof(uint32_t), st));
+    const unsigned int blocks = (unsigned int)((n + kPostBlock - 1) / kPostBlock);
+    hipLaunchKernelGGL(adapt_kernel, dim3(blocks), dim3(kPostBlock), 0, st, dev_pixels, dev_counters, dev_m2, dev_mask,
+                       n, no_source, p->min_count, p->rel_tol, p->abs_tol, dev_stats);
+    POSTCHECK(ctx, hipGetLastError());
+    POSTCHECK(ctx, hipEventRecord(S.done, st));
+    S.used = true;
+    S.last_stream = st;
+    return IPT_OK;
 }
 
 int ipt_pgm(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const float* pixel_max, float* smoothed,

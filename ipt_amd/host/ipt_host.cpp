@@ -469,6 +469,46 @@ void GpuRenderer::render(GridRenderPlane& plane, const RenderParams& p) {
     io.finish(plane);
 }
 
+namespace {
+AdaptResult run_adaptive(ipt_ctx* ctx, ipt_image img, size_t W, size_t H, const RenderParams& p, const AdaptParams& a,
+                         uint32_t flags) {
+    const ipt_params q = to_params(W, H, p, flags);
+    ipt_adapt_params ap{};
+    ap.width = (int)W;
+    ap.height = (int)H;
+    ap.min_count = (uint32_t)std::max(a.min_count, 0);
+    ap.rel_tol = a.rel_tol;
+    ap.abs_tol = a.abs_tol;
+    ap.flags = flags & IPT_FLAG_GUI_PLANE;
+    AdaptResult r;
+    r.mask.assign(W * H, 0);
+    r.m2.assign(W * H, 0.0f);
+    uint32_t st[4] = {0, 0, 0, 0};
+    check(ctx, ipt_render_adaptive(ctx, &q, &ap, a.round_spp, &img, r.m2.data(), r.mask.data(), st));
+    r.active = st[0];
+    r.starved = st[1];
+    r.nan = st[2];
+    r.passes = (int)st[3];
+    return r;
+}
+}  // namespace
+
+AdaptResult GpuRenderer::render_adaptive(GridRenderPlane& plane, const RenderParams& p, const AdaptParams& a) {
+    check_plane(plane);
+    PlaneIo io(plane, 2 * p.spp);  // (row 0 takes two samples per pass)
+    const AdaptResult r = run_adaptive(ctx_, io.image(plane.pixels), plane.width, plane.height, p, a, 0);
+    io.finish(plane);
+    return r;
+}
+
+AdaptResult GpuRenderer::render_adaptive(GuiRenderPlane& plane, const RenderParams& p, const AdaptParams& a) {
+    check_plane(plane);
+    PlaneIo io(plane, p.spp);
+    const AdaptResult r = run_adaptive(ctx_, io.image(plane.pixels), plane.width, plane.height, p, a, IPT_FLAG_GUI_PLANE);
+    io.finish(plane);
+    return r;
+}
+
 void GpuRenderer::transfer_bytes(uint64_t* host_to_device, uint64_t* device_to_host) const {
     check(ctx_, ipt_transfer_bytes(ctx_, host_to_device, device_to_host));
 }

@@ -220,6 +220,23 @@ struct DisplayStats {
     float max = 0.0f, hist_min = 0.0f, white = 0.0f;
 };
 
+// Adaptive sampling (ipt_render_adaptive): the loop's rule and round size, and
+// what it returns. A pixel stays active while it has fewer than min_count
+// samples or the squared standard error of its mean, m2 / (n (n - 1)), exceeds
+// (rel_tol |mean| + abs_tol)^2; inactive pixels are not traced.
+struct AdaptParams {
+    float rel_tol = 0.05f;
+    float abs_tol = 1e-3f;
+    int min_count = 8;  // >= 2
+    int round_spp = 4;  // passes per round; round 0 traces every pixel
+};
+struct AdaptResult {
+    uint32_t active = 0, starved = 0, nan = 0;  // of the last round (ipt_adapt_device's stats)
+    int passes = 0;                             // passes used, <= RenderParams::spp
+    std::vector<uint8_t> mask;                  // the last mask, by nominal destination pixel
+    std::vector<float> m2;                      // the second-moment plane
+};
+
 class GpuRenderer {
    public:
     explicit GpuRenderer(int device = 0);
@@ -231,6 +248,12 @@ class GpuRenderer {
     void render(GridRenderPlane& plane, const RenderParams& p);
     // the same into the Gui's plane (Gui::addRay's row map, IPT_FLAG_GUI_PLANE)
     void render(GuiRenderPlane& plane, const RenderParams& p);
+    // up to p.spp passes in rounds of a.round_spp, each followed by the next
+    // mask on the device, until no pixel is active (ipt_render_adaptive; one
+    // device, whole frame: p.n_shards > 1 throws IPT_E_UNSUPPORTED). The plane
+    // is continued as render() continues it; the second moments start at zero.
+    AdaptResult render_adaptive(GridRenderPlane& plane, const RenderParams& p, const AdaptParams& a);
+    AdaptResult render_adaptive(GuiRenderPlane& plane, const RenderParams& p, const AdaptParams& a);
     // the same into a C-ABI image (32-bit counters); with p.n_shards > 1 only
     // the shard's rows of it are read and written (ipt_render). flags: further
     // IPT_FLAG_* bits of the call (IPT_FLAG_GUI_PLANE for a Gui plane's image,

@@ -14,7 +14,16 @@
 //              [--glare CUTOFF --glare-out glare.pfm]
 //              [--gpu-display] [--gui-plane] [--preview] [--white-percentile F]
 //              [--histogram hist.txt [--hist-buckets 400]]
+//              [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]
 //
+// --adaptive REL renders adaptively (GpuRenderer::render_adaptive): rounds of
+// --round-spp passes (4), each followed on the device by the next sample mask,
+// until no pixel is active or --spp, here the cap, is used up. A pixel stays
+// active while it has fewer than --min-spp samples (8) or the standard error
+// of its mean exceeds REL * |mean| + A (--adaptive-abs, 1e-3). One device and
+// one batch (--passes 1); composes with --gui-plane, --preview and every
+// output option. The JSON line then carries "adaptive_passes" (passes used)
+// and "adaptive_active" (pixels still active at the end).
 // --gui-plane renders into the Gui's plane (GuiRenderPlane, Gui::addRay's row
 // map, gui.cpp:165-182) instead of a GridRenderPlane: the plane the reference
 // program displays and saves, so that with --gpu-display the chain render ->
@@ -72,7 +81,8 @@ namespace {
                  "                  [--pgm result.pgm] [--smooth SIDE] [--smoothed-max SIDE]\n"
                  "                  [--glare CUTOFF --glare-out F.pfm]\n"
                  "                  [--gpu-display] [--gui-plane] [--preview] [--white-percentile F]\n"
-                 "                  [--histogram hist.txt [--hist-buckets 400]]\n");
+                 "                  [--histogram hist.txt [--hist-buckets 400]]\n"
+                 "                  [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]\n");
     std::exit(2);
 }
 }  // namespace
@@ -83,7 +93,8 @@ int main(int argc, char** argv) {
     long hist_buckets = 400;
     long smooth = 0, smoothed_max = 0;
     bool gpu_display = false, gui_plane = false, preview = false;
-    double glare = -1.0;
+    double glare = -1.0, adaptive_rel = -1.0, adaptive_abs = 1e-3;
+    long min_spp = 8, round_spp = 4;
     long width = 640, height = 640, spp = 16, passes = 1, n_rays = 16, depth = 8, device = 0, tile_rows = 16;
     std::vector<int> devices;
     unsigned long long seed = 20241223ull;
@@ -124,6 +135,10 @@ int main(int argc, char** argv) {
         else if (a == "--white-percentile") white_percentile = std::atof(val());
         else if (a == "--histogram") hist_out = val();
         else if (a == "--hist-buckets") hist_buckets = std::atol(val());
+        else if (a == "--adaptive") adaptive_rel = std::atof(val());
+        else if (a == "--adaptive-abs") adaptive_abs = std::atof(val());
+        else if (a == "--min-spp") min_spp = std::atol(val());
+        else if (a == "--round-spp") round_spp = std::atol(val());
         else usage(("unknown option " + a).c_str());
     }
     if (width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || n_rays < 0 || depth < 0) usage("bad sizes");
@@ -134,6 +149,10 @@ int main(int argc, char** argv) {
     if (white_percentile >= 0.0 && !gpu_display) usage("--white-percentile needs --gpu-display");
     if (!(white_percentile < 0.0) && !(white_percentile <= 1.0)) usage("--white-percentile takes a fraction in [0, 1]");
     if (hist_buckets < 1 || hist_buckets > 4096) usage("--hist-buckets takes 1..4096");
+    const bool adaptive = adaptive_rel >= 0.0;
+    if (adaptive && (passes != 1 || devices.size() > 1)) usage("--adaptive renders one batch on one device");
+    if (adaptive && (!(adaptive_abs >= 0.0) || min_spp < 2 || round_spp < 1))
+        usage("--adaptive-abs >= 0, --min-spp >= 2, --round-spp >= 1");
     try {
         const ipt::Scene scene = ipt::make_scene_by_name(scene_name);
         if (devices.empty()) devices.push_back((int)device);
@@ -152,8 +171,17 @@ int main(int argc, char** argv) {
         p.seed = seed;
         p.preview = preview;
         double kernel_ms = 0.0;
+        ipt::AdaptResult ar;
         const auto t0 = std::chrono::steady_clock::now();
-        for (long pass = 0; pass < passes; ++pass) {  // progressive: each batch continues the RNG stream
+        if (adaptive) {
+            ipt::AdaptParams ad;
+            ad.rel_tol = (float)adaptive_rel;
+            ad.abs_tol = (float)adaptive_abs;
+            ad.min_count = (int)min_spp;
+            ad.round_spp = (int)round_spp;
+            ar = gui_plane ? gpu.render_adaptive(gui, p, ad) : gpu.render_adaptive(plane, p, ad);
+        }
+        for (long pass = 0; pass < passes && !adaptive; ++pass) {  // progressive: each batch continues the RNG stream
             p.spp_offset = (int)(pass * spp);
             if (gui_plane) gpus.render(gui, p);
             else gpus.render(plane, p);
@@ -211,10 +239,12 @@ int main(int argc, char** argv) {
             "{\"scene\": \"%s\", \"width\": %ld, \"height\": %ld, \"spp\": %ld, \"passes\": %ld, "
             "\"n_rays\": %ld, \"depth_max\": %ld, \"devices\": %zu, \"max_value\": %.9g, \"seconds\": %.4f, "
             "\"Mpaths_per_s\": %.3f, \"kernel_Mpaths_per_s\": %.3f, \"last_batch_h2d_bytes\": %llu, "
-            "\"last_batch_d2h_bytes\": %llu, \"plane\": \"%s\"}\n",
+            "\"last_batch_d2h_bytes\": %llu, \"plane\": \"%s\"",
             scene_name.c_str(), width, height, spp, passes, n_rays, depth, gpus.size(), (double)plane.max_value, secs,
             paths / secs / 1e6, kernel_ms > 0 ? paths / (kernel_ms * 1e-3) / 1e6 : 0.0, (unsigned long long)h2d,
             (unsigned long long)d2h, gui_plane ? "gui" : "grid");
+        if (adaptive) std::printf(", \"adaptive_passes\": %d, \"adaptive_active\": %u", ar.passes, ar.active);
+        std::printf("}\n");
     } catch (const ipt::IptError& e) {
         std::fprintf(stderr, "ipt_render: error %d: %s\n", e.code, e.what());
         return 1;
