@@ -1306,6 +1306,9 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         // (pre_w is read only behind pre_ok: left uninitialised, no per-step moves)
         uint32_t pre_w;
         bool pre_ok = false;
+        // product FIXED = K: pre_w picks the fall-through (one draw, not three);
+        // read by the pre-skip's leaf rule, only behind pre_ok as well
+        bool pre_ft;
         // lattice instances: the picked light's sample fields are
         // gathered with the CosineDdf gathers (whole wave, index 0 for lanes
         // without a light pick) instead of read in the direction phase
@@ -1488,6 +1491,12 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     r2 = odd ? e3 : e2;
                     pre_w = odd ? e4 : e3;
                     pre_ok = jj <= 3u && (kFixed || kp.sa_on);
+                    // (lattices: pick_p2w's own last test -- with cdf_p2 a pick
+                    // below nl has g < T[pick] <= T[nl] on the non-decreasing cdf
+                    // that cdf_p2 requires; without cdf_p2 the leaf rule is off,
+                    // the whole pick_word here measured -0.9 % on C5)
+                    if constexpr (kK > 0 && !COUNT)
+                        pre_ft = kPickIntCdf ? (pre_w >> 8) >= kp.cdf_end_t : pick_word(pre_w) > nl;
                 } else {
                     const bool hi = kSkipAhead && jj >= 4u;
                     r1 = hi ? w.b1 : sel4(jj & 3u, w.a1, w.a2, w.a3, w.b0);
@@ -2118,9 +2127,29 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             // (as selects: no exec-mask branch)
             const bool back = (tpos.z - kp.sa_pz) * kp.sa_nz < 0.0f;
             const bool lpick = (unsigned long long)pre_w < kp.sa_u;
-            const bool take = iter_lane && pre_ok && back && ti < ((kK > 0 ? kTreeRays : kp.n_rays) >> tdepth) && lpick;
+            // Product FIXED = K: the leaf behind the plane. A
+            // node at depth K has one iteration, whose ray (rdepth K + 1, no
+            // children) returns the light's power, 0/0 on a surface or 0 on a
+            // miss. Strictly behind the plane that ray reaches no light
+            // whatever the pick: in light_trace_ax num = n.z (P.z - o.z) has
+            // n.z's sign (or is +-0), a hit needs n_dir < 0, so t = num / n_dir
+            // is negative or a zero and lt_1em6 rejects it (the lattice's shared
+            // quotient is the same expression). The node's sum is then 0 +
+            // mult {NaN, +-0}, NaN or +0, and fin_s returns +0: its value does
+            // not depend on what it draws, and its draw count is its pick
+            // word's class, three words (pick <= nl) or one (the fall-through,
+            // pre_ft). So the child just pushed at depth K (ti == 0 there)
+            // takes its iteration here whatever pre_w picks, and the pop below
+            // unwinds it in this step with the pop's own arithmetic: the child
+            // costs no lane-step, and its frame is never built. The counting
+            // instances run the iteration: the oracle counts its events.
+            // (lattices: where the pick word's class is one compare, cdf_p2)
+            const bool leaf = kK > 0 && !COUNT && tdepth == kK && (!global_lights(LMODE) || kp.cdf_p2 != 0);
+            const bool take = iter_lane && pre_ok && back && ti < ((kK > 0 ? kTreeRays : kp.n_rays) >> tdepth) &&
+                              (kK > 0 && !COUNT ? lpick || leaf : lpick);
             ti += take ? 1 : 0;
-            k += take ? 3u : 0u;
+            // (a light pick is not the fall-through: pre_ft is true only on a leaf's take)
+            k += take ? (kK > 0 && !COUNT ? (pre_ft ? 1u : 3u) : 3u) : 0u;
             if (COUNT) {
                 c_iter += take ? 1u : 0u;
                 c_lsamp += take ? 1u : 0u;
@@ -4095,6 +4124,12 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     // Past the lights (ce >= nl) the scan's answer is ce's clamp to nl - 1, then
     // cdf[nl]. The kernel reads cdf[ce-1] and cdf[ce] only.
     ctx->cdf_p2 = 0;
+    // cdf[nl]'s threshold in every scene, not a previous scene's: the lattice
+    // instances' pre-skip compares the next pick word with it in every step
+    // (pre_ft), also where no leaf is taken (cdf_p2 == 0) -- there a taken
+    // word picks a light, below cdf[nl - 1] <= cdf[nl], and must read as
+    // three draws
+    ctx->cdf_end = cdf[nl];
     for (int e = 1; cdf_mono && nl > kLdsLights && !any_round && e <= 20 && !ctx->cdf_p2; ++e) {
         const double w = std::ldexp(1.0, -e);
         bool ok = (double)nl * w <= 1.0;

@@ -29,6 +29,13 @@ struct Pol {
     const char* name;
     uint32_t jmerge, omax, jmax;
     bool pre, post;
+    // the leaf rule: 0 none; 1 policy A, a depth-K child behind
+    // the plane is consumed in its parent's step whatever it picks (it is worth
+    // +0) and the following step takes no prologue merge (only the child's own
+    // step is counted); 2 policy B, the kernel as built: the following step's
+    // prologue applies its skip-ahead rule to the parent's next iteration like
+    // any other step's (it cannot fire: that step starts at j >= 2)
+    int elide = 0;
 };
 static const Pol kPols[] = {
     {"prologue merge j<=1 (product)", 1, 0, 3, false, false},
@@ -41,6 +48,8 @@ static const Pol kPols[] = {
     {"12-word window: merge j<=1 + pre-pop pre-skip, o<=7 (j up to 6)", 1, 7, 6, true, false},
     {"12-word window: merge j<=2 + pre-pop pre-skip, o<=7 (j up to 6)", 2, 7, 6, true, false},
     {"12-word window: merge j<=1 + pre-pop pre-skip, o<=9 (j up to 8)", 1, 9, 8, true, false},
+    {"policy A: product + leaf rule, no merge in the following step", 1, 6, 5, true, false, 1},
+    {"policy B: product + leaf rule + the following step's skip-ahead", 1, 6, 5, true, false, 2},
 };
 constexpr int kPol = sizeof(kPols) / sizeof(kPols[0]);
 
@@ -67,6 +76,11 @@ int main(int argc, char** argv) {
     // policies: steps per path when certain skips merge into the next iteration's step
     uint64_t paths = 0, iters = 0, skips = 0, cert = 0, cert_last = 0, cert_j[4] = {}, cert_chain = 0,
              n1_cert = 0, merged_cur = 0, merged_any1 = 0, merged_chain = 0, sim_steps[kPol] = {}, sim_bad[kPol] = {}, rem[4] = {}, rem_j[6] = {};
+    // depth-K nodes (one iteration: K = log2 n_rays), those behind the plane, and
+    // those of them whose pick word lies in the parent step's window (product rules)
+    int K = 0;
+    while ((p.n_rays >> (K + 1)) != 0) ++K;
+    uint64_t leafs = 0, leafs_back = 0, leafs_win = 0;
     std::vector<Ev> evs;
     g_evs = &evs;
     for (int s = 0; s < spp; ++s)
@@ -89,6 +103,7 @@ int main(int argc, char** argv) {
                 for (int pol = 0; pol < kPol; ++pol) {
                     const Pol& q = kPols[pol];
                     uint32_t blk = 0;
+                    bool after_elide = false;
                     for (size_t e = 0; e < evs.size();) {
                         const Ev& v = evs[e];
                         ++sim_steps[pol];
@@ -96,10 +111,30 @@ int main(int argc, char** argv) {
                         const uint32_t j = v.k - 4u * blk;
                         if (j > q.jmax) ++sim_bad[pol];
                         size_t r = e;  // the step's real event
-                        if (v.skip && v.back && v.i != v.n - 1 && j <= q.jmerge) r = e + 1;
+                        if (v.skip && v.back && v.i != v.n - 1 && j <= q.jmerge && !(q.elide == 1 && after_elide)) r = e + 1;
                         size_t nx = r + 1;
+                        // the leaf rule: the real event's child at depth K behind the
+                        // plane, pick word (the pre-skip's word) in the window, taken
+                        // by the step's pre-skip whatever it picks (one take per step)
+                        after_elide = false;
+                        if (nx < evs.size()) {
+                            const Ev& a = evs[r];
+                            const Ev& b = evs[nx];
+                            if (b.depth == a.depth + 1 && b.depth == K && b.i == 0) {
+                                const bool win = b.k - 4u * blk <= q.omax;
+                                if (pol == 3) {
+                                    ++leafs;
+                                    if (b.back) ++leafs_back;
+                                    if (b.back && win) ++leafs_win;
+                                }
+                                if (q.elide && b.back && win) {
+                                    ++nx;
+                                    after_elide = true;
+                                }
+                            }
+                        }
                         // pre-skip before the step's pop: the next event of the same node or of the pushed child
-                        if (q.pre && nx < evs.size()) {
+                        if (q.pre && !after_elide && nx < evs.size()) {
                             const Ev& a = evs[r];
                             const Ev& b = evs[nx];
                             const bool same = b.depth == a.depth && b.i == a.i + 1;
@@ -152,6 +187,8 @@ int main(int argc, char** argv) {
     for (int pol = 0; pol < kPol; ++pol)
         std::printf("%-55s lane-steps per path %.3f (j beyond the window: %llu)\n", kPols[pol].name,
                     sim_steps[pol] / P, (unsigned long long)sim_bad[pol]);
+    std::printf("depth-%d nodes per path %.3f; behind the plane %.3f (%.1f %%); of those, pick word in the window %.3f (%.1f %%)\n", K,
+                leafs / P, leafs_back / P, 100.0 * leafs_back / (double)leafs, leafs_win / P, 100.0 * leafs_win / (double)leafs_back);
     std::printf("product policy: certain-skip lane-steps left: not after a pop: non-last %.3f last %.3f | after a pop: non-last %.3f last %.3f\n",
                 rem[0] / P, rem[1] / P, rem[2] / P, rem[3] / P);
     std::printf("  (not after a pop, non-last, by j: %.3f %.3f %.3f %.3f %.3f %.3f)\n", rem_j[0] / P, rem_j[1] / P,
