@@ -181,7 +181,26 @@ enum {
        full-estimator launches into the same image on the same stream. Which
        estimator's samples a plane holds is the caller's business. Without the
        flag nothing changes. */
-    IPT_FLAG_PREVIEW = 4u
+    IPT_FLAG_PREVIEW = 4u,
+    /* ABI 7 addition: unit compaction. The path kernel's work pool holds only
+       the samples that are traced: masked samples (ipt_render_masked_device,
+       ipt_render_adaptive), samples the render plane maps outside the frame
+       and samples of other shards' rows are taken out before the path kernel
+       starts, on the device (without the flag each of them is a unit the
+       path kernel loads and drops).
+       Every output is bit-identical to the same call without the flag:
+       planes, m2, counters, ipt_render_values' values and codes. Honoured by
+       every full-estimator launch (ipt_render, ipt_render_device[_async],
+       ipt_render_masked_device[_async], ipt_render_values,
+       ipt_render_adaptive); accepted and without effect with
+       IPT_FLAG_PREVIEW, whose kernel has no pool; refused by
+       ipt_replay_samples like every flag but IPT_FLAG_GUI_PLANE. A compacting
+       launch runs three more passes over its samples (two before the path
+       kernel, one after). Measured the pool shrinks with the
+       active share and the launch time does not: even on contiguous masks,
+       slower on scattered ones, so nothing sets the flag by itself. Without
+       the flag nothing changes. */
+    IPT_FLAG_COMPACT = 8u
 };
 
 /* Caller-owned GridRenderPlane state (GridRenderPlane.h:9-12), width*height
@@ -236,7 +255,9 @@ const char* ipt_last_error(ipt_ctx* ctx); /* ctx may be NULL (creation errors) *
  * the RotateDdf frame-angle table 1 GiB (freed by ipt_destroy); a render with
  * IPT_FLAG_PREVIEW reads neither and does not allocate them. Work buffers
  * grow to the largest render: 37 B per sample (radiance, drift code, raygen
- * record; 5 B for a preview sample, which has no record) in equal chunks of at most 2^29 samples (18.5 GiB) and at most 3/4
+ * record; 5 B for a preview sample, which has no record; 45 B with
+ * IPT_FLAG_COMPACT, whose two buffers a context allocates on its first such
+ * launch) in equal chunks of at most 2^29 samples (18.5 GiB) and at most 3/4
  * of the device memory free at the call (plus the context's own work
  * buffers), so a context's footprint is <= ~20 GiB and contexts sharing a
  * device get smaller chunks rather than IPT_E_OOM; a call renders all its
@@ -440,6 +461,30 @@ int ipt_get_profile(ipt_ctx* ctx, uint64_t* out, int n);
    its start or from its predecessor's end, whichever is later (overlapped
    launches sum to their span); [1] = accumulate kernels. */
 int ipt_last_kernel_ms(ipt_ctx* ctx, float* path_ms, float* accumulate_ms);
+
+/* ABI 7 addition: work units of the full-estimator launches completed by the
+   most recent wait (ipt_last_kernel_ms's scope; preview and replay launches
+   have no pool and are not counted), summed over the launches:
+   out[0] = the launches' dense units (passes x candidate rows x width);
+   out[1] = the units their pools handed out: total_units - start, where a
+            compacting launch's pool starts at the compact range's begin
+            rounded down to 256 and any other launch's at 0;
+   out[2] = the units that were traced (n_active) for a compacting launch,
+            the dense units for any other.
+   Without IPT_FLAG_COMPACT the three are equal. A wait that completed no
+   such launch leaves the previous values. */
+int ipt_last_units(ipt_ctx* ctx, uint64_t out[3]);
+
+/* ABI 7 addition, a test probe: the compaction plan of the call's FIRST
+   launch (p as for a render, IPT_FLAG_COMPACT implied; dev_mask [H][W] on the
+   device as for ipt_render_masked_device, or NULL). Runs the launch's
+   classification, scan, scatter and pool preset, no path kernel, and touches
+   no image; synchronous. *n_active and *start as above; host_src[0 ..
+   n_active) = the dense units of the compact range, in its order (ascending).
+   IPT_E_INVALID if cap < n_active (the two counts are still returned);
+   IPT_E_UNSUPPORTED with IPT_FLAG_PREVIEW. Needs an uploaded scene. */
+int ipt_compact_plan(ipt_ctx* ctx, const ipt_params* p, const uint8_t* dev_mask, uint32_t* host_src, uint64_t cap,
+                     uint64_t* n_active, uint64_t* start);
 
 /* ---- image post-process on the GPU, bit-exact --------
    ipt_smooth: GridRenderPlane::smooth(side) (in_place = 1: pixels are

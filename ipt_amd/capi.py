@@ -36,6 +36,7 @@ IPT_LIGHT_SPHERE, IPT_LIGHT_POINT, IPT_LIGHT_OUTER_SPHERE = 2, 3, 4
 IPT_FLAG_COUNTERS = 1
 IPT_FLAG_GUI_PLANE = 2  # Gui::addRay's row map instead of GridRenderPlane::addRay's (ABI 7)
 IPT_FLAG_PREVIEW = 4  # ray_power_preview instead of ray_power_recursive (ABI 7 addition)
+IPT_FLAG_COMPACT = 8  # the path kernel's pool holds the traced samples alone (ABI 7 addition)
 IPT_REPLAY_MAX_SAMPLES = 1 << 24  # ipt_replay_samples: spp * width * height per call (ABI 7 addition)
 
 F3 = C.c_float * 3
@@ -119,6 +120,7 @@ EXPORTED_SYMBOLS = (
     "ipt_smooth_device", "ipt_pgm_device", "ipt_pgm", "ipt_logf_host", "ipt_logf_device",
     "ipt_preview_values", "ipt_replay_samples",
     "ipt_render_masked_device_async", "ipt_render_masked_device", "ipt_adapt_device", "ipt_render_adaptive",
+    "ipt_last_units", "ipt_compact_plan",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -215,6 +217,10 @@ def load(path: str | os.PathLike | None = None):
         lib.ipt_adapt_device.argtypes = [C.c_void_p, C.POINTER(AdaptParams)] + [C.c_void_p] * 6
         lib.ipt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(AdaptParams), C.c_int32,
                                             C.POINTER(Image), C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ipt_last_units"):  # ABI 7 additions (unit compaction)
+        lib.ipt_last_units.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.ipt_compact_plan.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint64,
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if path is None:
         _lib = lib
     return lib
@@ -599,6 +605,24 @@ class Context:
         a, b = C.c_float(), C.c_float()
         _check(self.lib, self.h, self.lib.ipt_last_kernel_ms(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def last_units(self):
+        """(dense units, units the pools handed out, units traced) of the
+        full-estimator launches completed by the last wait (ipt_last_units)."""
+        out = (C.c_uint64 * 3)()
+        _check(self.lib, self.h, self.lib.ipt_last_units(self.h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def compact_plan(self, p: Params, mask_ptr=None):
+        """The compaction plan of the call's first launch (ipt_compact_plan):
+        (src uint32[n_active], the dense units in compact order; n_active;
+        start, the pool's first unit). mask_ptr: a device mask or None."""
+        per_launch = p.spp * p.width * p.height
+        src = np.zeros(max(per_launch, 1), np.uint32)
+        n, start = C.c_uint64(), C.c_uint64()
+        _check(self.lib, self.h, self.lib.ipt_compact_plan(self.h, C.byref(p), mask_ptr, src.ctypes.data, per_launch,
+                                                           C.byref(n), C.byref(start)))
+        return src[:int(n.value)].copy(), int(n.value), int(start.value)
 
     def math_device(self, fn: int, x: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, np.float32)

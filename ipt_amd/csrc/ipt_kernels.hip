@@ -923,6 +923,181 @@ __global__ __launch_bounds__(256) void raygen_kernel(const KParams kp) {
     }
 }
 
+// ------------------------------------------------ unit compaction (IPT_FLAG_COMPACT)
+// A compacting launch takes raygen_kernel's place with four
+// kernels on the slot stream, and runs one more after the path kernel:
+//   compact_classify_kernel  new_path_setup once per dense unit that is not
+//                            masked (codes, the invalid units' values, flags
+//                            and the drift count, all as raygen_kernel leaves
+//                            them; a masked unit gets its value and code from
+//                            its mask byte alone) and each block's count of
+//                            valid units;
+//   compact_scan_kernel      (one workgroup) the counts -> exclusive offsets in
+//                            place, the total n_active behind them;
+//   compact_scatter_kernel   valid unit number j in ascending dense order gets
+//                            the compact index c = total_units - n_active + j:
+//                            its two records go to rg[2c], rg[2c+1], its dense
+//                            unit to src[c]; the pad [start, total_units -
+//                            n_active) gets valid = 0 records, start being the
+//                            compact range's begin rounded down to kPoolChunk;
+//   compact_preset_kernel    (one thread) the unit counter starts at `start`, so
+//                            the unchanged path_kernel hands out [start,
+//                            total_units) alone; {start, n_active} go to the
+//                            launch's ring entry (ipt_last_units);
+//   compact_expand_kernel    values[src[c]] = cvalues[c] for the compact range
+//                            (the path kernel's kp.values is cvalues).
+// Nothing crosses to the host: n_active is read from blocks[nblk] by the
+// kernels that need it. A block is 256 consecutive dense units throughout.
+struct CompactBufs {
+    unsigned int* blocks;       // [nblk + 1]: counts, then exclusive offsets; [nblk] = n_active
+    uint32_t* src;              // [total_units] dense unit of a compact index
+    float* cvalues;             // [total_units] the path kernel's values, by compact index
+    float* values;              // [total_units] the launch's dense values
+    unsigned long long* ring;   // {start, n_active} of this launch
+};
+
+__global__ __launch_bounds__(256) void compact_classify_kernel(const KParams kp, unsigned int* __restrict__ blocks) {
+    __shared__ unsigned int total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const unsigned long long unit = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false, drift = false;
+    if (unit < kp.total_units) {
+        const bool sharded = !(kp.n_shards <= 1 || kp.tile_rows <= 0);
+        // a masked unit is known from its nominal pixel alone: new_path_setup
+        // leaves it value 0 and code 0xfe whatever its draws are, no flag and
+        // no drift count, so its Philox block and jitter are not computed here
+        bool masked = false;
+        if (kp.mask) {
+            const uint32_t u32 = (uint32_t)unit;
+            const uint32_t rem = u32 - udiv_exact(u32, kp.per_pass32, kp.inv_per_pass) * kp.per_pass32;
+            const int cand = (int)udiv_exact(rem, (uint32_t)kp.W, kp.inv_w);
+            const int ix = (int)(rem - (uint32_t)cand * (uint32_t)kp.W);
+            const int iy = sharded ? kp.cand_rows[cand] : cand;
+            const int yn = kp.plane == kPlaneGui ? gui_nominal_row(iy, kp.H) : nominal_row(iy, kp.H);
+            masked = kp.mask[(size_t)yn * kp.W + ix] == 0;
+        }
+        if (masked) {
+            kp.values[unit] = 0.0f;
+            kp.codes[unit] = (uint8_t)0xfe;
+        } else {
+            const RayGen g = new_path_setup(kp, unit, sharded, kp.cand_rows);
+            valid = g.valid;
+            drift = g.drift;
+        }
+    }
+    if (kp.count) {
+        const uint64_t m = __ballot(drift);
+        if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1))
+            atomicAdd(&kp.counters[10], (unsigned long long)__popcll(m));
+    }
+    const unsigned int c = (unsigned int)__popcll(__ballot(valid));
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&total, c);
+    __syncthreads();
+    if (threadIdx.x == 0) blocks[blockIdx.x] = total;
+}
+
+// one workgroup: blocks[0..nblk) -> exclusive offsets in place, total -> blocks[nblk]
+__global__ __launch_bounds__(256) void compact_scan_kernel(unsigned int* __restrict__ blocks, unsigned int nblk) {
+    __shared__ unsigned int part[256];
+    const unsigned int per = (nblk + 255u) / 256u;
+    const unsigned int lo = min(threadIdx.x * per, nblk), hi = min(lo + per, nblk);
+    unsigned int s = 0;
+    for (unsigned int i = lo; i < hi; ++i) s += blocks[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned int acc = 0;
+        for (int t = 0; t < 256; ++t) {
+            const unsigned int v = part[t];
+            part[t] = acc;
+            acc += v;
+        }
+        blocks[nblk] = acc;
+    }
+    __syncthreads();
+    unsigned int off = part[threadIdx.x];
+    for (unsigned int i = lo; i < hi; ++i) {
+        const unsigned int v = blocks[i];
+        blocks[i] = off;
+        off += v;
+    }
+}
+
+// new_path_setup's record of a unit it found valid, without its stores: the
+// same draws, jitter and camera ray (the build contracts no operations, so the
+// ray's bits are raygen_kernel's)
+__device__ __forceinline__ void compact_record(const KParams& kp, uint32_t u32, bool sharded, uint4& r0, uint4& r1) {
+    const uint32_t s = udiv_exact(u32, kp.per_pass32, kp.inv_per_pass);
+    const uint32_t rem = u32 - s * kp.per_pass32;
+    const int cand = (int)udiv_exact(rem, (uint32_t)kp.W, kp.inv_w);
+    const int ix = (int)(rem - (uint32_t)cand * (uint32_t)kp.W);
+    const int iy = sharded ? kp.cand_rows[cand] : cand;
+    const uint32_t rpass = (uint32_t)(kp.spp_offset + (int)s);
+    const uint32_t rpix = (uint32_t)(iy * kp.W + ix);
+    uint32_t a0, a1, a2, a3;
+    philox_fill(a0, a1, a2, a3, 0u, rpass, rpix, kp.key0, kp.key1);
+    const float x = jitter_coord(ix, u01(a0), kp.W);
+    const float y = jitter_coord(iy, u01(a1), kp.H);
+    const vec3 rd = camera_dir(kp.cam_right, kp.cam_up, kp.cam_dir, x, y);
+    r0 = make_uint4(__float_as_uint(rd.x), __float_as_uint(rd.y), __float_as_uint(rd.z), 1u);
+    r1 = make_uint4(a2, a3, rpass, rpix);
+}
+
+__global__ __launch_bounds__(256) void compact_scatter_kernel(const KParams kp, const unsigned int* __restrict__ blocks,
+                                                              uint32_t* __restrict__ src) {
+    __shared__ unsigned int wave_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long unit = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = unit < kp.total_units;
+    const unsigned long long first = kp.total_units - blocks[gridDim.x];  // the compact range's begin
+    const unsigned long long start = first / kPoolChunk * kPoolChunk;
+    // (compact_classify_kernel's code: an invalid unit has 0xfe or 0xff)
+    const bool valid = in && kp.codes[unit] < (uint8_t)0xfe;
+    const unsigned long long mask = __ballot(valid);
+    if (lane == 0) wave_cnt[wave] = (unsigned int)__popcll(mask);
+    __syncthreads();
+    unsigned int before = 0;
+    for (int w = 0; w < 4; ++w) before += w < wave ? wave_cnt[w] : 0u;
+    uint4* rg = const_cast<uint4*>(kp.rg);
+    // the pad: records of the slot's earlier launches lie there, and one with
+    // valid = 1 would be traced and stored
+    if (in && unit >= start && unit < first) {
+        rg[2 * unit] = make_uint4(0u, 0u, 0u, 0u);
+        rg[2 * unit + 1] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (valid) {
+        const unsigned long long c =
+            first + blocks[blockIdx.x] + before + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
+        const bool sharded = !(kp.n_shards <= 1 || kp.tile_rows <= 0);
+        uint4 r0, r1;
+        compact_record(kp, (uint32_t)unit, sharded, r0, r1);
+        if (c < kp.total_units) {
+            rg[2 * c] = r0;
+            rg[2 * c + 1] = r1;
+            src[c] = (uint32_t)unit;
+        }
+    }
+}
+
+__global__ void compact_preset_kernel(const unsigned int* __restrict__ blocks, unsigned int nblk,
+                                      unsigned long long total_units, unsigned long long* __restrict__ unit_counter,
+                                      unsigned long long* __restrict__ ring) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const unsigned long long n_active = blocks[nblk];
+    const unsigned long long start = (total_units - n_active) / kPoolChunk * kPoolChunk;
+    *unit_counter = start;
+    ring[0] = start;
+    ring[1] = n_active;
+}
+
+__global__ __launch_bounds__(256) void compact_expand_kernel(const CompactBufs cb, unsigned int nblk,
+                                                             unsigned long long total_units) {
+    const unsigned long long c = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= total_units || c < total_units - cb.blocks[nblk]) return;
+    cb.values[cb.src[c]] = cb.cvalues[c];
+}
+
 // BOXIN (sphere-in-box instances; false in the others, which do not read it):
 // the box planes' range form, a property of the scene (box_inrange, set at
 // upload). true compiles the in-range trace alone, false the generic full-form
@@ -2896,6 +3071,13 @@ struct WorkSlot {
     int cand_cap_rows = 0, cand_cap_h = 0;
     int plan[5] = {-1, -1, -1, -1, -1};  // (H, tile_rows, n_shards, shard_id, plane) whose rows are on the device
     unsigned long long* d_unit = nullptr;
+    // a compacting launch's buffers (IPT_FLAG_COMPACT), allocated on the slot's
+    // first such launch: the path kernel's values by compact index, the compact
+    // indices' dense units, the scan's block counts (compact_cap / 256 + 2)
+    float* d_cvalues = nullptr;
+    uint32_t* d_src = nullptr;
+    unsigned int* d_cblk = nullptr;
+    size_t compact_cap = 0;  // elements
     // pool-drained flag in signal memory (hipExtMallocWithFlags(hipMallocSignalMemory),
     // the memory hipStreamWaitValue64 is specified for) and the sequence
     // number of the slot's last queued launch (the value it stores there)
@@ -2922,10 +3104,20 @@ struct AdaptArgs {
     float* m2;            // [H][W] or null
 };
 
+// ipt_compact_plan: the first launch's plan, read back after compact_preset_kernel
+struct CompactProbe {
+    uint32_t* host_src;
+    unsigned long long cap;
+    unsigned long long n_active = 0, start = 0;
+    int rc = 0;
+};
+
 struct ChunkTiming {
     hipEvent_t t0 = nullptr, t1 = nullptr;  // raygen start, path-kernel end (slot stream)
     hipEvent_t a0 = nullptr, a1 = nullptr;  // accumulate (caller stream; null without an image)
     int clk = -1;           // the accumulate's wall-clock pair in ctx->d_clk (ring entry)
+    unsigned long long units = 0;  // a full-estimator launch's total_units (ipt_last_units)
+    int uring = -1;         // a compacting launch's {start, n_active} in ctx->d_uring (ring entry)
     bool recorded = false;  // every event of the launch was recorded (its queueing succeeded)
 };
 constexpr int kClkRing = 32;  // > the launches settle_oldest lets queue up (8) plus the last settled one
@@ -3018,6 +3210,11 @@ struct ipt_ctx {
     unsigned long long* d_clk = nullptr;
     unsigned long long* d_clk_dummy = nullptr;  // (2 words: stamps of an untimed launch)
     unsigned next_clk = 0;
+    // compacting launches' {start, n_active}, a ring as d_clk is (compact_preset_kernel
+    // writes an entry, settle_oldest reads it), and ipt_last_units' sums
+    unsigned long long* d_uring = nullptr;
+    unsigned next_uring = 0;
+    unsigned long long run_units[3] = {0, 0, 0}, last_units[3] = {0, 0, 0};
     double clk_khz = 100000.0;
     unsigned long long* d_counters = nullptr;
     float* d_cos_a = nullptr;   // CosineDdf tables (cos_table_kernel): r 64 MiB,
@@ -3092,7 +3289,7 @@ int ensure_frame_table(ipt_ctx* ctx, hipStream_t st) {
 // rg_elems: the raygen records (0 for a preview launch, which has none: 5 B
 // per unit instead of 37); kinds_elems / hits_elems: ipt_preview_values' outputs.
 int ensure_work(ipt_ctx* ctx, WorkSlot& S, size_t elems, size_t npix, int H, int n_cand, size_t rg_elems,
-                size_t kinds_elems, size_t hits_elems) {
+                size_t kinds_elems, size_t hits_elems, size_t compact_elems) {
     // (the caller has waited for the slot's previous launch and its readers)
     if (elems > S.work_cap) {
         if (S.d_values) hipFree(S.d_values);
@@ -3114,6 +3311,24 @@ int ensure_work(ipt_ctx* ctx, WorkSlot& S, size_t elems, size_t npix, int H, int
         S.rg_cap = 0;
         HIPCHECK(ctx, hipMalloc(&S.d_rg, rg_elems * 2 * sizeof(uint4)));
         S.rg_cap = rg_elems;
+    }
+    if (compact_elems > S.compact_cap) {
+        for (void* b : {(void*)S.d_cvalues, (void*)S.d_src, (void*)S.d_cblk})
+            if (b) hipFree(b);
+        S.d_cvalues = nullptr;
+        S.d_src = nullptr;
+        S.d_cblk = nullptr;
+        S.compact_cap = 0;
+        DevBuf<float> v;
+        DevBuf<uint32_t> u;
+        DevBuf<unsigned int> b;
+        HIPCHECK(ctx, hipMalloc(&v.p, compact_elems * sizeof(float)));
+        HIPCHECK(ctx, hipMalloc(&u.p, compact_elems * sizeof(uint32_t)));
+        HIPCHECK(ctx, hipMalloc(&b.p, (compact_elems / 256 + 2) * sizeof(unsigned int)));
+        S.d_cvalues = v.release();
+        S.d_src = u.release();
+        S.d_cblk = b.release();
+        S.compact_cap = compact_elems;
     }
     if (kinds_elems > S.kinds_cap) {
         if (S.d_kinds) hipFree(S.d_kinds);
@@ -3202,6 +3417,18 @@ int settle_oldest(ipt_ctx* ctx) {
         path = std::max(0.0f, path - d);
     ctx->run_path_ms += path;
     ctx->run_acc_ms += acc;
+    if (c.units) {
+        // (an uncompacted launch's pool hands out every dense unit)
+        unsigned long long h[2] = {0ull, c.units};
+        if (c.uring >= 0 &&
+            hipMemcpy(h, ctx->d_uring + 2 * c.uring, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) {
+            pool_return(ctx, c);
+            return fail(ctx, IPT_E_DEVICE, "reading a compacting launch's unit counts failed");
+        }
+        ctx->run_units[0] += c.units;
+        ctx->run_units[1] += c.units - h[0];
+        ctx->run_units[2] += h[1];
+    }
     pool_return(ctx, ctx->prev);
     ctx->prev = c;
     return IPT_OK;
@@ -3227,6 +3454,8 @@ int drain(ipt_ctx* ctx) {
         ctx->last_acc_ms = ctx->run_acc_ms;
     }
     ctx->run_path_ms = ctx->run_acc_ms = 0.0f;
+    if (ctx->run_units[0]) std::copy(ctx->run_units, ctx->run_units + 3, ctx->last_units);
+    ctx->run_units[0] = ctx->run_units[1] = ctx->run_units[2] = 0;
     return rc;
 }
 
@@ -3445,9 +3674,13 @@ int launch_preview(ipt_ctx* ctx, const KParams& kp, const PreviewOut& po, hipStr
 // launch), everything else is the call's as rendered
 int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t st,
                   float* host_values, uint8_t* host_codes, bool preview = false, uint8_t* host_kinds = nullptr,
-                  float* host_hits = nullptr, const ReplaySrc* replay = nullptr, const AdaptArgs* adapt = nullptr) {
+                  float* host_hits = nullptr, const ReplaySrc* replay = nullptr, const AdaptArgs* adapt = nullptr,
+                  CompactProbe* probe = nullptr) {
     preview = preview || (p->flags & IPT_FLAG_PREVIEW) != 0;
     const bool traced = !preview && !replay;  // the full estimator's launches
+    // IPT_FLAG_COMPACT: the pool holds the valid units alone (the preview has
+    // no pool: the flag has no effect there)
+    const bool compact = traced && ((p->flags & IPT_FLAG_COMPACT) != 0 || probe);
     std::vector<int> rows, of_row;
     candidate_rows(p, rows, of_row);
     const int n_cand = (int)rows.size();
@@ -3467,13 +3700,17 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
     // (a preview unit is its value and code, 5 B, plus ipt_preview_values'
     // outputs; it has no raygen record and its launches read no table)
     constexpr size_t kRgBytes = 2 * sizeof(uint4);
-    const size_t unit_bytes = sizeof(float) + 1 + (!traced ? (host_kinds ? 1 : 0) + (host_hits ? 6 * sizeof(float) : 0) : kRgBytes);
+    // (a compacting launch adds its compact values and dense-unit list, 8 B)
+    constexpr size_t kCompactBytes = sizeof(float) + sizeof(uint32_t);
+    const size_t unit_bytes = sizeof(float) + 1 + (!traced ? (host_kinds ? 1 : 0) + (host_hits ? 6 * sizeof(float) : 0) : kRgBytes) +
+                              (compact ? kCompactBytes : 0);
     size_t budget = (size_t)1 << 29;
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             size_t avail = free_b + (ctx->slot[0].work_cap + ctx->slot[1].work_cap) * (sizeof(float) + 1) +
-                           (!traced ? 0 : (ctx->slot[0].rg_cap + ctx->slot[1].rg_cap) * kRgBytes);
+                           (!traced ? 0 : (ctx->slot[0].rg_cap + ctx->slot[1].rg_cap) * kRgBytes) +
+                           (!compact ? 0 : (ctx->slot[0].compact_cap + ctx->slot[1].compact_cap) * kCompactBytes);
             const size_t tables = !traced ? 0 :
                                   (ctx->d_cos_a ? 0 : ((size_t)3 << 26)) +
                                   (ctx->d_frame_sc || !frame_table_user(ctx->geometry_kind)
@@ -3508,14 +3745,16 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         ctx->next_slot ^= 1u;
         const size_t elems = (size_t)chunk * per_pass;
         const size_t rg_elems = !traced ? 0 : elems, kinds_elems = host_kinds ? elems : 0, hits_elems = host_hits ? elems : 0;
+        const size_t compact_elems = compact ? elems : 0;
         const bool grow = elems > S.work_cap || (size_t)W * H > S.flags_cap || n_cand > S.cand_cap_rows ||
                           H > S.cand_cap_h || rg_elems > S.rg_cap || kinds_elems > S.kinds_cap ||
-                          hits_elems > S.hits_cap;
+                          hits_elems > S.hits_cap || compact_elems > S.compact_cap;
         const int plan[5] = {H, p->tile_rows, p->n_shards, p->shard_id, plane_of(p)};
         const bool replan = !std::equal(plan, plan + 5, S.plan);
         if (S.used && (grow || replan)) HIPCHECK(ctx, hipEventSynchronize(S.done));
-        rc = ensure_work(ctx, S, elems, (size_t)W * H, H, n_cand, rg_elems, kinds_elems, hits_elems);
+        rc = ensure_work(ctx, S, elems, (size_t)W * H, H, n_cand, rg_elems, kinds_elems, hits_elems, compact_elems);
         if (rc) return rc;
+        if (compact && !ctx->d_uring) HIPCHECK(ctx, hipMalloc(&ctx->d_uring, sizeof(unsigned long long) * 2 * kClkRing));
         if (replan) {
             // (synchronous copies: the host vectors do not outlive the call)
             HIPCHECK(ctx, hipMemcpy(S.d_cand_rows, rows.data(), sizeof(int) * n_cand, hipMemcpyHostToDevice));
@@ -3669,7 +3908,8 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             HIPCHECK(ctx, hipStreamWaitEvent(ss, S.mask_ready, 0));
             mask_waited[sidx] = true;
         }
-        HIPCHECK(ctx, hipMemsetAsync(S.d_unit, 0, sizeof(unsigned long long), ss));
+        // (a compacting launch's counter is set by compact_preset_kernel)
+        if (!compact) HIPCHECK(ctx, hipMemsetAsync(S.d_unit, 0, sizeof(unsigned long long), ss));
         HIPCHECK(ctx, hipMemsetAsync(S.d_flags, 0, (size_t)W * H, ss));
         HIPCHECK(ctx, hipEventRecord(tm.t0, ss));
         if (replay) {
@@ -3681,12 +3921,51 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             const PreviewOut po{host_kinds ? S.d_kinds : nullptr, host_hits ? S.d_hits : nullptr};
             rc = (count || po.kinds || po.hits) ? launch_preview<true>(ctx, kp, po, ss) : launch_preview<false>(ctx, kp, po, ss);
             if (rc) return rc;
+        } else if (compact) {
+            // classify / scan / scatter / preset in raygen_kernel's place, the
+            // path kernel over the compact range of the same records with the
+            // compact values as its output, then the values back to their
+            // dense places: everything after reads the launch as an
+            // uncompacted one leaves it
+            const unsigned nblk = (unsigned)((kp.total_units + 255) / 256);
+            tmq.uring = (int)(ctx->next_uring++ % kClkRing);
+            const CompactBufs cb{S.d_cblk, S.d_src, S.d_cvalues, S.d_values, ctx->d_uring + 2 * tmq.uring};
+            if (probe) kp.count = 0;
+            hipLaunchKernelGGL(compact_classify_kernel, dim3(nblk), dim3(256), 0, ss, kp, cb.blocks);
+            hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(256), 0, ss, cb.blocks, nblk);
+            hipLaunchKernelGGL(compact_scatter_kernel, dim3(nblk), dim3(256), 0, ss, kp, (const unsigned int*)cb.blocks, cb.src);
+            hipLaunchKernelGGL(compact_preset_kernel, dim3(1), dim3(64), 0, ss, (const unsigned int*)cb.blocks, nblk,
+                               kp.total_units, S.d_unit, cb.ring);
+            HIPCHECK(ctx, hipGetLastError());
+            if (probe) {
+                // ipt_compact_plan: the plan of the call's first launch, no path kernel
+                unsigned long long h[2] = {0, 0};
+                HIPCHECK(ctx, hipStreamSynchronize(ss));
+                HIPCHECK(ctx, hipMemcpy(h, cb.ring, sizeof h, hipMemcpyDeviceToHost));
+                probe->start = h[0];
+                probe->n_active = h[1];
+                if (h[1] > kp.total_units || h[1] > probe->cap)
+                    probe->rc = fail(ctx, IPT_E_INVALID, "ipt_compact_plan: host_src holds fewer than n_active entries");
+                else if (h[1])
+                    HIPCHECK(ctx, hipMemcpy(probe->host_src, cb.src + (kp.total_units - h[1]), h[1] * sizeof(uint32_t),
+                                            hipMemcpyDeviceToHost));
+            } else {
+                KParams kc = kp;
+                kc.values = cb.cvalues;
+                rc = susp <= 4 ? launch_path<4>(ctx, kc, ss, count) : launch_path<8>(ctx, kc, ss, count);
+                if (rc) return rc;
+                S.seq = kp.drain_seq;
+                hipLaunchKernelGGL(compact_expand_kernel, dim3(nblk), dim3(256), 0, ss, cb, nblk, kp.total_units);
+                HIPCHECK(ctx, hipGetLastError());
+                tmq.units = kp.total_units;
+            }
         } else {
         hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((kp.total_units + 255) / 256)), dim3(256), 0, ss, kp);
         HIPCHECK(ctx, hipGetLastError());
         rc = susp <= 4 ? launch_path<4>(ctx, kp, ss, count) : launch_path<8>(ctx, kp, ss, count);
         if (rc) return rc;
         S.seq = kp.drain_seq;
+        tmq.units = kp.total_units;
         }
         S.total = kp.total_units;
         HIPCHECK(ctx, hipEventRecord(tm.t1, ss));
@@ -3751,6 +4030,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             HIPCHECK(ctx, hipEventRecord(S.done, st));
         }
         tmq.recorded = true;
+        if (probe) return probe->rc;
     }
     return IPT_OK;
 }
@@ -3892,12 +4172,13 @@ void ipt_destroy(ipt_ctx* ctx) {
     (void)drain(ctx);  // nothing queued may still use the buffers
     ipt_internal::post_release(ctx);
     void* bufs[] = {ctx->d_cdf_lo, ctx->d_lgrid, ctx->d_lax, ctx->d_bvh_nodes, ctx->d_bvh_prims, ctx->d_light_nodes, ctx->d_lights, ctx->d_weights, ctx->d_cdf, ctx->d_wall, ctx->d_spheres,
-                    ctx->d_counters, ctx->d_cos_a, ctx->d_cos_b, ctx->d_clk,
+                    ctx->d_counters, ctx->d_cos_a, ctx->d_cos_b, ctx->d_clk, ctx->d_uring,
                     ctx->d_grid_start, ctx->d_grid_items, ctx->d_grid_c4, ctx->d_frame_sc};
     for (void* b : bufs)
         if (b) hipFree(b);
     for (WorkSlot& S : ctx->slot) {
-        void* sb[] = {S.d_values, S.d_codes, S.d_rg, S.d_kinds, S.d_hits, S.d_flags, S.d_cand_rows, S.d_cand_of_row, S.d_unit, S.d_drained};
+        void* sb[] = {S.d_values, S.d_codes, S.d_rg, S.d_kinds, S.d_hits, S.d_flags, S.d_cand_rows, S.d_cand_of_row, S.d_unit, S.d_drained,
+                      S.d_cvalues, S.d_src, S.d_cblk};
         for (void* b : sb)
             if (b) hipFree(b);
         if (S.done) hipEventDestroy(S.done);
@@ -4564,6 +4845,32 @@ int ipt_last_kernel_ms(ipt_ctx* ctx, float* path_ms, float* accumulate_ms) {
     if (path_ms) *path_ms = ctx->last_path_ms;
     if (accumulate_ms) *accumulate_ms = ctx->last_acc_ms;
     return IPT_OK;
+}
+
+int ipt_last_units(ipt_ctx* ctx, uint64_t out[3]) {
+    if (!ctx || !out) return IPT_E_INVALID;
+    for (int i = 0; i < 3; ++i) out[i] = ctx->last_units[i];
+    return IPT_OK;
+}
+
+int ipt_compact_plan(ipt_ctx* ctx, const ipt_params* p, const uint8_t* dev_mask, uint32_t* host_src, uint64_t cap,
+                     uint64_t* n_active, uint64_t* start) {
+    int rc = validate(ctx, p);
+    if (rc) return rc;
+    if (!n_active || !start || (cap && !host_src)) return fail(ctx, IPT_E_INVALID, "ipt_compact_plan: NULL output");
+    if (p->flags & IPT_FLAG_PREVIEW) return fail(ctx, IPT_E_UNSUPPORTED, "ipt_compact_plan: the preview has no unit pool");
+    hipSetDevice(ctx->device);
+    rc = drain(ctx);
+    if (rc) return rc;
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the mask is the caller's, written on any stream before the call)
+    CompactProbe probe{host_src, cap};
+    const AdaptArgs adapt{dev_mask, nullptr};
+    rc = render_chunks(ctx, p, nullptr, ctx->stream, nullptr, nullptr, false, nullptr, nullptr, nullptr,
+                       dev_mask ? &adapt : nullptr, &probe);
+    const int rw = drain(ctx);
+    *n_active = probe.n_active;
+    *start = probe.start;
+    return rc ? rc : rw;
 }
 
 int ipt_math_host(int fn, const float* in, float* out, int64_t n) {

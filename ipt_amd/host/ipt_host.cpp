@@ -397,7 +397,8 @@ ipt_params to_params(size_t W, size_t H, const RenderParams& p, uint32_t flags) 
     q.n_rays = p.n_rays;
     q.depth_max = p.depth_max;
     q.seed = p.seed;
-    q.flags = (p.counters ? IPT_FLAG_COUNTERS : 0) | (p.preview ? IPT_FLAG_PREVIEW : 0) | flags;
+    q.flags = (p.counters ? IPT_FLAG_COUNTERS : 0) | (p.preview ? IPT_FLAG_PREVIEW : 0) |
+              (p.compact ? IPT_FLAG_COMPACT : 0) | flags;
     if (p.n_shards > 1) {
         q.tile_rows = p.tile_rows;
         q.n_shards = p.n_shards;

@@ -197,6 +197,12 @@ struct RenderParams {
     // frame shown while the camera moves (IPT_FLAG_PREVIEW; n_rays and
     // depth_max are then not read). Every render call below takes it.
     bool preview = false;
+    // unit compaction (IPT_FLAG_COMPACT): the path kernel's pool holds the
+    // traced samples alone (masked samples of render_adaptive's rounds and
+    // shards' halo rows leave it) -- the same image bit for bit; DESIGN.md
+    // 4.16 has what it costs. Every render call below takes it; no effect
+    // with preview.
+    bool compact = false;
     // destination-row tile shard of this call (ipt_params.tile_rows / n_shards /
     // shard_id): n_shards <= 1 renders the whole frame
     int tile_rows = 16;

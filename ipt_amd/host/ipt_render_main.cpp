@@ -13,6 +13,7 @@
 //              [--pgm result.pgm] [--smooth SIDE] [--smoothed-max SIDE]
 //              [--glare CUTOFF --glare-out glare.pfm]
 //              [--gpu-display] [--gui-plane] [--preview] [--white-percentile F]
+//              [--compact]
 //              [--histogram hist.txt [--hist-buckets 400]]
 //              [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]
 //
@@ -24,6 +25,10 @@
 // one batch (--passes 1); composes with --gui-plane, --preview and every
 // output option. The JSON line then carries "adaptive_passes" (passes used)
 // and "adaptive_active" (pixels still active at the end).
+// --compact renders with unit compaction (IPT_FLAG_COMPACT): the path kernel's
+// work pool holds only the samples that are traced (the masked samples of an
+// --adaptive render's rounds leave it); every output is the same bytes. It
+// composes with every other option (no effect with --preview).
 // --gui-plane renders into the Gui's plane (GuiRenderPlane, Gui::addRay's row
 // map, gui.cpp:165-182) instead of a GridRenderPlane: the plane the reference
 // program displays and saves, so that with --gpu-display the chain render ->
@@ -81,6 +86,7 @@ namespace {
                  "                  [--pgm result.pgm] [--smooth SIDE] [--smoothed-max SIDE]\n"
                  "                  [--glare CUTOFF --glare-out F.pfm]\n"
                  "                  [--gpu-display] [--gui-plane] [--preview] [--white-percentile F]\n"
+                 "                  [--compact]\n"
                  "                  [--histogram hist.txt [--hist-buckets 400]]\n"
                  "                  [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]\n");
     std::exit(2);
@@ -92,7 +98,7 @@ int main(int argc, char** argv) {
     double white_percentile = -1.0;
     long hist_buckets = 400;
     long smooth = 0, smoothed_max = 0;
-    bool gpu_display = false, gui_plane = false, preview = false;
+    bool gpu_display = false, gui_plane = false, preview = false, compact = false;
     double glare = -1.0, adaptive_rel = -1.0, adaptive_abs = 1e-3;
     long min_spp = 8, round_spp = 4;
     long width = 640, height = 640, spp = 16, passes = 1, n_rays = 16, depth = 8, device = 0, tile_rows = 16;
@@ -132,6 +138,7 @@ int main(int argc, char** argv) {
         else if (a == "--gpu-display") gpu_display = true;
         else if (a == "--gui-plane") gui_plane = true;
         else if (a == "--preview") preview = true;
+        else if (a == "--compact") compact = true;
         else if (a == "--white-percentile") white_percentile = std::atof(val());
         else if (a == "--histogram") hist_out = val();
         else if (a == "--hist-buckets") hist_buckets = std::atol(val());
@@ -170,6 +177,7 @@ int main(int argc, char** argv) {
         p.depth_max = (int)depth;
         p.seed = seed;
         p.preview = preview;
+        p.compact = compact;
         double kernel_ms = 0.0;
         ipt::AdaptResult ar;
         const auto t0 = std::chrono::steady_clock::now();

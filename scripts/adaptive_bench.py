@@ -17,6 +17,14 @@ ipt_last_kernel_ms. Configurations:
                   16 unmasked passes with rel_tol R (0.25, 0.05 and 0.02; abs_tol
                   1e-3, min_count 8: the dark lower half and the misses go
                   inactive first), with m2
+  NAME compact    the compacted twin of every masked configuration above (share
+                  X, loop R): the same call with IPT_FLAG_COMPACT
+  shard           one shard (shard 1) of a 3-shard plan of 16-row tiles, no mask,
+                  no m2; "shard compact" with IPT_FLAG_COMPACT (the halo rows of
+                  the other shards leave the pool)
+
+A line also holds ipt_last_units of the call: the launch's dense units, the
+units its pool handed out and the units traced.
 
 All configurations run alternating, --runs rounds (5) after one warm-up round;
 a line holds the medians, every run, and the spread (max - min) / median of
@@ -84,6 +92,10 @@ def main():
     m2 = torch.zeros(n, dtype=torch.float32, device=dev)
     stats = torch.zeros(4, dtype=torch.int32, device=dev)
     p = capi.make_params(W, H, a.spp, n_rays=16, depth_max=8)
+    pc = capi.make_params(W, H, a.spp, n_rays=16, depth_max=8, flags=capi.IPT_FLAG_COMPACT)
+    shard = dict(tile_rows=16, n_shards=3, shard_id=1)
+    ps = capi.make_params(W, H, a.spp, n_rays=16, depth_max=8, **shard)
+    psc = capi.make_params(W, H, a.spp, n_rays=16, depth_max=8, flags=capi.IPT_FLAG_COMPACT, **shard)
 
     masks = {}
     rng = np.random.default_rng([W, H, 2])
@@ -111,14 +123,23 @@ def main():
             return parent.last_kernel_ms()
         if name == "unmasked":
             ctx.render_device(p, pixels.data_ptr(), counters.data_ptr())
+        elif name in ("shard", "shard compact"):
+            ctx.render_device(psc if name.endswith(" compact") else ps, pixels.data_ptr(), counters.data_ptr())
         elif name == "m2":
             ctx.render_masked_device(p, pixels.data_ptr(), counters.data_ptr(), m2_ptr=m2.data_ptr())
         else:
-            ctx.render_masked_device(p, pixels.data_ptr(), counters.data_ptr(), mask_ptr=masks[name].data_ptr(),
-                                     m2_ptr=m2.data_ptr())
+            compact = name.endswith(" compact")
+            mask = masks[name[:-len(" compact")] if compact else name]
+            ctx.render_masked_device(pc if compact else p, pixels.data_ptr(), counters.data_ptr(),
+                                     mask_ptr=mask.data_ptr(), m2_ptr=m2.data_ptr())
+        units[name] = ctx.last_units()
         return ctx.last_kernel_ms()
 
-    names = ["unmasked"] + (["parent"] if parent else []) + ["m2"] + list(masks)
+    units = {}
+    names = ["unmasked"] + (["parent"] if parent else []) + ["m2"]
+    for k in masks:
+        names += [k, k + " compact"]
+    names += ["shard", "shard compact"]
     for name in names:  # warm-up: every configuration once
         call(name)
     samples = {k: [] for k in names}
@@ -130,13 +151,16 @@ def main():
     for name in names:
         path, acc = zip(*samples[name])
         mp = statistics.median(path)
-        share = 1.0 if name in ("unmasked", "parent", "m2") else float(masks[name].float().mean().item())
+        mask_name = name[:-len(" compact")] if name.endswith(" compact") else name
+        share = float(masks[mask_name].float().mean().item()) if mask_name in masks else 1.0
         line = {"config": name, "width": W, "height": H, "spp": a.spp, "n_rays": 16, "depth_max": 8, "runs": a.runs,
                 "active_share": share, "path_ms": mp, "accumulate_ms": statistics.median(acc),
                 "path_ms_runs": list(path), "accumulate_ms_runs": list(acc),
                 "path_spread": (max(path) - min(path)) / mp if mp > 0 else 0.0,
                 "path_vs_baseline": mp / base if base > 0 else 0.0,
                 "baseline": "parent" if parent else "unmasked"}
+        if name in units:
+            line["units"] = list(units[name])
         lines.append(line)
         print(json.dumps(line), flush=True)
     ctx.close()
