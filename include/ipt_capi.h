@@ -14,8 +14,8 @@
  * available from ipt_last_error(). Calls are synchronous unless they take a
  * stream argument and say otherwise (ipt_render_device_async,
  * ipt_render_masked_device_async, ipt_adapt_device, ipt_display_device,
- * ipt_display_stats_device, ipt_smooth_device and ipt_pgm_device return once
- * their work is queued). One context per HIP device; contexts are independent, a
+ * ipt_display_stats_device, ipt_smooth_device, ipt_pgm_device,
+ * ipt_guides_device and ipt_denoise_device return once their work is queued). One context per HIP device; contexts are independent, a
  * single context is not reentrant. There is NO CPU fallback: without a usable
  * gfx950 device every rendering call fails with IPT_E_DEVICE.
  */
@@ -701,6 +701,106 @@ int ipt_pgm(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const fl
    ipt_logf_host is the library's host build of the code the kernels run. */
 int ipt_logf_host(const float* x, float* out, int64_t n);
 int ipt_logf_device(ipt_ctx* ctx, const float* x, float* out, int64_t n);
+
+/* ---- denoising on the GPU (ABI 7 additions) --------------------------------------
+   A variance-guided, geometry-aware a-trous filter between "render" and
+   "display", for a plane that stays on the device: ipt_guides_device writes
+   each pixel's first hit, ipt_denoise_device filters the plane with them and
+   with the m2 plane ipt_render_masked_device keeps (entry points and two
+   structs added; no layout change). The filter is not the reference's (its
+   only spatial filter is smooth(side)); its definition is the one below, and
+   the kernels compute it bit for bit.
+
+   ipt_guides_device: dev_guides[yd][xd] = the first hit of ONE preview sample,
+   pass p->spp_offset of ipt_preview_values (same Philox stream, jitter, kinds
+   and hits), of the pixel's NOMINAL source, written at the nominal destination
+   whatever the sample's drift code:
+     Grid map:  yd <= H-2 takes source row H-2-yd; row H-1 has no nominal
+                source (as in ipt_adapt_device): kind 0xff, zeros. H == 1: row
+                0 takes source row 0.
+     IPT_FLAG_GUI_PLANE: yd takes source row H-1-yd.
+   kind is ipt_preview_values' kinds byte (0xff: the sample was not traced),
+   pos = hits[0..2], normal = hits[3..5] (a light outcome: the light position
+   and a zero normal; a miss: zeros), zero = 0.
+   p->spp must be 1 (IPT_E_INVALID otherwise, as for a NULL dev_guides);
+   n_rays and depth_max are not read; n_shards > 1 or a flag other than
+   IPT_FLAG_GUI_PLANE and IPT_FLAG_PREVIEW: IPT_E_UNSUPPORTED. No plane is
+   accumulated into. Stream and wait rules are ipt_display_device's: the record
+   plane is complete when `hip_stream` (NULL = the context's stream) reaches
+   the point after the call; ipt_render_wait, ipt_upload_scene and ipt_destroy
+   wait for it. */
+typedef struct ipt_guide { /* 32 B, one per destination pixel */
+    float pos[3];
+    uint32_t kind; /* ipt_preview_values' kinds byte, 0xff = no source */
+    float normal[3];
+    uint32_t zero;
+} ipt_guide;
+int ipt_guides_device(ipt_ctx* ctx, const ipt_params* p, ipt_guide* dev_guides /* [H][W] */, void* hip_stream);
+/* Host buffer: the same kernels, synchronous. */
+int ipt_guides(ipt_ctx* ctx, const ipt_params* p, ipt_guide* guides /* [H][W] */);
+
+/* ipt_denoise_device. All f32, no contraction, IEEE division and square root,
+   no exp / pow / log. max(a, 0) below is `a > 0 ? a : 0` (a NaN gives 0).
+   Participation: pixel d takes part iff
+     (guides[d].kind & 3) == 1   (a surface)
+     c = counters[d] >= 2
+     pixels[d] is finite
+     var0 = m2[d] / (nf * (nf - 1.0f)) is finite,  nf = (float)c
+   Every other pixel (light, miss, no source, starved, non-finite) is copied
+   unchanged to dev_out, gets var_out = var0 if c >= 2, else 0, and is never
+   read as a tap.
+   Iteration k = 0 .. iterations-1, s = 1 << k, reads (col, var) of iteration
+   k-1 (iteration 0: pixels and var0) and writes new ones for every
+   participating centre p at (x, y):
+     gs = gw = 0; for dy = -1..1, dx = -1..1 (dy outer), q = (x+dx, y+dy)
+       inside the frame and participating:
+         g = {1/4 centre, 1/8 edge, 1/16 corner};  gs += g * var_q;  gw += g
+     gv = gs / gw                   (distance 1 whatever s)
+     den = sigma_l * sqrtf(gv) + 0x1p-20f
+     sw = sc = sv = 0; for dy = -2..2, dx = -2..2 (dy outer), q = (x + s*dx,
+       y + s*dy) inside the frame and participating (the centre included):
+         h  = hk[|dx|] * hk[|dy|],  hk = {3/8, 1/4, 1/16}
+         wn = max((nx*nx' + ny*ny') + nz*nz', 0), then wn = wn * wn,
+              normal_pow times          (n the centre's normal, n' the tap's)
+         D  = P_q - P_p;  e = fabsf((nx*Dx + ny*Dy) + nz*Dz)
+         t  = max(1.0f - e / sigma_z, 0);                    wz = t * t
+         u  = max(1.0f - fabsf(col_q - col_p) / den, 0);     wl = u * u
+         w  = h * ((wn * wz) * wl)
+         sw += w;  sc += w * col_q;  sv += (w * w) * var_q
+     sw == 0: col' = col_p, var' = var_p; otherwise col' = sc / sw,
+     var' = sv / (sw * sw)
+   dev_out gets the last iteration's col, dev_var_out (may be NULL) its var.
+   Errors, all raised before a buffer is written: a NULL that is not optional,
+   a non-positive size, iterations outside 1..6, normal_pow outside 0..7, a
+   sigma that is not > 0 (NaN included): IPT_E_INVALID; an output sharing a
+   byte with an input or with the other output: IPT_E_INVALID; more than 2^31
+   pixels: IPT_E_UNSUPPORTED. The scratch (two planes of 32 B records) belongs
+   to the context, is allocated on first use and grows to the largest frame
+   seen. Stream and wait rules are ipt_display_device's: queued on `hip_stream`
+   (NULL = the context's stream), no value crosses to the host, a call on
+   another stream waits on the previous post-process call's event. */
+typedef struct ipt_denoise_params {
+    int32_t width, height;
+    int32_t iterations; /* 1..6; iteration k uses tap step 1 << k */
+    float sigma_l;      /* colour, in standard errors, > 0 */
+    int32_t normal_pow; /* 0..7 squarings of max(dot, 0) */
+    float sigma_z;      /* plane distance, world units, > 0 */
+} ipt_denoise_params;
+int ipt_denoise_device(ipt_ctx* ctx, const ipt_denoise_params* dp, const float* dev_pixels,
+                       const uint32_t* dev_counters, const float* dev_m2, const ipt_guide* dev_guides,
+                       float* dev_out, float* dev_var_out /* may be NULL */, void* hip_stream);
+/* Host buffers: the same kernels, synchronous. */
+int ipt_denoise(ipt_ctx* ctx, const ipt_denoise_params* dp, const float* pixels, const uint32_t* counters,
+                const float* m2, const ipt_guide* guides, float* out, float* var_out /* may be NULL */);
+
+/* A measuring probe: the kernel times, in ms from HIP events, of the passes of
+   the context's last ipt_denoise_device call made with IPT_DENOISE_PROFILE=1
+   in the environment (without it the call records nothing and this returns
+   IPT_E_INVALID): ms[0] = the prepare pass, ms[1 + k] = iteration k, the rest
+   0. Waits for that call. IPT_DENOISE_FORM=direct / tiled in the environment
+   makes every iteration of a call run that tap-loop form (DESIGN.md
+   "Denoising"; the results are the same bits). */
+int ipt_denoise_pass_ms(ipt_ctx* ctx, float ms[7]);
 
 /* ---- the path's DDF samplers, exactly as the kernels evaluate them -----------
    For sampler validation (the reference's chi^2 harness, check_ddf.cpp:114-203)

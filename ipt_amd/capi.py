@@ -93,6 +93,25 @@ class AdaptParams(C.Structure):  # ABI 7 additions (adaptive sampling)
                 ("rel_tol", C.c_float), ("abs_tol", C.c_float), ("flags", C.c_uint32)]
 
 
+class Guide(C.Structure):  # ABI 7 additions (denoising): ipt_guide, 32 B
+    _fields_ = [("pos", F3), ("kind", C.c_uint32), ("normal", F3), ("zero", C.c_uint32)]
+
+
+# ipt_guide as a numpy record, one per destination pixel
+GuideRecord = np.dtype([("pos", np.float32, 3), ("kind", np.uint32), ("normal", np.float32, 3),
+                        ("zero", np.uint32)])
+
+
+class DenoiseParams(C.Structure):  # ABI 7 additions (denoising)
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("sigma_l", C.c_float),
+                ("normal_pow", C.c_int32), ("sigma_z", C.c_float)]
+
+
+# the filter's defaults (DESIGN.md "Denoising"): 5 iterations, colour within 4
+# standard errors, normals to the 2^5 = 32nd power, planes within 0.1 units
+DENOISE_DEFAULTS = dict(iterations=5, sigma_l=4.0, normal_pow=5, sigma_z=0.1)
+
+
 ABI_VERSION = 7  # include/ipt_capi.h IPT_ABI_VERSION
 ABI_LAYOUT_COMPATIBLE = (3, 4, 5, 6, 7)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
 
@@ -121,6 +140,7 @@ EXPORTED_SYMBOLS = (
     "ipt_preview_values", "ipt_replay_samples",
     "ipt_render_masked_device_async", "ipt_render_masked_device", "ipt_adapt_device", "ipt_render_adaptive",
     "ipt_last_units", "ipt_compact_plan",
+    "ipt_guides_device", "ipt_guides", "ipt_denoise_device", "ipt_denoise", "ipt_denoise_pass_ms",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -221,6 +241,12 @@ def load(path: str | os.PathLike | None = None):
         lib.ipt_last_units.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.ipt_compact_plan.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "ipt_denoise_device"):  # ABI 7 additions (denoising)
+        lib.ipt_guides_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]
+        lib.ipt_guides.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p]
+        lib.ipt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)] + [C.c_void_p] * 7
+        lib.ipt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)] + [C.c_void_p] * 6
+        lib.ipt_denoise_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     if path is None:
         _lib = lib
     return lib
@@ -298,6 +324,16 @@ def make_adapt_params(width, height, min_count=8, rel_tol=0.05, abs_tol=1e-3, fl
     p = AdaptParams()
     p.width, p.height, p.min_count, p.flags = width, height, min_count, flags
     p.rel_tol, p.abs_tol = rel_tol, abs_tol
+    return p
+
+
+def make_denoise_params(width, height, iterations=DENOISE_DEFAULTS["iterations"],
+                        sigma_l=DENOISE_DEFAULTS["sigma_l"], normal_pow=DENOISE_DEFAULTS["normal_pow"],
+                        sigma_z=DENOISE_DEFAULTS["sigma_z"]) -> DenoiseParams:
+    """ipt_denoise_device's parameters: iteration k taps at step 1 << k."""
+    p = DenoiseParams()
+    p.width, p.height, p.iterations, p.normal_pow = width, height, iterations, normal_pow
+    p.sigma_l, p.sigma_z = sigma_l, sigma_z
     return p
 
 
@@ -444,6 +480,51 @@ class Context:
             self.h, C.byref(p), C.byref(ap), round_spp, C.byref(im), None if m2 is None else m2.ctypes.data,
             None if mask is None else mask.ctypes.data, st.ctypes.data))
         return {"active": int(st[0]), "starved": int(st[1]), "nan": int(st[2]), "passes": int(st[3])}
+
+    def guides_device(self, p: Params, guides_ptr, stream=None):
+        """Queue ipt_guides_device: the first hit of pass p.spp_offset's preview
+        sample per destination pixel (GuideRecord [H][W] at guides_ptr);
+        p.spp must be 1. Complete on `stream`'s order or after wait()."""
+        _check(self.lib, self.h, self.lib.ipt_guides_device(self.h, C.byref(p), guides_ptr, stream))
+
+    def guides(self, p: Params) -> np.ndarray:
+        """Host-buffer guide plane (ipt_guides): GuideRecord [H][W]."""
+        g = np.zeros((p.height, p.width), GuideRecord)
+        _check(self.lib, self.h, self.lib.ipt_guides(self.h, C.byref(p), g.ctypes.data))
+        return g
+
+    def denoise_device(self, dp: DenoiseParams, pixels_ptr, counters_ptr, m2_ptr, guides_ptr, out_ptr,
+                       var_out_ptr=None, stream=None):
+        """Queue ipt_denoise_device: the guided a-trous filter of the plane into
+        out_ptr (float32 [H][W]) and, optionally, the filtered variance of the
+        mean into var_out_ptr. Complete on `stream`'s order or after wait()."""
+        _check(self.lib, self.h, self.lib.ipt_denoise_device(self.h, C.byref(dp), pixels_ptr, counters_ptr, m2_ptr,
+                                                             guides_ptr, out_ptr, var_out_ptr, stream))
+
+    def denoise_pass_ms(self):
+        """[prepare, iteration 0, ...] kernel ms of the last denoise_device call
+        made under IPT_DENOISE_PROFILE=1 (ipt_denoise_pass_ms)."""
+        ms = (C.c_float * 7)()
+        _check(self.lib, self.h, self.lib.ipt_denoise_pass_ms(self.h, ms))
+        return [float(x) for x in ms]
+
+    def denoise(self, dp: DenoiseParams, pixels, counters, m2, guides, var: bool = True):
+        """Host-buffer filter (ipt_denoise): (out, var_out or None), float32
+        [H*W]; guides a GuideRecord array."""
+        px = np.ascontiguousarray(pixels, np.float32).reshape(-1)
+        cn = np.ascontiguousarray(counters, np.uint32).reshape(-1)
+        mm = np.ascontiguousarray(m2, np.float32).reshape(-1)
+        gd = np.ascontiguousarray(guides, GuideRecord).reshape(-1)
+        n = dp.width * dp.height
+        for a in (px, cn, mm, gd):
+            if a.size < n:
+                raise ValueError("a buffer holds fewer than width * height elements")
+        out = np.empty(max(n, 0), np.float32)
+        vo = np.empty(max(n, 0), np.float32) if var else None
+        _check(self.lib, self.h, self.lib.ipt_denoise(self.h, C.byref(dp), px.ctypes.data, cn.ctypes.data,
+                                                      mm.ctypes.data, gd.ctypes.data, out.ctypes.data,
+                                                      vo.ctypes.data if var else None))
+        return out, vo
 
     def wait(self):
         _check(self.lib, self.h, self.lib.ipt_render_wait(self.h))

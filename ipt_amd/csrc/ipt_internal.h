@@ -26,7 +26,11 @@ struct PostScratch {
     void* pgm = nullptr;           // ipt_smooth_device / ipt_pgm_device: the maxima, max_value, logf(contrast)
     float* processed = nullptr;    // glare output (smooth output, in-place copy) when the caller passes none
     float* tone = nullptr;         // tone-mapped image when the caller passes none
-    size_t bright_cap = 0, blocks_cap = 0, processed_cap = 0, tone_cap = 0;
+    void* denoise = nullptr;       // ipt_denoise_device: two planes of 32 B records (denoise_cap pixels each)
+    size_t bright_cap = 0, blocks_cap = 0, processed_cap = 0, tone_cap = 0, denoise_cap = 0;
+    // ipt_denoise_pass_ms (IPT_DENOISE_PROFILE=1): events around the last call's passes
+    hipEvent_t denoise_ev[8] = {};
+    int denoise_timed = 0;  // iterations of the last profiled call, 0: none
     hipEvent_t done = nullptr;
     hipStream_t last_stream = nullptr;
     bool used = false;
@@ -34,6 +38,10 @@ struct PostScratch {
 PostScratch& ctx_post(ipt_ctx* ctx);
 int post_wait(ipt_ctx* ctx);     // waits for the queued display work (0 or IPT_E_DEVICE)
 void post_release(ipt_ctx* ctx);  // frees the scratch (after post_wait)
+// ipt_guides_device's scatter (ipt_post.hip): one pass of the FULL preview
+// kernel's kinds and hits, [H][W] in source order, into the guide plane
+hipError_t launch_guide_scatter(hipStream_t st, const uint8_t* kinds, const float* hits, ipt_guide* dev_guides, int W,
+                                int H, bool gui);
 
 // Owning device allocation: a call's temporaries are freed on every return
 // path, early error returns included; release() hands the pointer over.

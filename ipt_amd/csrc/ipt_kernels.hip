@@ -3675,8 +3675,11 @@ int launch_preview(ipt_ctx* ctx, const KParams& kp, const PreviewOut& po, hipStr
 int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t st,
                   float* host_values, uint8_t* host_codes, bool preview = false, uint8_t* host_kinds = nullptr,
                   float* host_hits = nullptr, const ReplaySrc* replay = nullptr, const AdaptArgs* adapt = nullptr,
-                  CompactProbe* probe = nullptr) {
+                  CompactProbe* probe = nullptr, ipt_guide* guides = nullptr) {
     preview = preview || (p->flags & IPT_FLAG_PREVIEW) != 0;
+    // ipt_guides_device: the FULL preview instance's kinds and hits stay on the
+    // device, where a scatter on the caller's stream reads them
+    const bool want_kinds = host_kinds || guides, want_hits = host_hits || guides;
     const bool traced = !preview && !replay;  // the full estimator's launches
     // IPT_FLAG_COMPACT: the pool holds the valid units alone (the preview has
     // no pool: the flag has no effect there)
@@ -3702,7 +3705,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
     constexpr size_t kRgBytes = 2 * sizeof(uint4);
     // (a compacting launch adds its compact values and dense-unit list, 8 B)
     constexpr size_t kCompactBytes = sizeof(float) + sizeof(uint32_t);
-    const size_t unit_bytes = sizeof(float) + 1 + (!traced ? (host_kinds ? 1 : 0) + (host_hits ? 6 * sizeof(float) : 0) : kRgBytes) +
+    const size_t unit_bytes = sizeof(float) + 1 + (!traced ? (want_kinds ? 1 : 0) + (want_hits ? 6 * sizeof(float) : 0) : kRgBytes) +
                               (compact ? kCompactBytes : 0);
     size_t budget = (size_t)1 << 29;
     {
@@ -3744,7 +3747,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         WorkSlot& S = ctx->slot[ctx->next_slot];
         ctx->next_slot ^= 1u;
         const size_t elems = (size_t)chunk * per_pass;
-        const size_t rg_elems = !traced ? 0 : elems, kinds_elems = host_kinds ? elems : 0, hits_elems = host_hits ? elems : 0;
+        const size_t rg_elems = !traced ? 0 : elems, kinds_elems = want_kinds ? elems : 0, hits_elems = want_hits ? elems : 0;
         const size_t compact_elems = compact ? elems : 0;
         const bool grow = elems > S.work_cap || (size_t)W * H > S.flags_cap || n_cand > S.cand_cap_rows ||
                           H > S.cand_cap_h || rg_elems > S.rg_cap || kinds_elems > S.kinds_cap ||
@@ -3918,7 +3921,7 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
             HIPCHECK(ctx, hipGetLastError());
         } else if (preview) {
             // one fused kernel; the counting / AOV instance only where asked
-            const PreviewOut po{host_kinds ? S.d_kinds : nullptr, host_hits ? S.d_hits : nullptr};
+            const PreviewOut po{want_kinds ? S.d_kinds : nullptr, want_hits ? S.d_hits : nullptr};
             rc = (count || po.kinds || po.hits) ? launch_preview<true>(ctx, kp, po, ss) : launch_preview<false>(ctx, kp, po, ss);
             if (rc) return rc;
         } else if (compact) {
@@ -3981,7 +3984,16 @@ int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t
         if (host_hits)
             HIPCHECK(ctx, hipMemcpyAsync(host_hits + (size_t)s0 * per_pass * 6, S.d_hits, sizeof(float) * 6 * ns * per_pass,
                                          hipMemcpyDeviceToHost, ss));
-        if (!img) HIPCHECK(ctx, hipEventRecord(S.done, ss));
+        if (guides) {
+            // (one pass, whole frame: unit = iy * W + ix) the scatter runs on
+            // the caller's stream, in call order, after the preview kernel;
+            // the slot's buffers are free again once it has run
+            HIPCHECK(ctx, hipStreamWaitEvent(st, tm.t1, 0));
+            HIPCHECK(ctx, ipt_internal::launch_guide_scatter(st, S.d_kinds, S.d_hits, guides, W, H, kp.plane == kPlaneGui));
+            HIPCHECK(ctx, hipEventRecord(S.done, st));
+        } else if (!img) {
+            HIPCHECK(ctx, hipEventRecord(S.done, ss));
+        }
         if (img) {
             // the render plane's replay: on the caller's stream, in call order,
             // after this launch's path kernel
@@ -4730,6 +4742,38 @@ int ipt_preview_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t
     const int rw = drain(ctx);  // the host copies run on the slot streams
     if (rc) return rc;
     if (rw) return rw;
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return IPT_OK;
+}
+
+int ipt_guides_device(ipt_ctx* ctx, const ipt_params* p, ipt_guide* dev_guides, void* hip_stream) {
+    int rc = validate(ctx, p, true);
+    if (rc) return rc;
+    if (!dev_guides) return fail(ctx, IPT_E_INVALID, "ipt_guides_device: dev_guides is NULL");
+    if (p->spp != 1) return fail(ctx, IPT_E_INVALID, "ipt_guides_device: spp must be 1 (one sample per pixel)");
+    if (p->n_shards > 1) return fail(ctx, IPT_E_UNSUPPORTED, "ipt_guides_device writes whole frames");
+    if (p->flags & ~(uint32_t)(IPT_FLAG_GUI_PLANE | IPT_FLAG_PREVIEW))
+        return fail(ctx, IPT_E_UNSUPPORTED, "ipt_guides_device takes IPT_FLAG_GUI_PLANE and IPT_FLAG_PREVIEW alone");
+    hipSetDevice(ctx->device);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    // (tile_rows without shards: the call owns the whole frame)
+    return render_chunks(ctx, p, nullptr, st, nullptr, nullptr, true, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         dev_guides);
+}
+
+int ipt_guides(ipt_ctx* ctx, const ipt_params* p, ipt_guide* guides) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!guides) return fail(ctx, IPT_E_INVALID, "ipt_guides: guides is NULL");
+    if (!p || p->width <= 0 || p->height <= 0) return fail(ctx, IPT_E_INVALID, "ipt_guides: bad arguments");
+    hipSetDevice(ctx->device);
+    const size_t bytes = (size_t)p->width * (size_t)p->height * sizeof(ipt_guide);
+    DevBuf<ipt_guide> dg;
+    HIPCHECK(ctx, hipMalloc(&dg.p, bytes));
+    const int rc = ipt_guides_device(ctx, p, dg.p, ctx->stream);
+    const int rw = drain(ctx);
+    if (rc) return rc;
+    if (rw) return rw;
+    HIPCHECK(ctx, hipMemcpyAsync(guides, dg.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     return IPT_OK;
 }

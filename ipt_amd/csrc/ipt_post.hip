@@ -27,6 +27,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
@@ -662,6 +664,260 @@ __global__ __launch_bounds__(kPostBlock) void adapt_kernel(const float* __restri
     }
 }
 
+// ------------------------------------------------------------------ denoising
+// ipt_guides_device's second half: the FULL preview kernel's per-sample kinds
+// and hits of one pass, [H][W] in source order, into the guide plane in
+// destination order under the plane's nominal row map. One thread per
+// destination pixel; a row without a nominal source gets kind 0xff and zeros.
+// (one dword per store: the caller's plane may have any alignment a float has)
+__global__ __launch_bounds__(kPostBlock) void guide_scatter_kernel(const uint8_t* __restrict__ kinds,
+                                                                   const float* __restrict__ hits,
+                                                                   uint32_t* __restrict__ out, int W, int H, int gui,
+                                                                   long long n) {
+    const long long i = (long long)blockIdx.x * kPostBlock + threadIdx.x;
+    if (i >= n) return;
+    const int yd = (int)(i / W), xd = (int)(i - (long long)yd * W);
+    const int ys = gui ? H - 1 - yd : (H == 1 ? 0 : (yd <= H - 2 ? H - 2 - yd : -1));
+    uint32_t r[8] = {0, 0, 0, 0xffu, 0, 0, 0, 0};
+    if (ys >= 0) {
+        const long long u = (long long)ys * W + xd;
+        const float* h = hits + 6 * u;
+        r[0] = f2u(h[0]); r[1] = f2u(h[1]); r[2] = f2u(h[2]);
+        r[3] = kinds[u];
+        r[4] = f2u(h[3]); r[5] = f2u(h[4]); r[6] = f2u(h[5]);
+    }
+    uint32_t* o = out + 8 * i;
+    for (int j = 0; j < 8; ++j) o[j] = r[j];
+}
+
+// The filter's per-pixel record, two float4 per pixel: {P, col}, {n, var}. A
+// tap is two 16-byte loads. A pixel that does not take part carries zeros and
+// the var bits kDnSkip, and a tap that finds them is skipped. No arithmetic
+// produces these bits in a participating record: its col and var0 are finite,
+// the NaNs of its P and n are made canonical here, so every NaN in flight is
+// a canonical or quieted one, and a NaN var is stored canonical.
+constexpr uint32_t kDnSkip = 0xffffffffu;
+__device__ __forceinline__ float dn_canon_(float x) { return x != x ? u2f(0x7fc00000u) : x; }
+__device__ __forceinline__ float dn_pos_(float x) { return x > 0.0f ? x : 0.0f; }  // max(x, 0), NaN gives 0
+
+// var0 = m2 / (nf * (nf - 1)) where c >= 2, else 0 (ipt_adapt_device's e2)
+__device__ __forceinline__ float dn_var0_(uint32_t c, float m2) {
+    if (c < 2) return 0.0f;
+    const float nf = (float)c;
+    return div_(m2, nf * (nf - 1.0f));
+}
+
+__global__ __launch_bounds__(kPostBlock) void denoise_prepare_kernel(const float* __restrict__ pixels,
+                                                                     const uint32_t* __restrict__ counters,
+                                                                     const float* __restrict__ m2,
+                                                                     const uint32_t* __restrict__ guides,
+                                                                     float4* __restrict__ rec, long long n) {
+    const long long i = (long long)blockIdx.x * kPostBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t c = counters[i];
+    const float px = pixels[i];
+    const float var0 = dn_var0_(c, m2[i]);
+    const uint32_t* g = guides + 8 * i;
+    const bool part = (g[3] & 3u) == 1u && c >= 2 && isfinite_(px) && isfinite_(var0);
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = make_float4(0.0f, 0.0f, 0.0f, u2f(kDnSkip));
+    if (part) {
+        a = make_float4(dn_canon_(u2f(g[0])), dn_canon_(u2f(g[1])), dn_canon_(u2f(g[2])), px);
+        b = make_float4(dn_canon_(u2f(g[4])), dn_canon_(u2f(g[5])), dn_canon_(u2f(g[6])), var0);
+    }
+    rec[2 * i] = a;
+    rec[2 * i + 1] = b;
+}
+
+// What one iteration hands over: the record planes, the frame, the step and,
+// for the last iteration (LAST), the caller's planes.
+struct DnArgs {
+    const float4* in;
+    float4* out_rec;
+    int W, H, s, npow;
+    float sigma_l, sigma_z;
+    const uint32_t* pixels;  // LAST: bit copies of the pixels that take no part
+    const uint32_t* counters;
+    const float* m2;
+    float* out;
+    float* var_out;
+};
+
+constexpr int kDnTileW = 32, kDnTileH = 8;  // one workgroup's pixels (256 threads)
+
+// one tap of the 5 x 5 kernel, in the contract's operation order
+__device__ __forceinline__ void dn_tap_(const float4 a, const float4 b, const float4 qa, const float4 qb, float h,
+                                        float den, float sigma_z, int npow, float& sw, float& sc, float& sv) {
+    float wn = dn_pos_((b.x * qb.x + b.y * qb.y) + b.z * qb.z);
+    for (int j = 0; j < npow; ++j) wn = wn * wn;
+    const float dx = qa.x - a.x, dy = qa.y - a.y, dz = qa.z - a.z;
+    const float e = fabs_((b.x * dx + b.y * dy) + b.z * dz);
+    const float t = dn_pos_(1.0f - div_(e, sigma_z));
+    const float wz = t * t;
+    const float u = dn_pos_(1.0f - div_(fabs_(qa.w - a.w), den));
+    const float wl = u * u;
+    const float w = h * ((wn * wz) * wl);
+    sw += w;
+    sc += w * qa.w;
+    sv += (w * w) * qb.w;
+}
+
+__device__ __forceinline__ float dn_hk_(int d) { return d == 0 ? 0.375f : (d == 1 || d == -1 ? 0.25f : 0.0625f); }
+
+// the centre's finish: the quotients, or the centre itself when no weight is left
+__device__ __forceinline__ void dn_finish_(const float4 a, const float4 b, float sw, float sc, float sv, float& col,
+                                           float& var) {
+    col = a.w;
+    var = b.w;
+    if (!(sw == 0.0f)) {
+        col = div_(sc, sw);
+        var = dn_canon_(div_(sv, sw * sw));
+    }
+}
+
+// the pixel's outputs: the next record, or with LAST the caller's planes
+template <bool LAST>
+__device__ __forceinline__ void dn_store_(const DnArgs& d, size_t i, const float4 a, const float4 b, bool part,
+                                          float col, float var) {
+    if (!LAST) {
+        d.out_rec[2 * i] = make_float4(a.x, a.y, a.z, col);
+        d.out_rec[2 * i + 1] = make_float4(b.x, b.y, b.z, var);
+        return;
+    }
+    if (part) {
+        d.out[i] = col;
+        if (d.var_out) d.var_out[i] = var;
+    } else {
+        reinterpret_cast<uint32_t*>(d.out)[i] = d.pixels[i];
+        if (d.var_out) d.var_out[i] = dn_var0_(d.counters[i], d.m2[i]);
+    }
+}
+
+// Direct form: one thread per pixel, every tap gathered from the record plane
+// (25 x 2 16-byte loads at stride s, 9 4-byte loads for the variance prefilter).
+// (a one-dimensional grid of tiles_x * tiles_y workgroups: a frame may be 2^31 pixels tall)
+template <bool LAST>
+__global__ __launch_bounds__(kPostBlock) void denoise_direct_kernel(const DnArgs d, unsigned tiles_x) {
+    const unsigned by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
+    const int x = (int)(bx * kDnTileW + (threadIdx.x & (kDnTileW - 1)));
+    const int y = (int)(by * kDnTileH + (threadIdx.x / kDnTileW));
+    if (x >= d.W || y >= d.H) return;
+    const size_t i = (size_t)y * d.W + x;
+    const float4 a = d.in[2 * i], b = d.in[2 * i + 1];
+    if (f2u(b.w) == kDnSkip) {
+        dn_store_<LAST>(d, i, a, b, false, 0.0f, u2f(kDnSkip));
+        return;
+    }
+    float gs = 0.0f, gw = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= d.H) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= d.W) continue;
+            const float vq = d.in[2 * ((size_t)yy * d.W + xx) + 1].w;
+            if (f2u(vq) == kDnSkip) continue;
+            const float g = (dx == 0 && dy == 0) ? 0.25f : ((dx == 0 || dy == 0) ? 0.125f : 0.0625f);
+            gs += g * vq;
+            gw += g;
+        }
+    }
+    const float den = d.sigma_l * sqrt_(div_(gs, gw)) + 0x1p-20f;
+    float sw = 0.0f, sc = 0.0f, sv = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const long long yy = (long long)y + (long long)d.s * dy;
+        if (yy < 0 || yy >= d.H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const long long xx = (long long)x + (long long)d.s * dx;
+            if (xx < 0 || xx >= d.W) continue;
+            const size_t q = (size_t)yy * d.W + (size_t)xx;
+            const float4 qb = d.in[2 * q + 1];
+            if (f2u(qb.w) == kDnSkip) continue;
+            const float4 qa = d.in[2 * q];
+            dn_tap_(a, b, qa, qb, dn_hk_(dx) * dn_hk_(dy), den, d.sigma_z, d.npow, sw, sc, sv);
+        }
+    }
+    float col, var;
+    dn_finish_(a, b, sw, sc, sv, col, var);
+    dn_store_<LAST>(d, i, a, b, true, col, var);
+}
+
+// Lattice-tiled form: a workgroup owns a 32 x 8 tile of the pixels congruent
+// to (rx, ry) mod s, whose taps are the dense neighbours in that sub-lattice.
+// It stages the tile and a halo of 2 in LDS (36 x 12 records, 13.5 KiB; a
+// record outside the frame is staged as one that takes no part) and reads the
+// 25 taps from there, in the same order. A one-dimensional grid: column index
+// rx * tiles_x + tile column over min(s, W) residues, row index likewise over
+// min(s, H). The variance prefilter's neighbours are at
+// distance 1, outside the sub-lattice for s >= 2: read from global memory.
+constexpr int kDnHalo = 2, kDnLdsW = kDnTileW + 2 * kDnHalo, kDnLdsH = kDnTileH + 2 * kDnHalo;
+template <bool LAST>
+__global__ __launch_bounds__(kPostBlock) void denoise_tiled_kernel(const DnArgs d, unsigned tiles_x, unsigned tiles_y,
+                                                                   unsigned cols) {
+    __shared__ float4 la[kDnLdsH * kDnLdsW], lb[kDnLdsH * kDnLdsW];
+    const unsigned gy = blockIdx.x / cols, gx = blockIdx.x - gy * cols;
+    const int rx = (int)(gx / tiles_x), ry = (int)(gy / tiles_y);
+    // (64-bit: tile origin plus halo may pass 2^31 on a frame that long)
+    const long long u0 = (long long)(gx - rx * tiles_x) * kDnTileW, v0 = (long long)(gy - ry * tiles_y) * kDnTileH;
+    // (uniform: the whole workgroup leaves before the barrier)
+    if ((long long)rx + (long long)d.s * u0 >= d.W || (long long)ry + (long long)d.s * v0 >= d.H) return;
+    for (int k = threadIdx.x; k < kDnLdsH * kDnLdsW; k += kPostBlock) {
+        const int lv = k / kDnLdsW, lu = k - lv * kDnLdsW;
+        const long long xx = (long long)rx + (long long)d.s * (u0 + lu - kDnHalo);
+        const long long yy = (long long)ry + (long long)d.s * (v0 + lv - kDnHalo);
+        float4 qa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), qb = make_float4(0.0f, 0.0f, 0.0f, u2f(kDnSkip));
+        if (xx >= 0 && xx < d.W && yy >= 0 && yy < d.H) {
+            const size_t q = (size_t)yy * d.W + (size_t)xx;
+            qa = d.in[2 * q];
+            qb = d.in[2 * q + 1];
+        }
+        la[k] = qa;
+        lb[k] = qb;
+    }
+    __syncthreads();
+    const int tu = threadIdx.x & (kDnTileW - 1), tv = threadIdx.x / kDnTileW;
+    const long long xl = (long long)rx + (long long)d.s * (u0 + tu), yl = (long long)ry + (long long)d.s * (v0 + tv);
+    if (xl >= d.W || yl >= d.H) return;
+    const int x = (int)xl, y = (int)yl;
+    const size_t i = (size_t)y * d.W + x;
+    const int lc = (tv + kDnHalo) * kDnLdsW + tu + kDnHalo;
+    const float4 a = la[lc], b = lb[lc];
+    if (f2u(b.w) == kDnSkip) {
+        dn_store_<LAST>(d, i, a, b, false, 0.0f, u2f(kDnSkip));
+        return;
+    }
+    float gs = 0.0f, gw = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= d.H) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= d.W) continue;
+            const float vq = d.in[2 * ((size_t)yy * d.W + xx) + 1].w;
+            if (f2u(vq) == kDnSkip) continue;
+            const float g = (dx == 0 && dy == 0) ? 0.25f : ((dx == 0 || dy == 0) ? 0.125f : 0.0625f);
+            gs += g * vq;
+            gw += g;
+        }
+    }
+    const float den = d.sigma_l * sqrt_(div_(gs, gw)) + 0x1p-20f;
+    float sw = 0.0f, sc = 0.0f, sv = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int lq = lc + dy * kDnLdsW + dx;
+            const float4 qb = lb[lq];
+            if (f2u(qb.w) == kDnSkip) continue;
+            dn_tap_(a, b, la[lq], qb, dn_hk_(dx) * dn_hk_(dy), den, d.sigma_z, d.npow, sw, sc, sv);
+        }
+    }
+    float col, var;
+    dn_finish_(a, b, sw, sc, sv, col, var);
+    dn_store_<LAST>(d, i, a, b, true, col, var);
+}
+
 // powf_'s stated domain for y (ipt_math.h)
 bool powf_y_ok(float y) { return isfinite_(y) && y > 0.0f && y != std::trunc(y); }
 
@@ -767,6 +1023,41 @@ int pgm_check(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const 
                                       "ipt_pgm: contrast finite and > 1, gamma finite, > 0 and no integer");
     return IPT_OK;
 }
+
+// the argument rules of ipt_denoise / ipt_denoise_device (ipt_capi.h)
+int denoise_check(ipt_ctx* ctx, const ipt_denoise_params* p, const float* pixels, const uint32_t* counters,
+                  const float* m2, const ipt_guide* guides, const float* out, const float* var_out) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!p || !pixels || !counters || !m2 || !guides || !out || p->width <= 0 || p->height <= 0 ||
+        p->iterations < 1 || p->iterations > 6 || p->normal_pow < 0 || p->normal_pow > 7 || !(p->sigma_l > 0.0f) ||
+        !(p->sigma_z > 0.0f))
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID,
+                                      "ipt_denoise: bad arguments (iterations 1..6, normal_pow 0..7, sigmas > 0)");
+    if ((long long)p->width * p->height > (1ll << 31))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_denoise: at most 2^31 pixels");
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    const void* buf[6] = {pixels, counters, m2, guides, out, var_out};
+    const size_t len[6] = {n * 4, n * 4, n * 4, n * sizeof(ipt_guide), n * 4, n * 4};
+    for (int a = 0; a < 6; ++a)
+        for (int b = std::max(a + 1, 4); b < 6; ++b)  // every pair with an output in it
+            if (overlap_(buf[a], len[a], buf[b], len[b]))
+                return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_denoise: an output overlaps another buffer");
+    return IPT_OK;
+}
+
+// Which tap-loop form an iteration runs. IPT_DENOISE_FORM=direct / tiled
+// (diagnostics, the A/B of scripts/denoise_bench.py) forces one for every
+// step; otherwise the measured choice (DESIGN.md "Denoising").
+constexpr int kDnAuto = 0, kDnDirect = 1, kDnTiled = 2;
+constexpr int kDnTiledMaxStep = 8;  // auto: steps up to here run the tiled form, larger ones the direct form
+int denoise_form() {
+    const char* e = std::getenv("IPT_DENOISE_FORM");
+    if (!e) return kDnAuto;
+    return std::strcmp(e, "direct") == 0 ? kDnDirect : (std::strcmp(e, "tiled") == 0 ? kDnTiled : kDnAuto);
+}
+struct DnRecord {
+    float4 a, b;
+};
 
 // The PGM path's share of the context's scratch: the scalars and, where a call
 // needs a plane of its own, `processed`. Only the first call or a larger image
@@ -1196,6 +1487,124 @@ int ipt_adapt_device(ipt_ctx* ctx, const ipt_adapt_params* p, const float* dev_p
     return IPT_OK;
 }
 
+int ipt_denoise_device(ipt_ctx* ctx, const ipt_denoise_params* p, const float* dev_pixels, const uint32_t* dev_counters,
+                       const float* dev_m2, const ipt_guide* dev_guides, float* dev_out, float* dev_var_out,
+                       void* hip_stream) {
+    if (const int rc = denoise_check(ctx, p, dev_pixels, dev_counters, dev_m2, dev_guides, dev_out, dev_var_out))
+        return rc;
+    const int W = p->width, H = p->height;
+    const size_t n = (size_t)W * (size_t)H;
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    if (!S.done || n > S.denoise_cap) {
+        // (first call or a larger frame: the only path that allocates or waits)
+        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
+        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+        if (n > S.denoise_cap)
+            if (const int rc = post_grow(ctx, S.denoise, S.denoise_cap, n, 2 * sizeof(DnRecord))) return rc;
+    }
+    // the scratch is shared: a call on another stream runs after the previous one
+    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
+    float4* rec[2] = {static_cast<float4*>(S.denoise), static_cast<float4*>(S.denoise) + 2 * S.denoise_cap};
+    // (diagnostics: an event after every pass, read by ipt_denoise_pass_ms)
+    const char* prof = std::getenv("IPT_DENOISE_PROFILE");
+    const bool timed = prof && std::atoi(prof) != 0;
+    S.denoise_timed = 0;
+    if (timed) {
+        for (hipEvent_t& e : S.denoise_ev)
+            if (!e) POSTCHECK(ctx, hipEventCreate(&e));
+        POSTCHECK(ctx, hipEventRecord(S.denoise_ev[0], st));
+    }
+    hipLaunchKernelGGL(denoise_prepare_kernel, dim3((unsigned)((n + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0,
+                       st, dev_pixels, dev_counters, dev_m2, reinterpret_cast<const uint32_t*>(dev_guides), rec[0],
+                       (long long)n);
+    if (timed) POSTCHECK(ctx, hipEventRecord(S.denoise_ev[1], st));
+    const int form = denoise_form();
+    for (int k = 0; k < p->iterations; ++k) {
+        const bool last = k == p->iterations - 1;
+        DnArgs d{};
+        d.in = rec[k & 1];
+        d.out_rec = rec[(k & 1) ^ 1];
+        d.W = W;
+        d.H = H;
+        d.s = 1 << k;
+        d.npow = p->normal_pow;
+        d.sigma_l = p->sigma_l;
+        d.sigma_z = p->sigma_z;
+        d.pixels = reinterpret_cast<const uint32_t*>(dev_pixels);
+        d.counters = dev_counters;
+        d.m2 = dev_m2;
+        d.out = dev_out;
+        d.var_out = dev_var_out;
+        if (form == kDnTiled || (form == kDnAuto && d.s <= kDnTiledMaxStep)) {
+            // the sub-lattice of a residue has ceil(W / s) x ceil(H / s) pixels at most
+            // (64-bit: W or H may be within a tile of 2^31)
+            const unsigned tx = (unsigned)((((long long)W + d.s - 1) / d.s + kDnTileW - 1) / kDnTileW);
+            const unsigned ty = (unsigned)((((long long)H + d.s - 1) / d.s + kDnTileH - 1) / kDnTileH);
+            const unsigned cols = tx * (unsigned)std::min(d.s, W), rows = ty * (unsigned)std::min(d.s, H);
+            if (last)
+                hipLaunchKernelGGL(denoise_tiled_kernel<true>, dim3(cols * rows), dim3(kPostBlock), 0, st, d, tx, ty, cols);
+            else
+                hipLaunchKernelGGL(denoise_tiled_kernel<false>, dim3(cols * rows), dim3(kPostBlock), 0, st, d, tx, ty, cols);
+        } else {
+            const unsigned tx = (unsigned)(((long long)W + kDnTileW - 1) / kDnTileW);
+            const unsigned ty = (unsigned)(((long long)H + kDnTileH - 1) / kDnTileH);
+            if (last)
+                hipLaunchKernelGGL(denoise_direct_kernel<true>, dim3(tx * ty), dim3(kPostBlock), 0, st, d, tx);
+            else
+                hipLaunchKernelGGL(denoise_direct_kernel<false>, dim3(tx * ty), dim3(kPostBlock), 0, st, d, tx);
+        }
+        if (timed) POSTCHECK(ctx, hipEventRecord(S.denoise_ev[2 + k], st));
+    }
+    if (timed) S.denoise_timed = p->iterations;
+    POSTCHECK(ctx, hipGetLastError());
+    POSTCHECK(ctx, hipEventRecord(S.done, st));
+    S.used = true;
+    S.last_stream = st;
+    return IPT_OK;
+}
+
+int ipt_denoise_pass_ms(ipt_ctx* ctx, float* ms) {
+    if (!ctx) return IPT_E_INVALID;
+    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+    if (!ms || S.denoise_timed <= 0)
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID,
+                                      "ipt_denoise_pass_ms: no ipt_denoise_device call under IPT_DENOISE_PROFILE=1");
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    POSTCHECK(ctx, hipEventSynchronize(S.denoise_ev[1 + S.denoise_timed]));
+    for (int k = 0; k < 7; ++k) ms[k] = 0.0f;
+    for (int k = 0; k <= S.denoise_timed; ++k)
+        POSTCHECK(ctx, hipEventElapsedTime(&ms[k], S.denoise_ev[k], S.denoise_ev[k + 1]));
+    return IPT_OK;
+}
+
+int ipt_denoise(ipt_ctx* ctx, const ipt_denoise_params* p, const float* pixels, const uint32_t* counters,
+                const float* m2, const ipt_guide* guides, float* out, float* var_out) {
+    if (const int rc = denoise_check(ctx, p, pixels, counters, m2, guides, out, var_out)) return rc;
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    hipStream_t st = ipt_internal::ctx_stream(ctx);
+    const size_t n = (size_t)p->width * p->height;
+    DevBuf<float> dpx, dm2, dout, dvar;
+    DevBuf<uint32_t> dcnt;
+    DevBuf<ipt_guide> dg;
+    POSTCHECK(ctx, hipMalloc(&dpx.p, n * sizeof(float)));
+    POSTCHECK(ctx, hipMalloc(&dcnt.p, n * sizeof(uint32_t)));
+    POSTCHECK(ctx, hipMalloc(&dm2.p, n * sizeof(float)));
+    POSTCHECK(ctx, hipMalloc(&dg.p, n * sizeof(ipt_guide)));
+    POSTCHECK(ctx, hipMalloc(&dout.p, n * sizeof(float)));
+    if (var_out) POSTCHECK(ctx, hipMalloc(&dvar.p, n * sizeof(float)));
+    POSTCHECK(ctx, hipMemcpyAsync(dpx.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
+    POSTCHECK(ctx, hipMemcpyAsync(dcnt.p, counters, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    POSTCHECK(ctx, hipMemcpyAsync(dm2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, st));
+    POSTCHECK(ctx, hipMemcpyAsync(dg.p, guides, n * sizeof(ipt_guide), hipMemcpyHostToDevice, st));
+    if (const int rc = ipt_denoise_device(ctx, p, dpx.p, dcnt.p, dm2.p, dg.p, dout.p, dvar.p, st)) return rc;
+    POSTCHECK(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (var_out) POSTCHECK(ctx, hipMemcpyAsync(var_out, dvar.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    POSTCHECK(ctx, hipStreamSynchronize(st));
+    return IPT_OK;
+}
+
 int ipt_pgm(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const float* pixel_max, float* smoothed,
             uint8_t* gray8, float* stats) {
     if (const int rc = pgm_check(ctx, p, pixels, pixel_max, smoothed, gray8, stats)) return rc;
@@ -1299,9 +1708,19 @@ int post_wait(ipt_ctx* ctx) {
 
 void post_release(ipt_ctx* ctx) {
     PostScratch& S = ctx_post(ctx);
-    for (void* b : {S.bright, (void*)S.blocks, S.scalars, S.stats, S.pgm, (void*)S.processed, (void*)S.tone})
+    for (void* b : {S.bright, (void*)S.blocks, S.scalars, S.stats, S.pgm, (void*)S.processed, (void*)S.tone, S.denoise})
         if (b) (void)hipFree(b);
     if (S.done) (void)hipEventDestroy(S.done);
+    for (hipEvent_t e : S.denoise_ev)
+        if (e) (void)hipEventDestroy(e);
     S = PostScratch{};
+}
+
+hipError_t launch_guide_scatter(hipStream_t st, const uint8_t* kinds, const float* hits, ipt_guide* dev_guides, int W,
+                                int H, bool gui) {
+    const long long n = (long long)W * H;
+    hipLaunchKernelGGL(guide_scatter_kernel, dim3((unsigned)((n + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0, st,
+                       kinds, hits, reinterpret_cast<uint32_t*>(dev_guides), W, H, gui ? 1 : 0, n);
+    return hipGetLastError();
 }
 }  // namespace ipt_internal

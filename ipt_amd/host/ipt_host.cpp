@@ -510,6 +510,69 @@ AdaptResult GpuRenderer::render_adaptive(GuiRenderPlane& plane, const RenderPara
     return r;
 }
 
+namespace {
+// one unmasked round: nothing is decided from its mask
+AdaptParams one_round(const RenderParams& p) {
+    AdaptParams a;
+    a.round_spp = std::max(p.spp, 1);
+    return a;
+}
+std::vector<float> run_denoise(ipt_ctx* ctx, const std::vector<float>& pixels, const std::vector<size_t>& counters,
+                               size_t W, size_t H, const std::vector<float>& m2, const std::vector<ipt_guide>& guides,
+                               const RenderParams& p, std::vector<float>* var_out) {
+    const size_t n = W * H;
+    if (m2.size() != n || guides.size() != n)
+        throw IptError(IPT_E_INVALID, "denoise: m2 and guides must hold width*height elements");
+    std::vector<uint32_t> cnt(n);
+    for (size_t i = 0; i < n; ++i) cnt[i] = counters[i] > 0xffffffffull ? 0xffffffffu : (uint32_t)counters[i];
+    ipt_denoise_params q{};
+    q.width = (int32_t)W;
+    q.height = (int32_t)H;
+    q.iterations = p.denoise_iterations;
+    q.sigma_l = p.denoise_sigma_l;
+    q.normal_pow = p.denoise_normal_pow;
+    q.sigma_z = p.denoise_sigma_z;
+    std::vector<float> out(n);
+    if (var_out) var_out->assign(n, 0.0f);
+    check(ctx, ipt_denoise(ctx, &q, pixels.data(), cnt.data(), m2.data(), guides.data(), out.data(),
+                           var_out ? var_out->data() : nullptr));
+    return out;
+}
+}  // namespace
+
+std::vector<float> GpuRenderer::render_m2(GridRenderPlane& plane, const RenderParams& p) {
+    return render_adaptive(plane, p, one_round(p)).m2;
+}
+
+std::vector<float> GpuRenderer::render_m2(GuiRenderPlane& plane, const RenderParams& p) {
+    return render_adaptive(plane, p, one_round(p)).m2;
+}
+
+std::vector<ipt_guide> GpuRenderer::guides(size_t width, size_t height, const RenderParams& p, bool gui_plane) {
+    RenderParams one = p;
+    one.spp = 1;
+    one.counters = one.compact = false;
+    one.n_shards = 1;
+    const ipt_params q = to_params(width, height, one, gui_plane ? IPT_FLAG_GUI_PLANE : 0);
+    std::vector<ipt_guide> g(width * height);
+    check(ctx_, ipt_guides(ctx_, &q, g.data()));
+    return g;
+}
+
+std::vector<float> GpuRenderer::denoise(const GridRenderPlane& plane, const std::vector<float>& m2,
+                                        const std::vector<ipt_guide>& guides, const RenderParams& p,
+                                        std::vector<float>* var_out) {
+    check_plane(plane);
+    return run_denoise(ctx_, plane.pixels, plane.pixel_counters, plane.width, plane.height, m2, guides, p, var_out);
+}
+
+std::vector<float> GpuRenderer::denoise(const GuiRenderPlane& plane, const std::vector<float>& m2,
+                                        const std::vector<ipt_guide>& guides, const RenderParams& p,
+                                        std::vector<float>* var_out) {
+    check_plane(plane);
+    return run_denoise(ctx_, plane.pixels, plane.value_counter, plane.width, plane.height, m2, guides, p, var_out);
+}
+
 void GpuRenderer::transfer_bytes(uint64_t* host_to_device, uint64_t* device_to_host) const {
     check(ctx_, ipt_transfer_bytes(ctx_, host_to_device, device_to_host));
 }

@@ -203,6 +203,15 @@ struct RenderParams {
     // 4.16 has what it costs. Every render call below takes it; no effect
     // with preview.
     bool compact = false;
+    // the guided a-trous filter of GpuRenderer::denoise (ipt_denoise): its
+    // iterations (1..6, iteration k taps at step 1 << k; 0: no filter is
+    // asked for) and sigmas: colour in standard errors, squarings of the
+    // normals' clamped dot product, distance from the centre's plane in world
+    // units. No render call reads them.
+    int denoise_iterations = 0;
+    float denoise_sigma_l = 4.0f;
+    int denoise_normal_pow = 5;
+    float denoise_sigma_z = 0.1f;
     // destination-row tile shard of this call (ipt_params.tile_rows / n_shards /
     // shard_id): n_shards <= 1 renders the whole frame
     int tile_rows = 16;
@@ -260,6 +269,29 @@ class GpuRenderer {
     // is continued as render() continues it; the second moments start at zero.
     AdaptResult render_adaptive(GridRenderPlane& plane, const RenderParams& p, const AdaptParams& a);
     AdaptResult render_adaptive(GuiRenderPlane& plane, const RenderParams& p, const AdaptParams& a);
+    // p.spp unmasked passes through the masked entry point, which keeps the
+    // second moments the filter below needs (one round of ipt_render_adaptive:
+    // round 0 traces every pixel; this layer holds host buffers only and
+    // links no HIP runtime, and that call is the C-ABI's host-buffer way to the
+    // masked entry point. It also runs one ipt_adapt_device pass whose mask
+    // is dropped). Returns m2; the plane is continued as render() continues
+    // it, bit for bit.
+    std::vector<float> render_m2(GridRenderPlane& plane, const RenderParams& p);
+    std::vector<float> render_m2(GuiRenderPlane& plane, const RenderParams& p);
+    // the guide plane (ipt_guides): the first hit of pass p.spp_offset's preview
+    // sample per destination pixel, [height][width], under the Grid row map or,
+    // with gui_plane, the Gui's
+    std::vector<ipt_guide> guides(size_t width, size_t height, const RenderParams& p, bool gui_plane = false);
+    // the plane's pixels filtered (ipt_denoise) with p.denoise_iterations and
+    // its sigmas, m2 (render_m2's, or AdaptResult::m2) and the guide plane;
+    // var_out, when given, gets the filtered variance of the mean. The plane
+    // itself is not changed.
+    std::vector<float> denoise(const GridRenderPlane& plane, const std::vector<float>& m2,
+                               const std::vector<ipt_guide>& guides, const RenderParams& p,
+                               std::vector<float>* var_out = nullptr);
+    std::vector<float> denoise(const GuiRenderPlane& plane, const std::vector<float>& m2,
+                               const std::vector<ipt_guide>& guides, const RenderParams& p,
+                               std::vector<float>* var_out = nullptr);
     // the same into a C-ABI image (32-bit counters); with p.n_shards > 1 only
     // the shard's rows of it are read and written (ipt_render). flags: further
     // IPT_FLAG_* bits of the call (IPT_FLAG_GUI_PLANE for a Gui plane's image,

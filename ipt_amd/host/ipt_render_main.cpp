@@ -16,7 +16,17 @@
 //              [--compact]
 //              [--histogram hist.txt [--hist-buckets 400]]
 //              [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]
+//              [--denoise K [--denoise-sigma L,N,Z]]
 //
+// --denoise K filters the rendered plane with K iterations (1..6) of the guided
+// a-trous filter (GpuRenderer::denoise, ipt_capi.h "denoising"; iteration k
+// taps at step 1 << k) before every output stage: --smooth, --glare, --pgm,
+// --gpu-display, the PNG and --pfm see the filtered pixels. --denoise-sigma
+// L,N,Z sets the colour sigma in standard errors (4), the squarings of the
+// normals' dot product (5) and the plane distance in world units (0.1). The
+// filter needs the plane's second moments: with --adaptive it takes that
+// loop's; otherwise the render runs through the masked entry point with no
+// mask (the same plane, bit for bit). One device and one batch (--passes 1).
 // --adaptive REL renders adaptively (GpuRenderer::render_adaptive): rounds of
 // --round-spp passes (4), each followed on the device by the next sample mask,
 // until no pixel is active or --spp, here the cap, is used up. A pixel stays
@@ -88,7 +98,8 @@ namespace {
                  "                  [--gpu-display] [--gui-plane] [--preview] [--white-percentile F]\n"
                  "                  [--compact]\n"
                  "                  [--histogram hist.txt [--hist-buckets 400]]\n"
-                 "                  [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]\n");
+                 "                  [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]\n"
+                 "                  [--denoise K [--denoise-sigma L,N,Z]]\n");
     std::exit(2);
 }
 }  // namespace
@@ -100,7 +111,8 @@ int main(int argc, char** argv) {
     long smooth = 0, smoothed_max = 0;
     bool gpu_display = false, gui_plane = false, preview = false, compact = false;
     double glare = -1.0, adaptive_rel = -1.0, adaptive_abs = 1e-3;
-    long min_spp = 8, round_spp = 4;
+    long min_spp = 8, round_spp = 4, denoise = 0, denoise_pow = 5;
+    double denoise_l = 4.0, denoise_z = 0.1;
     long width = 640, height = 640, spp = 16, passes = 1, n_rays = 16, depth = 8, device = 0, tile_rows = 16;
     std::vector<int> devices;
     unsigned long long seed = 20241223ull;
@@ -146,6 +158,11 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive-abs") adaptive_abs = std::atof(val());
         else if (a == "--min-spp") min_spp = std::atol(val());
         else if (a == "--round-spp") round_spp = std::atol(val());
+        else if (a == "--denoise") denoise = std::atol(val());
+        else if (a == "--denoise-sigma") {
+            if (std::sscanf(val(), "%lf,%ld,%lf", &denoise_l, &denoise_pow, &denoise_z) != 3)
+                usage("--denoise-sigma takes L,N,Z");
+        }
         else usage(("unknown option " + a).c_str());
     }
     if (width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || n_rays < 0 || depth < 0) usage("bad sizes");
@@ -160,6 +177,10 @@ int main(int argc, char** argv) {
     if (adaptive && (passes != 1 || devices.size() > 1)) usage("--adaptive renders one batch on one device");
     if (adaptive && (!(adaptive_abs >= 0.0) || min_spp < 2 || round_spp < 1))
         usage("--adaptive-abs >= 0, --min-spp >= 2, --round-spp >= 1");
+    if (denoise < 0 || denoise > 6) usage("--denoise takes 1..6 iterations");
+    if (denoise > 0 && (passes != 1 || devices.size() > 1)) usage("--denoise filters one batch on one device");
+    if (denoise > 0 && (!(denoise_l > 0.0) || !(denoise_z > 0.0) || denoise_pow < 0 || denoise_pow > 7))
+        usage("--denoise-sigma: L > 0, N in 0..7, Z > 0");
     try {
         const ipt::Scene scene = ipt::make_scene_by_name(scene_name);
         if (devices.empty()) devices.push_back((int)device);
@@ -178,6 +199,11 @@ int main(int argc, char** argv) {
         p.seed = seed;
         p.preview = preview;
         p.compact = compact;
+        p.denoise_iterations = (int)denoise;
+        p.denoise_sigma_l = (float)denoise_l;
+        p.denoise_normal_pow = (int)denoise_pow;
+        p.denoise_sigma_z = (float)denoise_z;
+        std::vector<float> m2;
         double kernel_ms = 0.0;
         ipt::AdaptResult ar;
         const auto t0 = std::chrono::steady_clock::now();
@@ -188,8 +214,11 @@ int main(int argc, char** argv) {
             ad.min_count = (int)min_spp;
             ad.round_spp = (int)round_spp;
             ar = gui_plane ? gpu.render_adaptive(gui, p, ad) : gpu.render_adaptive(plane, p, ad);
+            m2 = ar.m2;
+        } else if (denoise > 0) {
+            m2 = gui_plane ? gpu.render_m2(gui, p) : gpu.render_m2(plane, p);
         }
-        for (long pass = 0; pass < passes && !adaptive; ++pass) {  // progressive: each batch continues the RNG stream
+        for (long pass = 0; pass < passes && !adaptive && denoise == 0; ++pass) {  // progressive: each batch continues the RNG stream
             p.spp_offset = (int)(pass * spp);
             if (gui_plane) gpus.render(gui, p);
             else gpus.render(plane, p);
@@ -206,6 +235,8 @@ int main(int argc, char** argv) {
             // (the Gui keeps no max_value; the JSON line reports the plane's largest pixel)
             for (float v : plane.pixels) plane.max_value = v > plane.max_value ? v : plane.max_value;
         }
+        if (denoise > 0)  // (the plane holds either map's pixels by now; the guides follow the map)
+            plane.pixels = gpu.denoise(plane, m2, gpu.guides(plane.width, plane.height, p, gui_plane), p);
         if (smooth > 0) gpu.smooth(plane, (size_t)smooth);
         if (glare >= 0.0 && !glare_out.empty()) {
             ipt::GridRenderPlane g(plane.width, plane.height);
