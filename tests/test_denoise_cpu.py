@@ -1,7 +1,10 @@
 """The denoiser's restatement (tests/denoise_cases.py) without a GPU: it tells
 the wrong variants apart on pinned cases, keeps what the filter must keep,
 reduces the error of a 4-pass frame against the oracle's own 256-pass plane,
-and the header, the binding and the library agree on the new entry points.
+and the header, the binding and the library agree on the new entry points;
+on which frames a tap leaves its lattice tile (the seam variants), which
+planes leave the windows of the range-free division and root or hold
+denormals (the operand census), and that the edge planes do not degenerate.
 Oracle and preview restatement only."""
 import ctypes as C
 import re
@@ -191,3 +194,259 @@ def test_header_binding_and_library_agree():
         assert re.search(r"^int\s+%s\s*\(" % s, hdr, re.M), s
         assert s in capi.EXPORTED_SYMBOLS and s in exported and hasattr(lib, s)
     assert lib.ipt_abi_version() == 7
+
+
+# ---- lattice tiles ---------------------------------------------------------------------------
+# pixels whose (colour, variance) differ from the restatement's under ("seam",
+# axis, S): dn.random_plane(W, H, 6) on dn.crease_guides, 6 iterations, sigma_l
+# 6. Pinned where the frame spans two tiles at that step (dn.spans_two_tiles);
+# everywhere else no tap leaves its tile and the variant is the restatement.
+SEAM_COUNTS = {
+    (300, 75): {("x", 4): (14069, 14417), ("x", 8): (7005, 7104), ("y", 4): (21014, 21022), ("y", 8): (17097, 17205)},
+    (1061, 9): {("x", 4): (5242, 5403), ("x", 8): (2111, 2144), ("x", 16): (686, 688), ("x", 32): (247, 247)},
+    (9, 277): {("y", 4): (2071, 2081), ("y", 8): (1704, 1711), ("y", 16): (902, 906), ("y", 32): (163, 163)},
+    (1061, 277): {("x", 4): (249190, 252906), ("x", 8): (132346, 134745), ("x", 16): (43896, 44058),
+                  ("x", 32): (15287, 15301), ("y", 4): (278426, 278477), ("y", 8): (269533, 270053),
+                  ("y", 16): (189733, 190293), ("y", 32): (37665, 37706)},
+    # the largest frame before SEAM_FRAMES: one tile column from step 8, one tile row from step 16
+    (131, 67): {("x", 4): (2855, 2930), ("y", 4): (7976, 7991), ("y", 8): (3376, 3441)},
+}
+
+
+def _seam_counts(W, H):
+    """{(axis, S): differing (colour, variance)}; a variant goes on from the
+    restatement's own plane before step S, where it first applies."""
+    px, cn, m2 = dn.random_plane(W, H, 6)
+    g = dn.crease_guides(W, H)
+    kw = dict(iterations=6, sigma_l=6.0)
+    trace = []
+    ref = dn.denoise(px, cn, m2, g, W, H, trace=trace, **kw)
+    got = {}
+    for axis in "xy":
+        for S in dn.SEAM_STEPS:
+            k = S.bit_length() - 1
+            out = dn.denoise(px, cn, m2, g, W, H, wrong=("seam", axis, S), resume=(k,) + trace[k - 1], **kw)
+            got[axis, S] = (int((~dn.same(ref[0], out[0])).sum()), int((~dn.same(ref[1], out[1])).sum()))
+    return got
+
+
+@pytest.mark.parametrize("frame", sorted(SEAM_COUNTS), ids=lambda f: "%dx%d" % f)
+def test_dropping_the_taps_of_another_tile_shows_where_a_frame_spans_two(frame):
+    W, H = frame
+    got = _seam_counts(W, H)
+    for (axis, S), n in got.items():
+        if dn.spans_two_tiles(W, H, axis, S):
+            assert n == SEAM_COUNTS[frame][axis, S] and n[0] > 0, (axis, S, n)
+        else:
+            assert n == (0, 0) and (axis, S) not in SEAM_COUNTS[frame], (axis, S, n)
+    if frame == (131, 67):  # what the frames before SEAM_FRAMES could not see
+        assert got["x", 8] == got["x", 16] == got["y", 16] == (0, 0)
+    else:
+        assert frame in dn.SEAM_FRAMES
+
+
+def test_resuming_a_trace_is_the_whole_run():
+    W, H = 67, 35
+    px, cn, m2 = dn.random_plane(W, H, 6)
+    g = dn.crease_guides(W, H)
+    trace = []
+    ref = dn.denoise(px, cn, m2, g, W, H, iterations=4, sigma_l=6.0, trace=trace)
+    assert len(trace) == 4 and np.array_equal(trace[3][0].reshape(-1).view(np.uint32), ref[0].view(np.uint32))
+    for wrong in (None, ("seam", "y", 4)):
+        whole = dn.denoise(px, cn, m2, g, W, H, iterations=4, sigma_l=6.0, wrong=wrong)
+        part = dn.denoise(px, cn, m2, g, W, H, iterations=4, sigma_l=6.0, wrong=wrong, resume=(2,) + trace[1])
+        assert dn.same(whole[0], part[0]).all() and dn.same(whole[1], part[1]).all()
+    assert not dn.same(whole[0], ref[0]).all()
+
+
+# ---- values outside the window ---------------------------------------------------------------
+# dn.denoise's census of each dn.EDGE_CASES plane, 67 x 35: per operation
+# (evaluations, with an operand outside the window of ipt_math.h's range-free
+# division / root, with a denormal operand or result)
+EDGE_CENSUS = {
+    "colour_e-70": {"var0": (2214, 2205, 2205), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 132030, 0),
+                    "sc/sw": (6642, 6642, 0), "sv/sw2": (6642, 155, 155), "sqrt": (6642, 2088, 2088)},
+    "colour_e-64": {"var0": (2214, 2214, 2214), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 132030, 0),
+                    "sc/sw": (6642, 6642, 0), "sv/sw2": (6642, 6642, 6642), "sqrt": (6642, 6642, 6642)},
+    "colour_e-50": {"var0": (2214, 2214, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 132030, 0),
+                    "sc/sw": (6642, 6642, 0), "sv/sw2": (6642, 6642, 0), "sqrt": (6642, 6642, 0)},
+    "colour_e45": {"var0": (2214, 2214, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 138672, 0),
+                   "sc/sw": (6642, 5509, 0), "sv/sw2": (6642, 6642, 0), "sqrt": (6642, 0, 0)},
+    "colour_e63": {"var0": (2214, 2214, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 138672, 0),
+                   "sc/sw": (6642, 6642, 0), "sv/sw2": (6642, 6642, 0), "sqrt": (6642, 0, 0)},
+    "colour_e-70_it1": {"var0": (2214, 2205, 2205), "e/sigma_z": (49682, 0, 0), "dc/den": (49682, 47468, 0),
+                        "sc/sw": (2214, 2214, 0), "sv/sw2": (2214, 155, 155), "sqrt": (2214, 2082, 2082)},
+    "colour_e-64_it5": {"var0": (2214, 2214, 2214), "e/sigma_z": (188016, 0, 0), "dc/den": (188016, 176946, 0),
+                        "sc/sw": (11070, 11070, 0), "sv/sw2": (11070, 7376, 7376), "sqrt": (11070, 9565, 9565)},
+    "colour_e63_it5": {"var0": (2214, 2214, 0), "e/sigma_z": (188016, 0, 0), "dc/den": (188016, 188016, 0),
+                       "sc/sw": (11070, 11070, 0), "sv/sw2": (11070, 11070, 0), "sqrt": (11070, 0, 0)},
+    "world_e-140": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 138672, 138672), "dc/den": (138672, 0, 0),
+                    "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "world_e-120": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 138672, 0), "dc/den": (138672, 0, 0),
+                    "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "world_e-45": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 138672, 0), "dc/den": (138672, 0, 0),
+                   "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "world_e45": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 138672, 0), "dc/den": (138672, 0, 0),
+                  "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "world_e60": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 138672, 0), "dc/den": (138672, 0, 0),
+                  "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "sigma_l_inf": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 138672, 0),
+                    "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "sigma_l_3e38": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 138672, 77350),
+                     "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "sigma_l_1e-45": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 0, 0),
+                      "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "sigma_z_inf": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 138672, 0), "dc/den": (138672, 0, 0),
+                    "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "sigma_z_3e38": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 138672, 4725), "dc/den": (138672, 0, 0),
+                     "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "sigma_z_1e-45": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 138672, 138672), "dc/den": (138672, 0, 0),
+                      "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "normal_e-30_pow0": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 0, 0),
+                         "sc/sw": (6642, 6642, 0), "sv/sw2": (6642, 6642, 6642), "sqrt": (6642, 0, 0)},
+    "normal_e10_pow0": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 0, 0),
+                        "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "normal_e-32_pow1": {"var0": (2214, 0, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 88990, 0),
+                         "sc/sw": (2214, 2214, 2214), "sv/sw2": (2214, 2214, 0), "sqrt": (6642, 4428, 0)},
+    "counters_2p24": {"var0": (2214, 2214, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 0, 0),
+                      "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "counters_2p31": {"var0": (2214, 2214, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 0, 0),
+                      "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+    "counters_mix": {"var0": (2214, 1652, 0), "e/sigma_z": (138672, 0, 0), "dc/den": (138672, 0, 0),
+                     "sc/sw": (6642, 0, 0), "sv/sw2": (6642, 0, 0), "sqrt": (6642, 0, 0)},
+}
+# what each plane is there for: (operation, 1 = outside the window / 2 = denormal).
+# normal_e10_pow0 is there for weights of about 2^20, which stay inside every
+# window, and sigma_l_1e-45 for a ramp of 2^-20 that stops nearly every tap.
+EDGE_THERE_FOR = {
+    "colour_e-70": (("sqrt", 2), ("var0", 2)), "colour_e-64": (("sv/sw2", 2), ("sqrt", 2)),
+    "colour_e-50": (("sqrt", 1),), "colour_e45": (("dc/den", 1), ("sc/sw", 1)),
+    "colour_e63": (("dc/den", 1), ("sc/sw", 1)), "colour_e-70_it1": (("sqrt", 2), ("sv/sw2", 2)),
+    "colour_e-64_it5": (("sv/sw2", 2), ("sqrt", 2)), "colour_e63_it5": (("dc/den", 1), ("sc/sw", 1)),
+    "world_e-140": (("e/sigma_z", 2),), "world_e-120": (("e/sigma_z", 1),), "world_e-45": (("e/sigma_z", 1),),
+    "world_e45": (("e/sigma_z", 1),), "world_e60": (("e/sigma_z", 1),),
+    "sigma_l_inf": (("dc/den", 1),), "sigma_l_3e38": (("dc/den", 1),), "sigma_l_1e-45": (),
+    "sigma_z_inf": (("e/sigma_z", 1),), "sigma_z_3e38": (("e/sigma_z", 1),), "sigma_z_1e-45": (("e/sigma_z", 2),),
+    "normal_e-30_pow0": (("sv/sw2", 2),), "normal_e10_pow0": (), dn.EDGE_OVERFLOW: (("sc/sw", 2), ("sv/sw2", 1)),
+    "counters_2p24": (("var0", 1),), "counters_2p31": (("var0", 1),), "counters_mix": (("var0", 1),),
+}
+# the census of box_plane(131, 67) on box_guides, 6 iterations, the defaults:
+# a rendered plane does leave the windows (dark pixels with tiny variances)
+BOX_CENSUS_131x67 = {"var0": (8646, 0, 0), "e/sigma_z": (656808, 0, 0), "dc/den": (656808, 634, 0),
+                     "sc/sw": (37116, 252, 0), "sv/sw2": (37116, 880, 16), "sqrt": (37116, 8, 5)}
+# pixels whose (colour, variance) differ from the restatement's under each
+# dn.WRONG_EDGES variant, by plane; "random" is dn.random_plane(67, 35, 3) on
+# crease guides, 3 iterations, sigma_l 6. At 2^-70 every variance is 0 after
+# two iterations and den is 2^-20 whatever the root: three iterations cannot
+# show a flushed denormal there, one iteration does.
+WRONG_EDGES_COUNTS = {
+    "daz": {"random": (0, 0), "colour_e-64": (0, 2214), "colour_e-70": (0, 0), "colour_e-70_it1": (0, 155),
+            "sigma_z_1e-45": (2214, 2214), "world_e-140": (2214, 2214), "normal_e-30_pow0": (2213, 2214)},
+    "signed_counter": {"random": (0, 0), "counters_2p24": (0, 0), "counters_2p31": (2214, 2214),
+                       "counters_mix": (2214, 2214)},
+}
+
+
+def _edge(name):
+    if name == "random":
+        return dn.random_plane(67, 35, dn.EDGE_SEED) + (dn.crease_guides(67, 35), dict(iterations=3, sigma_l=6.0))
+    return dn.edge_case(name)
+
+
+@pytest.mark.parametrize("name", dn.EDGE_CASES)
+def test_edge_planes_leave_the_windows_and_do_not_degenerate(name):
+    W, H = 67, 35
+    px, cn, m2, g, kw = dn.edge_case(name)
+    census = {}
+    out, var = dn.denoise(px, cn, m2, g, W, H, census=census, **kw)
+    plain = dn.denoise(px, cn, m2, g, W, H, **kw)  # the census changes no result
+    assert dn.same(out, plain[0]).all() and dn.same(var, plain[1]).all()
+    assert np.array_equal(dn.var0_of(cn, m2, census={}).view(np.uint32), dn.var0_of(cn, m2).view(np.uint32))
+    assert {k: tuple(v) for k, v in census.items()} == EDGE_CENSUS[name]
+    for op, column in EDGE_THERE_FOR[name]:
+        assert census[op][column] >= 100, (op, column)
+    part = dn.participation(px, cn, m2, g.reshape(-1))
+    n = int(part.sum())
+    assert n == 2214
+    changed = int((~dn.same(out, px))[part].sum())
+    bad = int((~(np.isfinite(out) & np.isfinite(var)))[part].sum())
+    if name == dn.EDGE_OVERFLOW:  # sv / 0 on every pixel: no variance is finite, every colour is
+        assert changed == n and np.isfinite(out).all() and not np.isfinite(var[part]).any()
+    elif name == "sigma_l_1e-45":
+        assert changed == 199 and bad == 0
+    else:
+        assert 2 * changed >= n and 10 * bad <= n, (changed, bad)
+
+
+def test_the_planes_before_the_edge_planes_stay_inside_every_window():
+    """dn.random_plane and dn.two_level_plane: no operand of the six operations
+    is outside its window and none is denormal. The rendered box plane has
+    some of each; pinned."""
+    W, H = 67, 35
+    for (px, cn, m2), g in ((dn.random_plane(W, H, 5), dn.crease_guides(W, H)),
+                            (dn.random_plane(W, H, 3), dn.step_guides(W, H)),
+                            (dn.two_level_plane(W, H), dn.step_guides(W, H))):
+        census = {}
+        dn.denoise(px, cn, m2, g, W, H, iterations=5, sigma_l=6.0, census=census)
+        assert set(census) == set(dn.OPS)
+        for op, (n, outside, denormal) in census.items():
+            assert n > 2000 and outside == 0 and denormal == 0, op
+    W, H = 131, 67
+    img, m2 = dn.box_plane(W, H)
+    census = {}
+    dn.denoise(img["pixels"], img["counters"], m2, dn.box_guides(W, H), W, H, iterations=6, census=census)
+    assert {k: tuple(v) for k, v in census.items()} == BOX_CENSUS_131x67
+
+
+@pytest.mark.parametrize("wrong,name", [(w, n) for w in dn.WRONG_EDGES for n in WRONG_EDGES_COUNTS[w]])
+def test_restatement_differs_from_each_edge_variant(wrong, name):
+    px, cn, m2, g, kw = _edge(name)
+    ref = dn.denoise(px, cn, m2, g, 67, 35, **kw)
+    out = dn.denoise(px, cn, m2, g, 67, 35, wrong=wrong, **kw)
+    got = (int((~dn.same(ref[0], out[0])).sum()), int((~dn.same(ref[1], out[1])).sum()))
+    assert got == WRONG_EDGES_COUNTS[wrong][name]
+
+
+def test_counter_planes_round_and_pass_two_to_the_31():
+    for key, vals in dn.COUNTER_SETS.items():
+        px, cn, m2 = dn.counter_plane(67, 35, dn.EDGE_SEED, vals)
+        assert set(np.unique(cn)) == set(vals) | {1}
+        v0 = dn.var0_of(cn, m2)
+        assert np.isfinite(v0).all() and (v0[cn >= 2] < 0.25).all() and np.median(v0[cn >= 2]) > 0.05
+    assert np.float32(np.uint32(2 ** 24 + 1)) == 2 ** 24 and np.float32(np.uint32(2 ** 32 - 1)) == 2 ** 32
+
+
+def test_guides_that_are_no_numbers_stay_local():
+    """NaN (quiet and signalling) and infinite positions and NaN normals: every
+    tap of the pixel, its own included, has weight 0, so it keeps its colour;
+    nothing beyond the filter's reach 2 (2^iterations - 1) changes; and with
+    no infinite normal every colour stays finite. An infinite normal makes
+    NaN (inf * 0) on its pixel and the taps that reach it, nowhere else."""
+    W, H = 67, 35
+    px, cn, m2 = dn.random_plane(W, H, dn.EDGE_SEED)
+    g0 = dn.crease_guides(W, H)
+    part0 = dn.participation(px, cn, m2, g0.reshape(-1))
+    # (three iterations reach 14 pixels and leave 18 of this frame's out of reach, two reach 6)
+    for it, infinite_normals in ((3, False), (3, True), (2, False), (2, True)):
+        kw = dict(iterations=it, sigma_l=6.0)
+        clean = dn.denoise(px, cn, m2, g0, W, H, **kw)
+        r = 2 * (2 ** it - 1)
+        g, where, kinds = dn.poisoned_guides(g0, part0, infinite_normals)
+        assert len(where) == (6 if infinite_normals else 4) and len(kinds) == 6
+        assert g["pos"].view(np.uint32).reshape(-1, 3)[where["pos_snan"], 1] == 0x7f800001
+        part = dn.participation(px, cn, m2, g.reshape(-1))
+        assert {k: bool(part[i]) for i, k in kinds.items()} == {0: False, 2: False, 3: False, 0x81: True, 0xfd: True,
+                                                                 0xfe: False}
+        assert part[list(where.values())].all()
+        out, var = dn.denoise(px, cn, m2, g, W, H, **kw)
+        kept = [where[k] for k in ("pos_nan", "pos_snan", "normal_nan", "pos_inf")]
+        assert np.array_equal(out[kept].view(np.uint32), px[kept].view(np.uint32))
+        far = ~dn.reach(W, H, list(where.values()) + list(kinds), r)
+        assert far.sum() >= (18 if it == 3 else 300) and dn.same(out, clean[0])[far].all() and dn.same(var, clean[1])[far].all()
+        assert not dn.same(out, clean[0]).all()
+        if infinite_normals:
+            inf_at = [where["normal_pinf"], where["normal_ninf"]]
+            assert np.isnan(out[inf_at]).all()
+            assert np.isfinite(out[~dn.reach(W, H, inf_at, r)]).all()
+        else:
+            assert np.isfinite(out).all()

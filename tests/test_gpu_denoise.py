@@ -3,7 +3,10 @@ restatement, bit for bit: the guide plane (ipt_guides_device), the filter
 (ipt_denoise_device, ipt_denoise) in both tap-loop forms, its participation
 edges, the chain render -> guides -> denoise -> display in stream order, and
 the argument rules. tests/test_denoise_cpu.py pins, without a GPU, that the
-restatement is the filter meant."""
+restatement is the filter meant, on which frames a tap leaves its lattice tile
+and which planes leave the windows of the range-free division and root."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -74,9 +77,10 @@ def _denoise(ctx, dp, px, cn, m2, g, var=True, form=None, monkeypatch=None):
     return _h(out), (_h(vo) if var else None)
 
 
-def _check_filter(ctx, monkeypatch, W, H, px, cn, m2, g, what="", **kw):
-    """Every form against the restatement, colour and variance."""
-    ro, rv = dn.denoise(px, cn, m2, g, W, H, **kw)
+def _check_filter(ctx, monkeypatch, W, H, px, cn, m2, g, what="", ref=None, **kw):
+    """Every form against the restatement (ref: its planes, where a test
+    shares them), colour and variance."""
+    ro, rv = ref if ref is not None else dn.denoise(px, cn, m2, g, W, H, **kw)
     dp = capi.make_denoise_params(W, H, **kw)
     for form in FORMS:
         out, var = _denoise(ctx, dp, px, cn, m2, g, form=form, monkeypatch=monkeypatch)
@@ -275,6 +279,143 @@ def test_depth_step_stops_the_filter(gpu_ctx, oracle, monkeypatch):
     px, cn, m2 = dn.two_level_plane(W, H)
     ro, _ = _check_filter(gpu_ctx, monkeypatch, W, H, px, cn, m2, dn.step_guides(W, H), iterations=4, sigma_l=1000.0)
     _bits(ro, px, "the edge is kept")
+
+
+# ---- lattice tiles ---------------------------------------------------------------------------
+# The tiled form's taps leave their workgroup's 32 x 8 lattice tile along x
+# where W > 32 s and along y where H > 8 s: on 300 x 75 at steps 4 and 8, on
+# 1061 x 9 along x and on 9 x 277 along y up to step 32, on 1061 x 277 both
+# (tests/test_denoise_cpu.py pins how many pixels a dropped halo tap changes).
+SEAM_ITERATIONS = {(300, 75): 4, (1061, 9): 6, (9, 277): 6, (1061, 277): 6}
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_case(W, H, guides="crease"):
+    """(pixels, counters, m2, guides, keywords, the restatement's planes), read-only."""
+    px, cn, m2 = dn.random_plane(W, H, 6)
+    g = dn.crease_guides(W, H) if guides == "crease" else dn.step_guides(W, H)
+    kw = dict(iterations=SEAM_ITERATIONS[W, H], sigma_l=6.0)
+    ref = dn.denoise(px, cn, m2, g, W, H, **kw)
+    for a in (px, cn, m2, g) + ref:
+        a.setflags(write=False)
+    return px, cn, m2, g, kw, ref
+
+
+@pytest.mark.parametrize("frame", dn.SEAM_FRAMES, ids=lambda f: "%dx%d" % f)
+def test_filter_across_lattice_tiles(gpu_ctx, oracle, monkeypatch, frame):
+    W, H = frame
+    px, cn, m2, g, kw, ref = _seam_case(W, H)
+    _check_filter(gpu_ctx, monkeypatch, W, H, px, cn, m2, g, frame, ref=ref, **kw)
+    assert not np.array_equal(ref[0], px)
+
+
+def test_filter_across_lattice_tiles_on_a_depth_step_and_without_var(gpu_ctx, oracle, monkeypatch):
+    W, H = 300, 75
+    px, cn, m2, g, kw, ref = _seam_case(W, H, "step")
+    _check_filter(gpu_ctx, monkeypatch, W, H, px, cn, m2, g, "step", ref=ref, **kw)
+    assert not np.array_equal(ref[0], px)
+    px, cn, m2, g, kw, ref = _seam_case(W, H)
+    dp = capi.make_denoise_params(W, H, **kw)
+    for form in FORMS:
+        out, var = _denoise(gpu_ctx, dp, px, cn, m2, g, var=False, form=form, monkeypatch=monkeypatch)
+        assert var is None
+        _same(out, ref[0], (form, "var_out NULL"))
+
+
+def test_filter_rendered_across_a_tile_at_step_8(gpu_ctx, oracle, monkeypatch):
+    """The box scene on 300 x 75 through the chain, 4 iterations: the shipped
+    form's last tiled step, 8, with ten tile columns per residue."""
+    W, H = 300, 75
+    px, cn, m2 = _render(gpu_ctx, W, H)
+    img, rm2 = dn.box_plane(W, H)
+    _bits(px, img["pixels"], "pixels")
+    _bits(m2, rm2, "m2")
+    g = _guides(gpu_ctx, capi.make_params(W, H, 1))
+    _guides_equal(g, dn.box_guides(W, H))
+    ro, _ = _check_filter(gpu_ctx, monkeypatch, W, H, px, cn, m2, g, "box 300x75", iterations=4)
+    assert not np.array_equal(ro, px)
+
+
+def test_small_frame_queued_behind_a_large_one(oracle):
+    """1061 x 277 and then 37 x 23 on one context with no wait between the
+    calls: the small frame's second record plane lies where the large frame's
+    does, 345 small frames into the scratch, not behind its own first one."""
+    ctx = capi.Context(0)
+    try:
+        W, H = 1061, 277
+        px, cn, m2, g, kw, ref = _seam_case(W, H)
+        w, h = 37, 23
+        spx, scn, sm2 = dn.random_plane(w, h, 6)
+        sg = dn.crease_guides(w, h)
+        big = [_t(a) for a in (px, cn, m2, g)]
+        small = [_t(a) for a in (spx, scn, sm2, sg)]
+        outs = [torch.full((n,), 777.0, dtype=torch.float32, device=DEV) for n in (W * H, W * H, w * h, w * h)]
+        torch.cuda.synchronize()
+        ctx.denoise_device(capi.make_denoise_params(W, H, **kw), *(t.data_ptr() for t in big), outs[0].data_ptr(),
+                           outs[1].data_ptr())
+        ctx.denoise_device(capi.make_denoise_params(w, h, iterations=5, sigma_l=6.0), *(t.data_ptr() for t in small),
+                           outs[2].data_ptr(), outs[3].data_ptr())
+        ctx.wait()
+        torch.cuda.synchronize()
+        _same(_h(outs[0]), ref[0], "large out")
+        _same(_h(outs[1]), ref[1], "large var")
+        ro, rv = dn.denoise(spx, scn, sm2, sg, w, h, iterations=5, sigma_l=6.0)
+        _same(_h(outs[2]), ro, "small out")
+        _same(_h(outs[3]), rv, "small var")
+    finally:
+        ctx.close()
+
+
+# ---- values outside the in-range window --------------------------------------------------------
+@pytest.mark.parametrize("name", dn.EDGE_CASES)
+def test_filter_edge_planes(gpu_ctx, oracle, monkeypatch, name):
+    """Operands outside [2^-40, 2^41) (division) and [2^-96, 2^126) (root),
+    denormal operands and results, counters past 2^24 and 2^31, sv / 0
+    (tests/test_denoise_cpu.py pins the census of each plane)."""
+    W, H = 67, 35
+    px, cn, m2, g, kw = dn.edge_case(name)
+    ro, rv = _check_filter(gpu_ctx, monkeypatch, W, H, px, cn, m2, g, name, **kw)
+    assert not np.array_equal(ro, px)
+
+
+@pytest.mark.parametrize("name", ("counters_mix", "colour_e-64", "world_e-45"))
+def test_filter_edge_planes_in_halos(gpu_ctx, oracle, monkeypatch, name):
+    W, H = 300, 75
+    px, cn, m2, g, kw = dn.edge_case(name, W, H)
+    ro, rv = _check_filter(gpu_ctx, monkeypatch, W, H, px, cn, m2, g, name, **dict(kw, iterations=4))
+    assert not np.array_equal(ro, px)
+
+
+@pytest.mark.parametrize("infinite_normals", (False, True))
+def test_guides_that_are_no_numbers(gpu_ctx, oracle, monkeypatch, infinite_normals):
+    """NaN and infinite guide components on participating pixels and kinds of
+    every kind & 3: a NaN-guided pixel keeps its colour, nothing beyond the
+    filter's reach differs from the clean run, and without an infinite normal
+    every colour is finite (with one, the restatement's NaNs, bit for bit)."""
+    W, H, it = 67, 35, 3
+    kw = dict(iterations=it, sigma_l=6.0)
+    px, cn, m2 = dn.random_plane(W, H, dn.EDGE_SEED)
+    g0 = dn.crease_guides(W, H)
+    g, where, kinds = dn.poisoned_guides(g0, dn.participation(px, cn, m2, g0.reshape(-1)), infinite_normals)
+    _check_filter(gpu_ctx, monkeypatch, W, H, px, cn, m2, g, "poisoned guides", **kw)
+    dp = capi.make_denoise_params(W, H, **kw)
+    clean, clean_var = _denoise(gpu_ctx, dp, px, cn, m2, g0)
+    out, var = _denoise(gpu_ctx, dp, px, cn, m2, g)
+    kept = [where[k] for k in ("pos_nan", "pos_snan", "normal_nan", "pos_inf")]
+    _bits(out[kept], px[kept], "NaN-guided pixels keep their colour")
+    off = [i for i, k in kinds.items() if (k & 3) != 1]
+    _bits(out[off], px[off], "copied")
+    r = 2 * (2 ** it - 1)
+    far = ~dn.reach(W, H, list(where.values()) + list(kinds), r)
+    assert far.sum() >= 18
+    _bits(out[far], clean[far], "beyond the reach")
+    _bits(var[far], clean_var[far], "beyond the reach, var")
+    assert not np.array_equal(out, clean)
+    if infinite_normals:
+        inf_at = [where["normal_pinf"], where["normal_ninf"]]
+        assert np.isnan(out[inf_at]).all() and np.isfinite(out[~dn.reach(W, H, inf_at, r)]).all()
+    else:
+        assert np.isfinite(out).all()
 
 
 # ---- stream order ----------------------------------------------------------------------------
