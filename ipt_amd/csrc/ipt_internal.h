@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 
 #include "../../include/ipt_capi.h"
 
@@ -44,13 +45,19 @@ hipError_t launch_guide_scatter(hipStream_t st, const uint8_t* kinds, const floa
                                 int H, bool gui);
 
 // Owning device allocation: a call's temporaries are freed on every return
-// path, early error returns included; release() hands the pointer over.
+// path, early error returns included; release() hands the pointer over, a
+// move hands it to another DevBuf (which frees what it held).
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);  // (o frees the old allocation when it goes)
+        return *this;
+    }
     ~DevBuf() {
         if (p) (void)hipFree(p);
     }

@@ -3068,7 +3068,7 @@ struct WorkSlot {
     size_t flags_cap = 0;
     int* d_cand_rows = nullptr;
     int* d_cand_of_row = nullptr;
-    int cand_cap_rows = 0, cand_cap_h = 0;
+    size_t cand_cap_rows = 0, cand_cap_h = 0;
     int plan[5] = {-1, -1, -1, -1, -1};  // (H, tile_rows, n_shards, shard_id, plane) whose rows are on the device
     unsigned long long* d_unit = nullptr;
     // a compacting launch's buffers (IPT_FLAG_COMPACT), allocated on the slot's
@@ -3090,6 +3090,17 @@ struct WorkSlot {
     unsigned long long total = 0;   // work units of its last launch
     bool used = false;
     bool idle = true;  // its last launch is known complete (a drain since): nothing to wait for
+    // everything the slot owns (after a drain: nothing queued uses it)
+    void release() {
+        for (void* b : {(void*)d_values, (void*)d_codes, (void*)d_rg, (void*)d_kinds, (void*)d_hits, (void*)d_flags,
+                        (void*)d_cand_rows, (void*)d_cand_of_row, (void*)d_unit, (void*)d_drained, (void*)d_cvalues,
+                        (void*)d_src, (void*)d_cblk})
+            if (b) hipFree(b);
+        for (hipEvent_t e : {done, path_end, mask_ready})
+            if (e) hipEventDestroy(e);
+        if (st) hipStreamDestroy(st);
+        *this = WorkSlot{};
+    }
 };
 #if IPT_RAYLOG
 // IPT_RAYLOG's buffer (scripts/probes/walk_split.hip arms it)
@@ -3099,17 +3110,54 @@ static unsigned long long g_raylog_cap = 0;
 static unsigned g_raylog_every = 1;
 #endif
 
-struct AdaptArgs {
-    const uint8_t* mask;  // [H][W] or null
-    float* m2;            // [H][W] or null
-};
-
 // ipt_compact_plan: the first launch's plan, read back after compact_preset_kernel
 struct CompactProbe {
     uint32_t* host_src;
     unsigned long long cap;
     unsigned long long n_active = 0, start = 0;
     int rc = 0;
+};
+
+// What a C-API entry point asks of render_chunks: each fills what it uses.
+struct LaunchRequest {
+    ipt_image* img = nullptr;   // device planes the samples are accumulated into, or null
+    hipStream_t st = nullptr;   // the caller's stream
+    // [spp][H][W] host outputs (whole frames), each null or given
+    float* host_values = nullptr;
+    uint8_t* host_codes = nullptr;
+    uint8_t* host_kinds = nullptr;  // (the preview's, as host_hits)
+    float* host_hits = nullptr;
+    bool preview = false;  // ray_power_preview's launches whatever IPT_FLAG_PREVIEW says (ipt_preview_values, guides)
+    ReplaySrc replay{nullptr, nullptr};  // ipt_replay_samples: the call's passes [spp][H][W], on the device
+    // ipt_render_masked_device: sample mask and second-moment plane, [H][W] on the device, each or null
+    const uint8_t* mask = nullptr;
+    float* m2 = nullptr;
+    CompactProbe* probe = nullptr;  // ipt_compact_plan
+    ipt_guide* guides = nullptr;    // ipt_guides_device: the guide plane, on the device
+};
+
+// A call's mode, derived once from its flags and request (render_chunks).
+struct LaunchMode {
+    bool preview;  // the preview estimator's launches
+    bool replay;   // the caller's samples
+    bool traced;   // neither: the full estimator's (raygen + path kernel)
+    bool compact;  // IPT_FLAG_COMPACT or the probe: the pool holds the valid units alone (traced launches only)
+    bool adapt;    // a mask or an m2 plane: accumulate_kernel's ADAPT instances
+    bool want_kinds, want_hits;  // the FULL preview instance's per-sample outputs (host copies or guides)
+    bool count;    // IPT_FLAG_COUNTERS
+    int susp;      // the DFS's suspended levels, <= 8 (validate)
+};
+
+// What the launches of one render_chunks call share.
+struct Call {
+    const ipt_params* p;
+    const LaunchRequest& rq;
+    LaunchMode m;
+    std::vector<int> rows, of_row;  // candidate_rows
+    int n_cand = 0;
+    size_t per_pass = 0;  // units of one pass: n_cand * W
+    int chunk = 1;        // passes per launch
+    bool mask_waited[2] = {false, false};  // the slot stream waits for the caller's mask once per call
 };
 
 struct ChunkTiming {
@@ -3144,6 +3192,39 @@ struct ResidentPlane {
     std::vector<uint8_t> shadow;  // per field, the owned runs' bytes as last returned
     bool shadow_ok = false;
     unsigned long long h2d = 0, d2h = 0;  // bytes moved by the last ipt_render
+    void release() {
+        for (void* b : {(void*)d_pixels, (void*)d_counters, (void*)d_sums, (void*)d_pmax})
+            if (b) hipFree(b);
+        *this = ResidentPlane{};
+    }
+};
+
+using ipt_internal::DevBuf;
+// The uploaded scene, kept once. ipt_upload_scene builds a fresh record and
+// swaps it in only after every upload succeeded; the record it replaces frees
+// its buffers as it goes.
+struct Scene {
+    // Every KParams field that depends only on the scene and on the context's
+    // creation-time settings: each launch starts from a copy (launch_params).
+    // What a scene does not use stays zero. The host reads the scene's values
+    // here as well (geometry_kind, n_lights, sa_on, box_inrange, ...): no second copy.
+    KParams kp{};
+    // the device buffers kp points into (grid_c4: [items] centre/radius, then
+    // [items] original indices; cdf_lo: none when a bucket is crowded)
+    struct Bufs {
+        DevBuf<LightDev> lights;
+        DevBuf<float> weights, cdf;
+        DevBuf<Frame> wall;
+        DevBuf<float4> spheres, grid_c4;
+        DevBuf<BvhNode> bvh_nodes, light_nodes;
+        DevBuf<BvhSphere> bvh_prims, grid_items;
+        DevBuf<int> grid_start, lgrid, cdf_lo;
+        DevBuf<LightAx> lax;
+    } bufs;
+    // what selects the path-kernel instance and is no kernel parameter
+    bool any_round_light = false;
+    int light_axis = 0;     // axis_aligned_light() of a single AreaLight (kLightsOneA10/A01)
+    int light_pattern = 0;  // LightGrid::pattern != 0: coplanar light lattice (kLightsGridA10/A01)
 };
 
 struct ipt_ctx {
@@ -3153,43 +3234,10 @@ struct ipt_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     bool has_scene = false;
-    int geometry_kind = 0;
-    int n_lights = 0;
-    LightDev* d_lights = nullptr;
-    float* d_weights = nullptr;
-    float* d_cdf = nullptr;
-    Frame* d_wall = nullptr;
-    float4* d_spheres = nullptr;
-    int n_spheres = 0;
-    BvhNode* d_bvh_nodes = nullptr;
-    BvhSphere* d_bvh_prims = nullptr;
-    int n_nodes = 0;
-    float bvh_tmargin = 0.0f;  // sphere BVH pruning margin (ipt_bvh.h)
-    SphereGrid grid;           // geometry of the uniform sphere grid (host copy)
-    int n_grid = 0;
-    size_t grid_n_items = 0;
-    int* d_grid_start = nullptr;
-    BvhSphere* d_grid_items = nullptr;
-    float4* d_grid_c4 = nullptr;  // [items] centre/radius, then [items] original indices
-    BvhNode* d_light_nodes = nullptr;
-    int n_light_nodes = 0;
-    int cdf_bsearch = 0;
-    int cdf_p2 = 0, cdf_p2e = 0;
-    float cdf_end = 0.0f;
-    int* d_cdf_lo = nullptr;  // cdf bucket starts (global light modes), null when a bucket is crowded
-    bool any_round_light = false;
-    int light_axis = 0;  // axis_aligned_light() of a single AreaLight (kLightsOneA10/A01)
-    LightGrid lgrid;     // lgrid.pattern != 0: coplanar light lattice (kLightsGridA10/A01)
-    unsigned long long pk_u0 = 0, pk_u1 = 0, sa_u = 0;  // word thresholds (KParams)
-    int sa_on = 0;       // the lights' sample points share the plane z = sa_pz, normal (0, 0, sa_nz) (skip-ahead)
-    float sa_pz = 0.0f, sa_nz = 0.0f;
-    int* d_lgrid = nullptr;
-    LightAx* d_lax = nullptr;  // lattice lights' compact records
+    Scene scene;
     int bpc_override = 0;
     int lnodes_lds = 1;  // stage the light BVH in LDS (IPT_LNODES_LDS=0: global memory)
     int light_grid_on = 1;  // coplanar light lattices by cell lookup (IPT_LIGHT_GRID=0: the light BVH)
-    vec3 cam_pos, cam_dir, cam_right, cam_up;
-    int box_inrange = 0;
     // work buffers: two slots, used by consecutive launches in turn (WorkSlot)
     WorkSlot slot[2];
     unsigned next_slot = 0;
@@ -3248,8 +3296,6 @@ int fail(ipt_ctx* ctx, int code, const std::string& msg) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));             \
     } while (0)
 
-using ipt_internal::DevBuf;
-
 // The exact sampling tables are built once per context. Each is published in
 // the context only after its allocation, its build kernel and that kernel's
 // completion all succeeded, so a failure leaves no half-built table behind.
@@ -3283,90 +3329,57 @@ int ensure_frame_table(ipt_ctx* ctx, hipStream_t st) {
     return IPT_OK;
 }
 
-// Work buffers grow on demand. A buffer's capacity is dropped to 0 together
-// with the buffer, so a failed regrowth never leaves a stale capacity over a
-// null pointer.
-// rg_elems: the raygen records (0 for a preview launch, which has none: 5 B
-// per unit instead of 37); kinds_elems / hits_elems: ipt_preview_values' outputs.
-int ensure_work(ipt_ctx* ctx, WorkSlot& S, size_t elems, size_t npix, int H, int n_cand, size_t rg_elems,
-                size_t kinds_elems, size_t hits_elems, size_t compact_elems) {
-    // (the caller has waited for the slot's previous launch and its readers)
-    if (elems > S.work_cap) {
-        if (S.d_values) hipFree(S.d_values);
-        if (S.d_codes) hipFree(S.d_codes);
-        S.d_values = nullptr;
-        S.d_codes = nullptr;
-        S.work_cap = 0;
-        DevBuf<float> v;
-        DevBuf<uint8_t> c;
-        HIPCHECK(ctx, hipMalloc(&v.p, elems * sizeof(float)));
-        HIPCHECK(ctx, hipMalloc(&c.p, elems));
-        S.d_values = v.release();
-        S.d_codes = c.release();
-        S.work_cap = elems;
+// Work buffers grow on demand, a group of buffers under one capacity: the
+// group's buffers and its capacity are dropped together and the capacity is
+// published only once every buffer of the group is allocated, so a failed
+// regrowth never leaves a capacity over a missing buffer (what it did
+// allocate is freed by the next regrowth or by WorkSlot::release). busy: the
+// event after the last reader of the buffers, waited for before they go.
+struct GrowBuf {
+    void** p;
+    size_t bytes;
+};
+template <class T>
+GrowBuf grow_buf(T*& p, size_t bytes) {
+    return {reinterpret_cast<void**>(&p), bytes};
+}
+int regrow(ipt_ctx* ctx, hipEvent_t busy, size_t& cap, size_t want, std::initializer_list<GrowBuf> bufs) {
+    if (want <= cap) return IPT_OK;
+    if (busy) HIPCHECK(ctx, hipEventSynchronize(busy));
+    for (const GrowBuf& b : bufs) {
+        if (*b.p) hipFree(*b.p);
+        *b.p = nullptr;
     }
-    if (rg_elems > S.rg_cap) {
-        if (S.d_rg) hipFree(S.d_rg);
-        S.d_rg = nullptr;
-        S.rg_cap = 0;
-        HIPCHECK(ctx, hipMalloc(&S.d_rg, rg_elems * 2 * sizeof(uint4)));
-        S.rg_cap = rg_elems;
-    }
-    if (compact_elems > S.compact_cap) {
-        for (void* b : {(void*)S.d_cvalues, (void*)S.d_src, (void*)S.d_cblk})
-            if (b) hipFree(b);
-        S.d_cvalues = nullptr;
-        S.d_src = nullptr;
-        S.d_cblk = nullptr;
-        S.compact_cap = 0;
-        DevBuf<float> v;
-        DevBuf<uint32_t> u;
-        DevBuf<unsigned int> b;
-        HIPCHECK(ctx, hipMalloc(&v.p, compact_elems * sizeof(float)));
-        HIPCHECK(ctx, hipMalloc(&u.p, compact_elems * sizeof(uint32_t)));
-        HIPCHECK(ctx, hipMalloc(&b.p, (compact_elems / 256 + 2) * sizeof(unsigned int)));
-        S.d_cvalues = v.release();
-        S.d_src = u.release();
-        S.d_cblk = b.release();
-        S.compact_cap = compact_elems;
-    }
-    if (kinds_elems > S.kinds_cap) {
-        if (S.d_kinds) hipFree(S.d_kinds);
-        S.d_kinds = nullptr;
-        S.kinds_cap = 0;
-        HIPCHECK(ctx, hipMalloc(&S.d_kinds, kinds_elems));
-        S.kinds_cap = kinds_elems;
-    }
-    if (hits_elems > S.hits_cap) {
-        if (S.d_hits) hipFree(S.d_hits);
-        S.d_hits = nullptr;
-        S.hits_cap = 0;
-        HIPCHECK(ctx, hipMalloc(&S.d_hits, hits_elems * 6 * sizeof(float)));
-        S.hits_cap = hits_elems;
-    }
-    if (npix > S.flags_cap) {
-        if (S.d_flags) hipFree(S.d_flags);
-        S.d_flags = nullptr;
-        S.flags_cap = 0;
-        HIPCHECK(ctx, hipMalloc(&S.d_flags, npix));
-        S.flags_cap = npix;
-    }
-    if (n_cand > S.cand_cap_rows || H > S.cand_cap_h) {
-        if (S.d_cand_rows) hipFree(S.d_cand_rows);
-        if (S.d_cand_of_row) hipFree(S.d_cand_of_row);
-        S.d_cand_rows = nullptr;
-        S.d_cand_of_row = nullptr;
-        S.cand_cap_rows = S.cand_cap_h = 0;
-        S.plan[0] = -1;
-        DevBuf<int> r, o;
-        HIPCHECK(ctx, hipMalloc(&r.p, sizeof(int) * std::max(n_cand, 1)));
-        HIPCHECK(ctx, hipMalloc(&o.p, sizeof(int) * std::max(H, 1)));
-        S.d_cand_rows = r.release();
-        S.d_cand_of_row = o.release();
-        S.cand_cap_rows = n_cand;
-        S.cand_cap_h = H;
-    }
+    cap = 0;
+    for (const GrowBuf& b : bufs) HIPCHECK(ctx, hipMalloc(b.p, b.bytes));
+    cap = want;
     return IPT_OK;
+}
+
+// The slot's buffer groups at the sizes a launch of the call needs. rg: the
+// raygen records (none for a preview or replay launch: 5 B per unit instead of
+// 37); kinds / hits: the FULL preview instance's outputs; compact: a compacting
+// launch's buffers. (A used slot's buffers go only after its last launch's readers.)
+int ensure_work(ipt_ctx* ctx, WorkSlot& S, const Call& c) {
+    const size_t elems = (size_t)c.chunk * c.per_pass, npix = (size_t)c.p->width * c.p->height;
+    const size_t rows = (size_t)c.n_cand, h = (size_t)c.p->height;
+    const size_t rg = c.m.traced ? elems : 0, compact = c.m.compact ? elems : 0;
+    const size_t kinds = c.m.want_kinds ? elems : 0, hits = c.m.want_hits ? elems : 0;
+    const hipEvent_t busy = S.used ? S.done : nullptr;
+    int rc = regrow(ctx, busy, S.work_cap, elems, {grow_buf(S.d_values, elems * sizeof(float)), grow_buf(S.d_codes, elems)});
+    if (!rc) rc = regrow(ctx, busy, S.rg_cap, rg, {grow_buf(S.d_rg, rg * 2 * sizeof(uint4))});
+    if (!rc)
+        rc = regrow(ctx, busy, S.compact_cap, compact,
+                    {grow_buf(S.d_cvalues, compact * sizeof(float)), grow_buf(S.d_src, compact * sizeof(uint32_t)),
+                     grow_buf(S.d_cblk, (compact / 256 + 2) * sizeof(unsigned int))});
+    if (!rc) rc = regrow(ctx, busy, S.kinds_cap, kinds, {grow_buf(S.d_kinds, kinds)});
+    if (!rc) rc = regrow(ctx, busy, S.hits_cap, hits, {grow_buf(S.d_hits, hits * 6 * sizeof(float))});
+    if (!rc) rc = regrow(ctx, busy, S.flags_cap, npix, {grow_buf(S.d_flags, npix)});
+    // the shard's row maps: new buffers hold no plan
+    if (rows > S.cand_cap_rows || h > S.cand_cap_h) S.plan[0] = -1;
+    if (!rc) rc = regrow(ctx, busy, S.cand_cap_rows, rows, {grow_buf(S.d_cand_rows, rows * sizeof(int))});
+    if (!rc) rc = regrow(ctx, busy, S.cand_cap_h, h, {grow_buf(S.d_cand_of_row, h * sizeof(int))});
+    return rc;
 }
 
 hipEvent_t pool_event(ipt_ctx* ctx) {
@@ -3518,7 +3531,7 @@ int validate(ipt_ctx* ctx, const ipt_params* p, bool preview = false) {
     // word (ti | kind << s, ti <= n_rays): s = 8 for n_rays < 256, else 16,
     // which leaves 16 bits for the node kind (6 + sphere index)
     if (p->n_rays < 0 || p->n_rays > 65535) return fail(ctx, IPT_E_UNSUPPORTED, "n_rays must be in [0,65535]");
-    if (p->n_rays > 255 && ctx->n_spheres > 65535 - 6)
+    if (p->n_rays > 255 && ctx->scene.kp.n_spheres > 65535 - 6)
         return fail(ctx, IPT_E_UNSUPPORTED, "n_rays > 255 with more than 65529 spheres");
     if (p->depth_max < 0 || p->depth_max > 64) return fail(ctx, IPT_E_INVALID, "depth_max out of range");
     // the deepest pushed node: n_rays < 256 bounds it by 7 (a node at depth d
@@ -3577,7 +3590,7 @@ int launch_path5(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
 template <int MAXSUSP, bool COUNT, int LMODE, int GEOM>
 int launch_path4(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     if constexpr (GEOM == IPT_GEOM_SPHERE_IN_BOX) {
-        if (ctx->box_inrange && !ctx->box_generic) {
+        if (kp.box_inrange && !ctx->box_generic) {
             if constexpr (step_fixed_mode(LMODE)) {
                 const uint32_t nr = (uint32_t)kp.n_rays;
                 if (kp.sa_on && nr != 0u && (nr & (nr - 1u)) == 0u) {
@@ -3615,10 +3628,10 @@ int launch_path3(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
 }
 template <int MAXSUSP, bool COUNT>
 int launch_path2(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
-    if (ctx->any_round_light) return launch_path3<MAXSUSP, COUNT, kLightsAny>(ctx, kp, st);
+    if (ctx->scene.any_round_light) return launch_path3<MAXSUSP, COUNT, kLightsAny>(ctx, kp, st);
     if (kp.n_lights == 1) {
-        if (ctx->light_axis == 1) return launch_path3<MAXSUSP, COUNT, kLightsOneA10>(ctx, kp, st);
-        if (ctx->light_axis == 2) return launch_path3<MAXSUSP, COUNT, kLightsOneA01>(ctx, kp, st);
+        if (ctx->scene.light_axis == 1) return launch_path3<MAXSUSP, COUNT, kLightsOneA10>(ctx, kp, st);
+        if (ctx->scene.light_axis == 2) return launch_path3<MAXSUSP, COUNT, kLightsOneA01>(ctx, kp, st);
         return launch_path3<MAXSUSP, COUNT, kLightsOne>(ctx, kp, st);
     }
     if (kp.n_lights <= kLdsLights) return launch_path3<MAXSUSP, COUNT, kLightsLds>(ctx, kp, st);
@@ -3626,12 +3639,12 @@ int launch_path2(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
         // (the lattice is only built for sphere-in-box scenes)
         // the records-in-LDS instance wherever its LDS fits one workgroup per CU
         constexpr int G = IPT_GEOM_SPHERE_IN_BOX;
-        if (ctx->lgrid.pattern == 1 && kp.geometry_kind == G) {
+        if (ctx->scene.light_pattern == 1 && kp.geometry_kind == G) {
             if (ctx->lattice_lds && path_lds_bytes<MAXSUSP, kLightsGridA10L, G>(kp) <= ctx->max_lds)
                 return launch_path4<MAXSUSP, COUNT, kLightsGridA10L, G>(ctx, kp, st);
             return launch_path4<MAXSUSP, COUNT, kLightsGridA10, G>(ctx, kp, st);
         }
-        if (ctx->lgrid.pattern == 2 && kp.geometry_kind == G) {
+        if (ctx->scene.light_pattern == 2 && kp.geometry_kind == G) {
             if (ctx->lattice_lds && path_lds_bytes<MAXSUSP, kLightsGridA01L, G>(kp) <= ctx->max_lds)
                 return launch_path4<MAXSUSP, COUNT, kLightsGridA01L, G>(ctx, kp, st);
             return launch_path4<MAXSUSP, COUNT, kLightsGridA01, G>(ctx, kp, st);
@@ -3639,9 +3652,10 @@ int launch_path2(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     }
     return launch_path3<MAXSUSP, COUNT, kLightsGlobal>(ctx, kp, st);
 }
-template <int MAXSUSP>
-int launch_path(ipt_ctx* ctx, const KParams& kp, hipStream_t st, bool count) {
-    return count ? launch_path2<MAXSUSP, true>(ctx, kp, st) : launch_path2<MAXSUSP, false>(ctx, kp, st);
+// the instances for the call's stack depth (4 or 8 suspended levels) and counting flag
+int launch_path(ipt_ctx* ctx, const KParams& kp, hipStream_t st, const LaunchMode& m) {
+    if (m.susp <= 4) return m.count ? launch_path2<4, true>(ctx, kp, st) : launch_path2<4, false>(ctx, kp, st);
+    return m.count ? launch_path2<8, true>(ctx, kp, st) : launch_path2<8, false>(ctx, kp, st);
 }
 
 template <bool FULL>
@@ -3662,387 +3676,373 @@ int launch_preview(ipt_ctx* ctx, const KParams& kp, const PreviewOut& po, hipStr
     return IPT_OK;
 }
 
-// preview: ray_power_preview's launches (IPT_FLAG_PREVIEW, or forced by
-// ipt_preview_values, whose host_kinds / host_hits may each be null)
-// adapt: ipt_render_masked_device's mask and m2 plane (either may be null):
-// raygen / the preview kernel read the mask, the replay's ADAPT instance runs;
-// with a mask, each slot stream the call uses first waits for the caller's
-// stream as it stands at the call (the mask is caller memory, written there)
-// replay: ipt_replay_samples' source, the caller's samples of the call's passes
-// [spp][H][W] on the device: replay_mark_kernel takes the place of the raygen
-// and path launches (no table, no raygen record, no tail gate, as a preview
-// launch), everything else is the call's as rendered
-int render_chunks(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, hipStream_t st,
-                  float* host_values, uint8_t* host_codes, bool preview = false, uint8_t* host_kinds = nullptr,
-                  float* host_hits = nullptr, const ReplaySrc* replay = nullptr, const AdaptArgs* adapt = nullptr,
-                  CompactProbe* probe = nullptr, ipt_guide* guides = nullptr) {
-    preview = preview || (p->flags & IPT_FLAG_PREVIEW) != 0;
-    // ipt_guides_device: the FULL preview instance's kinds and hits stay on the
-    // device, where a scatter on the caller's stream reads them
-    const bool want_kinds = host_kinds || guides, want_hits = host_hits || guides;
-    const bool traced = !preview && !replay;  // the full estimator's launches
-    // IPT_FLAG_COMPACT: the pool holds the valid units alone (the preview has
-    // no pool: the flag has no effect there)
-    const bool compact = traced && ((p->flags & IPT_FLAG_COMPACT) != 0 || probe);
-    std::vector<int> rows, of_row;
-    candidate_rows(p, rows, of_row);
-    const int n_cand = (int)rows.size();
-    const int W = p->width, H = p->height;
-    const size_t per_pass = (size_t)n_cand * W;
-    if (per_pass == 0 || p->spp == 0) return IPT_OK;
-    // chunk passes so that the work buffers stay bounded: at most 2^29 units
-    // (37 B each: 2 GiB of radiance + 512 MiB of codes + 16 GiB of raygen
-    // records, of 288 GB), and at most 3/4 of the device memory this context
-    // can still obtain (hipMemGetInfo's free memory plus its own work buffers,
-    // less the sampling tables not yet built), so that contexts sharing a
-    // device split their passes into more launches instead of failing with
-    // IPT_E_OOM. Equal chunks: each launch ends with a tail in which lanes run
-    // out of work (the longest paths finish alone; 7 % of a 32-spp C2 launch),
-    // so few large launches beat many small ones (C2 1024^2 x 256 spp is a
-    // single launch).
+LaunchMode mode_of(const ipt_params* p, const LaunchRequest& rq) {
+    LaunchMode m{};
+    m.preview = rq.preview || (p->flags & IPT_FLAG_PREVIEW) != 0;
+    m.replay = rq.replay.values != nullptr;
+    m.traced = !m.preview && !m.replay;
+    // (the preview has no pool: the flag has no effect there)
+    m.compact = m.traced && ((p->flags & IPT_FLAG_COMPACT) != 0 || rq.probe);
+    m.adapt = rq.mask || rq.m2;
+    // (guides: the kinds and hits stay on the device, where the scatter reads them)
+    m.want_kinds = rq.host_kinds || rq.guides;
+    m.want_hits = rq.host_hits || rq.guides;
+    m.count = (p->flags & IPT_FLAG_COUNTERS) != 0;
+    m.susp = m.traced ? needed_susp(p) : 0;
+    return m;
+}
+
+// Passes per launch, so that the work buffers stay bounded: at most 2^29 units
+// (37 B each: 2 GiB of radiance + 512 MiB of codes + 16 GiB of raygen
+// records, of 288 GB), and at most 3/4 of the device memory this context
+// can still obtain (hipMemGetInfo's free memory plus its own work buffers,
+// less the sampling tables not yet built), so that contexts sharing a
+// device split their passes into more launches instead of failing with
+// IPT_E_OOM. Equal chunks: each launch ends with a tail in which lanes run
+// out of work (the longest paths finish alone; 7 % of a 32-spp C2 launch),
+// so few large launches beat many small ones (C2 1024^2 x 256 spp is a
+// single launch).
+int chunk_passes(ipt_ctx* ctx, const Call& c) {
+    const LaunchMode& m = c.m;
     // (a preview unit is its value and code, 5 B, plus ipt_preview_values'
     // outputs; it has no raygen record and its launches read no table)
     constexpr size_t kRgBytes = 2 * sizeof(uint4);
     // (a compacting launch adds its compact values and dense-unit list, 8 B)
     constexpr size_t kCompactBytes = sizeof(float) + sizeof(uint32_t);
-    const size_t unit_bytes = sizeof(float) + 1 + (!traced ? (want_kinds ? 1 : 0) + (want_hits ? 6 * sizeof(float) : 0) : kRgBytes) +
-                              (compact ? kCompactBytes : 0);
+    const size_t unit_bytes = sizeof(float) + 1 +
+                              (!m.traced ? (m.want_kinds ? 1 : 0) + (m.want_hits ? 6 * sizeof(float) : 0) : kRgBytes) +
+                              (m.compact ? kCompactBytes : 0);
     size_t budget = (size_t)1 << 29;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            size_t avail = free_b + (ctx->slot[0].work_cap + ctx->slot[1].work_cap) * (sizeof(float) + 1) +
-                           (!traced ? 0 : (ctx->slot[0].rg_cap + ctx->slot[1].rg_cap) * kRgBytes) +
-                           (!compact ? 0 : (ctx->slot[0].compact_cap + ctx->slot[1].compact_cap) * kCompactBytes);
-            const size_t tables = !traced ? 0 :
-                                  (ctx->d_cos_a ? 0 : ((size_t)3 << 26)) +
-                                  (ctx->d_frame_sc || !frame_table_user(ctx->geometry_kind)
-                                       ? 0 : kFrameTabEntries * sizeof(float2));
-            avail = avail > tables ? avail - tables : 0;
-            // (two slots: consecutive launches hold a chunk each)
-            budget = std::min(budget, std::max<size_t>(per_pass, avail / 8 * 3 / unit_bytes));
-        }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        const WorkSlot* S = ctx->slot;
+        size_t avail = free_b + (S[0].work_cap + S[1].work_cap) * (sizeof(float) + 1) +
+                       (!m.traced ? 0 : (S[0].rg_cap + S[1].rg_cap) * kRgBytes) +
+                       (!m.compact ? 0 : (S[0].compact_cap + S[1].compact_cap) * kCompactBytes);
+        const size_t tables = !m.traced ? 0 :
+                              (ctx->d_cos_a ? 0 : ((size_t)3 << 26)) +
+                              (ctx->d_frame_sc || !frame_table_user(ctx->scene.kp.geometry_kind)
+                                   ? 0 : kFrameTabEntries * sizeof(float2));
+        avail = avail > tables ? avail - tables : 0;
+        // (two slots: consecutive launches hold a chunk each)
+        budget = std::min(budget, std::max<size_t>(c.per_pass, avail / 8 * 3 / unit_bytes));
     }
-    if (ctx->chunk_cap_test) budget = std::min(budget, std::max<size_t>(per_pass, ctx->chunk_cap_test));
-    const size_t n_chunks = std::max<size_t>(1, ((size_t)p->spp * per_pass + budget - 1) / budget);
-    int chunk = (int)std::max<size_t>(1, ((size_t)p->spp + n_chunks - 1) / n_chunks);
-    while (chunk > 1 && (size_t)chunk * per_pass > budget) --chunk;
-    // (the preview reads neither table: a context that only renders previews
-    // never builds them)
-    int rc = !traced ? IPT_OK : ensure_cos_tables(ctx, st);
-    if (rc) return rc;
-    if (traced && frame_table_user(ctx->geometry_kind)) {  // path_kernel's frame builds
-        rc = ensure_frame_table(ctx, st);
-        if (rc) return rc;
+    if (ctx->chunk_cap_test) budget = std::min(budget, std::max<size_t>(c.per_pass, ctx->chunk_cap_test));
+    const size_t n_chunks = std::max<size_t>(1, ((size_t)c.p->spp * c.per_pass + budget - 1) / budget);
+    int chunk = (int)std::max<size_t>(1, ((size_t)c.p->spp + n_chunks - 1) / n_chunks);
+    while (chunk > 1 && (size_t)chunk * c.per_pass > budget) --chunk;
+    return chunk;
+}
+
+// The next launch's slot. Its previous launch and that launch's readers
+// (accumulate, host copies) must be done before its buffers are regrown or
+// rewritten: the slot stream waits for them on the device, the host only where
+// it rewrites device memory itself. Then the slot stream takes the gate on the
+// other slot's launch, its predecessor.
+int take_slot(ipt_ctx* ctx, const Call& c, WorkSlot*& out) {
+    const ipt_params* p = c.p;
+    WorkSlot& S = ctx->slot[ctx->next_slot];
+    WorkSlot& P = ctx->slot[ctx->next_slot ^ 1u];
+    ctx->next_slot ^= 1u;
+    out = &S;
+    if (const int rc = ensure_work(ctx, S, c)) return rc;
+    const int plan[5] = {p->height, p->tile_rows, p->n_shards, p->shard_id, plane_of(p)};
+    const bool replan = !std::equal(plan, plan + 5, S.plan);
+    if (c.m.compact && !ctx->d_uring) HIPCHECK(ctx, hipMalloc(&ctx->d_uring, sizeof(unsigned long long) * 2 * kClkRing));
+    if (replan) {
+        if (S.used) HIPCHECK(ctx, hipEventSynchronize(S.done));
+        // (synchronous copies: the host vectors do not outlive the call)
+        HIPCHECK(ctx, hipMemcpy(S.d_cand_rows, c.rows.data(), sizeof(int) * c.n_cand, hipMemcpyHostToDevice));
+        HIPCHECK(ctx, hipMemcpy(S.d_cand_of_row, c.of_row.data(), sizeof(int) * p->height, hipMemcpyHostToDevice));
+        std::copy(plan, plan + 5, S.plan);
     }
-    const int susp = !traced ? 0 : needed_susp(p);  // <= 8 (validate)
-    const bool count = (p->flags & IPT_FLAG_COUNTERS) != 0;
-    bool mask_waited[2] = {false, false};
-    for (int s0 = 0; s0 < p->spp; s0 += chunk) {
-        const int ns = std::min(chunk, p->spp - s0);
-        // this launch's slot; its previous launch and that launch's readers
-        // (accumulate, host copies) must be done before its buffers are
-        // regrown or rewritten: the slot stream waits for them on the device,
-        // the host only where it rewrites device memory itself
-        WorkSlot& S = ctx->slot[ctx->next_slot];
-        ctx->next_slot ^= 1u;
-        const size_t elems = (size_t)chunk * per_pass;
-        const size_t rg_elems = !traced ? 0 : elems, kinds_elems = want_kinds ? elems : 0, hits_elems = want_hits ? elems : 0;
-        const size_t compact_elems = compact ? elems : 0;
-        const bool grow = elems > S.work_cap || (size_t)W * H > S.flags_cap || n_cand > S.cand_cap_rows ||
-                          H > S.cand_cap_h || rg_elems > S.rg_cap || kinds_elems > S.kinds_cap ||
-                          hits_elems > S.hits_cap || compact_elems > S.compact_cap;
-        const int plan[5] = {H, p->tile_rows, p->n_shards, p->shard_id, plane_of(p)};
-        const bool replan = !std::equal(plan, plan + 5, S.plan);
-        if (S.used && (grow || replan)) HIPCHECK(ctx, hipEventSynchronize(S.done));
-        rc = ensure_work(ctx, S, elems, (size_t)W * H, H, n_cand, rg_elems, kinds_elems, hits_elems, compact_elems);
-        if (rc) return rc;
-        if (compact && !ctx->d_uring) HIPCHECK(ctx, hipMalloc(&ctx->d_uring, sizeof(unsigned long long) * 2 * kClkRing));
-        if (replan) {
-            // (synchronous copies: the host vectors do not outlive the call)
-            HIPCHECK(ctx, hipMemcpy(S.d_cand_rows, rows.data(), sizeof(int) * n_cand, hipMemcpyHostToDevice));
-            HIPCHECK(ctx, hipMemcpy(S.d_cand_of_row, of_row.data(), sizeof(int) * H, hipMemcpyHostToDevice));
-            std::copy(plan, plan + 5, S.plan);
-        }
-        if (S.used) HIPCHECK(ctx, hipStreamWaitEvent(S.st, S.done, 0));
-        // start in the predecessor's tail: once its pool is drained (or, without
-        // stream value waits, once it has finished)
-        const unsigned sidx = (unsigned)(&S - ctx->slot);
-        WorkSlot& P = ctx->slot[sidx ^ 1u];
-        // (P's counter is reset only by P's next launch, which waits for this
-        // launch's pool in turn, so this wait cannot miss its value)
-        // (a preview launch has no tail to overlap and takes no gate; a preview
-        // predecessor leaves P.seq at that of P's last full launch, which
-        // precedes it in P's stream)
-        if (traced && P.used && !P.idle) {
-            if (ctx->gate_on_pool)
-                HIPCHECK(ctx, hipStreamWaitValue64(S.st, P.d_drained, P.seq, hipStreamWaitValueGte, ~0ull));
-            else
-                HIPCHECK(ctx, hipStreamWaitEvent(S.st, P.path_end, 0));
-        }
-        // bounded timing backlog: settle launches far behind (they are done or
-        // nearly so; the queue of launches ahead is untouched)
-        while (ctx->pending.size() >= 8) {
-            rc = settle_oldest(ctx);
-            if (rc) return rc;
-        }
-        ChunkTiming tm;
-        tm.t0 = pool_event(ctx);
-        tm.t1 = pool_event(ctx);
-        if (img) {
-            tm.a0 = pool_event(ctx);
-            tm.a1 = pool_event(ctx);
-        }
-        if (!tm.t0 || !tm.t1 || (img && (!tm.a0 || !tm.a1))) {
-            pool_return(ctx, tm);
-            return fail(ctx, IPT_E_DEVICE, "hipEventCreate failed");
-        }
-        KParams kp{};
-        kp.W = W;
-        kp.H = H;
-        kp.spp = ns;
-        kp.spp_offset = p->spp_offset + s0;
-        kp.n_rays = p->n_rays;
-        kp.meta_shift = p->n_rays > 255 ? 16 : 8;
-        kp.depth_max = p->depth_max;
-        kp.key0 = (uint32_t)p->seed;
-        kp.key1 = (uint32_t)(p->seed >> 32);
-        kp.n_cand = n_cand;
-        kp.cand_rows = S.d_cand_rows;
-        kp.tile_rows = p->tile_rows;
-        kp.n_shards = p->n_shards;
-        kp.shard_id = p->shard_id;
-        kp.total_units = (unsigned long long)ns * per_pass;
-        if (kp.total_units >= (1ull << 32)) return fail(ctx, IPT_E_INVALID, "more than 2^32 work units in one launch");
-        kp.per_pass32 = (uint32_t)per_pass;
-        kp.box_inrange = ctx->box_inrange;
-        kp.inv_per_pass = 1.0 / (double)per_pass;
-        kp.inv_w = 1.0 / (double)W;
-        kp.unit_counter = S.d_unit;
-        kp.drained = ctx->gate_on_pool ? S.d_drained : nullptr;
+    if (S.used) HIPCHECK(ctx, hipStreamWaitEvent(S.st, S.done, 0));
+    // start in the predecessor's tail: once its pool is drained (or, without
+    // stream value waits, once it has finished)
+    // (P's counter is reset only by P's next launch, which waits for this
+    // launch's pool in turn, so this wait cannot miss its value)
+    // (a preview or replay launch has no tail to overlap and takes no gate;
+    // such a predecessor leaves P.seq at that of P's last full launch, which
+    // precedes it in P's stream)
+    if (c.m.traced && P.used && !P.idle) {
+        if (ctx->gate_on_pool)
+            HIPCHECK(ctx, hipStreamWaitValue64(S.st, P.d_drained, P.seq, hipStreamWaitValueGte, ~0ull));
+        else
+            HIPCHECK(ctx, hipStreamWaitEvent(S.st, P.path_end, 0));
+    }
+    return IPT_OK;
+}
+
+// A launch's kernel parameters: the scene's template and what the call and
+// this launch (passes [s0, s0 + ns) on slot S) add.
+KParams launch_params(ipt_ctx* ctx, const Call& c, const WorkSlot& S, int s0, int ns) {
+    const ipt_params* p = c.p;
+    KParams kp = ctx->scene.kp;
+    kp.W = p->width;
+    kp.H = p->height;
+    kp.spp = ns;
+    kp.spp_offset = p->spp_offset + s0;
+    kp.n_rays = p->n_rays;
+    kp.meta_shift = p->n_rays > 255 ? 16 : 8;
+    kp.depth_max = p->depth_max;
+    kp.key0 = (uint32_t)p->seed;
+    kp.key1 = (uint32_t)(p->seed >> 32);
+    kp.n_cand = c.n_cand;
+    kp.cand_rows = S.d_cand_rows;
+    kp.tile_rows = p->tile_rows;
+    kp.n_shards = p->n_shards;
+    kp.shard_id = p->shard_id;
+    kp.total_units = (unsigned long long)ns * c.per_pass;
+    kp.per_pass32 = (uint32_t)c.per_pass;
+    kp.inv_per_pass = 1.0 / (double)c.per_pass;
+    kp.inv_w = 1.0 / (double)p->width;
+    kp.unit_counter = S.d_unit;
+    kp.drained = ctx->gate_on_pool ? S.d_drained : nullptr;
+    kp.drain_seq = S.seq + 1;
 #if IPT_RAYLOG
-        kp.raylog = g_raylog;
-        kp.raylog_n = g_raylog_n;
-        kp.raylog_cap = g_raylog_cap;
-        kp.raylog_every = g_raylog_every;
+    kp.raylog = g_raylog;
+    kp.raylog_n = g_raylog_n;
+    kp.raylog_cap = g_raylog_cap;
+    kp.raylog_every = g_raylog_every;
 #endif
-        kp.drain_seq = S.seq + 1;
-        kp.values = S.d_values;
-        kp.codes = S.d_codes;
-        kp.flags = S.d_flags;
-        kp.counters = ctx->d_counters;
-        kp.geometry_kind = ctx->geometry_kind;
-        kp.n_lights = ctx->n_lights;
-        kp.lights = ctx->d_lights;
-        kp.weights = ctx->d_weights;
-        kp.cdf = ctx->d_cdf;
-        kp.wall_frames = ctx->d_wall;
-        kp.cam_pos = ctx->cam_pos;
-        kp.cam_dir = ctx->cam_dir;
-        kp.cam_right = ctx->cam_right;
-        kp.cam_up = ctx->cam_up;
-        kp.n_spheres = ctx->n_spheres;
-        kp.spheres = ctx->d_spheres;
-        kp.bvh_nodes = ctx->d_bvh_nodes;
-        kp.bvh_tmargin = ctx->bvh_tmargin;
-        kp.n_grid = ctx->n_grid;
-        for (int a = 0; a < 3; ++a) {
-            kp.grid_g0[a] = ctx->grid.g0[a];
-            kp.grid_h[a] = ctx->grid.h[a];
-            kp.grid_inv_h[a] = ctx->grid.inv_h[a];
-            kp.grid_n[a] = ctx->grid.n[a];
-            kp.grid_g1[a] = ctx->grid.g0[a] + (float)ctx->grid.n[a] * ctx->grid.h[a];
-        }
-        kp.grid_m = ctx->grid.m;
-        kp.grid_start = ctx->d_grid_start;
-        kp.grid_items = ctx->d_grid_items;
-        kp.grid_c4 = ctx->d_grid_c4;
-        kp.grid_idx = ctx->d_grid_c4 ? reinterpret_cast<const int*>(ctx->d_grid_c4 + ctx->grid_n_items) : nullptr;
-        kp.bvh_prims = ctx->d_bvh_prims;
-        kp.n_nodes = ctx->n_nodes;
-        kp.light_nodes = ctx->d_light_nodes;
-        kp.n_light_nodes = ctx->n_light_nodes;
-        // light BVH staged in LDS (IPT_LNODES_LDS=0 at ipt_create keeps it in
-        // global memory): the resumable light walk runs at 3 workgroups/CU, which
-        // the extra LDS keeps, and gains 10 % on C5 (43.8 vs 40.2 Mpaths/s)
-        kp.lnodes_lds = (ctx->lnodes_lds && ctx->n_light_nodes > 0 && ctx->n_light_nodes <= kLdsLightNodesMax) ? 1 : 0;
-        kp.cdf_bsearch = ctx->cdf_bsearch;
-        kp.cdf_p2 = ctx->cdf_p2;
-        kp.cdf_p2e = ctx->cdf_p2e;
-        kp.cdf_end_t = (uint32_t)(word_threshold(ctx->cdf_end) >> 8);
-        kp.cdf_lo = ctx->d_cdf_lo;
-        kp.lgrid = ctx->d_lgrid;
-        kp.lax = reinterpret_cast<const float4*>(ctx->d_lax);
-        kp.lg_nu = ctx->lgrid.nu;
-        kp.lg_nv = ctx->lgrid.nv;
-        kp.lg_u0 = ctx->lgrid.u0;
-        kp.lg_v0 = ctx->lgrid.v0;
-        kp.lg_icw = ctx->lgrid.icw;
-        kp.lg_ich = ctx->lgrid.ich;
-        kp.lg_e = ctx->lgrid.e;
-        kp.pk_u0 = ctx->pk_u0;
-        kp.pk_u1 = ctx->pk_u1;
-        kp.sa_u = ctx->sa_u;
-        kp.sa_on = ctx->sa_on;
-        kp.sa_pz = ctx->sa_pz;
-        kp.sa_nz = ctx->sa_nz;
-        kp.lg_pn = ctx->lgrid.pn;
-        kp.lg_nn = ctx->lgrid.nn;
-        kp.cos_a = ctx->d_cos_a;
-        kp.frame_sc = ctx->d_frame_sc;
-        kp.rg = S.d_rg;
-        kp.count = count ? 1 : 0;
-        kp.plane = plane_of(p);
-        kp.mask = adapt ? adapt->mask : nullptr;
-        // the slot stream: t0..t1 is the path's per-sample work, raygen_kernel
-        // (render_sample's jitter, camera ray, Philox block 0; ~0.2 % of a C2
-        // launch) and path_kernel
-        const hipStream_t ss = S.st;
-        ctx->pending.push_back(tm);  // (settled by drain, also on an error below: unrecorded, untimed)
-        ChunkTiming& tmq = ctx->pending.back();
-        S.used = true;
-        S.idle = false;
-        S.total = 0;  // (until its kernel is queued: a successor must not wait on a launch that failed)
-        if (kp.mask && !mask_waited[sidx]) {
-            // raygen reads caller memory: this slot stream's launches of the
-            // call run after what the caller's stream holds at the call
-            if (!S.mask_ready) HIPCHECK(ctx, hipEventCreateWithFlags(&S.mask_ready, hipEventDisableTiming));
-            HIPCHECK(ctx, hipEventRecord(S.mask_ready, st));
-            HIPCHECK(ctx, hipStreamWaitEvent(ss, S.mask_ready, 0));
-            mask_waited[sidx] = true;
-        }
-        // (a compacting launch's counter is set by compact_preset_kernel)
-        if (!compact) HIPCHECK(ctx, hipMemsetAsync(S.d_unit, 0, sizeof(unsigned long long), ss));
-        HIPCHECK(ctx, hipMemsetAsync(S.d_flags, 0, (size_t)W * H, ss));
-        HIPCHECK(ctx, hipEventRecord(tm.t0, ss));
-        if (replay) {
-            const ReplaySrc src{replay->values + (size_t)s0 * W * H, replay->codes + (size_t)s0 * W * H};
-            hipLaunchKernelGGL(replay_mark_kernel, dim3((unsigned)((kp.total_units + 255) / 256)), dim3(256), 0, ss, kp, src);
-            HIPCHECK(ctx, hipGetLastError());
-        } else if (preview) {
-            // one fused kernel; the counting / AOV instance only where asked
-            const PreviewOut po{want_kinds ? S.d_kinds : nullptr, want_hits ? S.d_hits : nullptr};
-            rc = (count || po.kinds || po.hits) ? launch_preview<true>(ctx, kp, po, ss) : launch_preview<false>(ctx, kp, po, ss);
-            if (rc) return rc;
-        } else if (compact) {
-            // classify / scan / scatter / preset in raygen_kernel's place, the
-            // path kernel over the compact range of the same records with the
-            // compact values as its output, then the values back to their
-            // dense places: everything after reads the launch as an
-            // uncompacted one leaves it
-            const unsigned nblk = (unsigned)((kp.total_units + 255) / 256);
-            tmq.uring = (int)(ctx->next_uring++ % kClkRing);
-            const CompactBufs cb{S.d_cblk, S.d_src, S.d_cvalues, S.d_values, ctx->d_uring + 2 * tmq.uring};
-            if (probe) kp.count = 0;
-            hipLaunchKernelGGL(compact_classify_kernel, dim3(nblk), dim3(256), 0, ss, kp, cb.blocks);
-            hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(256), 0, ss, cb.blocks, nblk);
-            hipLaunchKernelGGL(compact_scatter_kernel, dim3(nblk), dim3(256), 0, ss, kp, (const unsigned int*)cb.blocks, cb.src);
-            hipLaunchKernelGGL(compact_preset_kernel, dim3(1), dim3(64), 0, ss, (const unsigned int*)cb.blocks, nblk,
-                               kp.total_units, S.d_unit, cb.ring);
-            HIPCHECK(ctx, hipGetLastError());
-            if (probe) {
-                // ipt_compact_plan: the plan of the call's first launch, no path kernel
-                unsigned long long h[2] = {0, 0};
-                HIPCHECK(ctx, hipStreamSynchronize(ss));
-                HIPCHECK(ctx, hipMemcpy(h, cb.ring, sizeof h, hipMemcpyDeviceToHost));
-                probe->start = h[0];
-                probe->n_active = h[1];
-                if (h[1] > kp.total_units || h[1] > probe->cap)
-                    probe->rc = fail(ctx, IPT_E_INVALID, "ipt_compact_plan: host_src holds fewer than n_active entries");
-                else if (h[1])
-                    HIPCHECK(ctx, hipMemcpy(probe->host_src, cb.src + (kp.total_units - h[1]), h[1] * sizeof(uint32_t),
-                                            hipMemcpyDeviceToHost));
-            } else {
-                KParams kc = kp;
-                kc.values = cb.cvalues;
-                rc = susp <= 4 ? launch_path<4>(ctx, kc, ss, count) : launch_path<8>(ctx, kc, ss, count);
-                if (rc) return rc;
-                S.seq = kp.drain_seq;
-                hipLaunchKernelGGL(compact_expand_kernel, dim3(nblk), dim3(256), 0, ss, cb, nblk, kp.total_units);
-                HIPCHECK(ctx, hipGetLastError());
-                tmq.units = kp.total_units;
-            }
-        } else {
-        hipLaunchKernelGGL(raygen_kernel, dim3((unsigned)((kp.total_units + 255) / 256)), dim3(256), 0, ss, kp);
+    kp.values = S.d_values;
+    kp.codes = S.d_codes;
+    kp.flags = S.d_flags;
+    kp.rg = S.d_rg;
+    kp.counters = ctx->d_counters;
+    kp.cos_a = ctx->d_cos_a;  // (built before the call's first traced launch)
+    kp.frame_sc = ctx->d_frame_sc;
+    kp.count = c.m.count ? 1 : 0;
+    kp.plane = plane_of(p);
+    kp.mask = c.rq.mask;
+    return kp;
+}
+
+// Queues the source of the launch's samples on the slot stream, between its
+// t0 and t1 events: the caller's samples (replay_mark_kernel in the place of
+// the raygen and path launches: no table, no raygen record), the preview
+// kernel, or raygen + path kernel -- compacted or not.
+int queue_samples(ipt_ctx* ctx, const Call& c, WorkSlot& S, const KParams& kp, int s0, ChunkTiming& tm) {
+    const hipStream_t ss = S.st;
+    const unsigned nblk = (unsigned)((kp.total_units + 255) / 256);
+    if (c.m.replay) {
+        const size_t off = (size_t)s0 * kp.W * kp.H;
+        const ReplaySrc src{c.rq.replay.values + off, c.rq.replay.codes + off};
+        hipLaunchKernelGGL(replay_mark_kernel, dim3(nblk), dim3(256), 0, ss, kp, src);
         HIPCHECK(ctx, hipGetLastError());
-        rc = susp <= 4 ? launch_path<4>(ctx, kp, ss, count) : launch_path<8>(ctx, kp, ss, count);
-        if (rc) return rc;
+        return IPT_OK;
+    }
+    if (c.m.preview) {
+        // one fused kernel; the counting / AOV instance only where asked
+        const PreviewOut po{c.m.want_kinds ? S.d_kinds : nullptr, c.m.want_hits ? S.d_hits : nullptr};
+        return (c.m.count || po.kinds || po.hits) ? launch_preview<true>(ctx, kp, po, ss)
+                                                  : launch_preview<false>(ctx, kp, po, ss);
+    }
+    if (!c.m.compact) {
+        hipLaunchKernelGGL(raygen_kernel, dim3(nblk), dim3(256), 0, ss, kp);
+        HIPCHECK(ctx, hipGetLastError());
+        if (const int rc = launch_path(ctx, kp, ss, c.m)) return rc;
         S.seq = kp.drain_seq;
-        tmq.units = kp.total_units;
-        }
-        S.total = kp.total_units;
-        HIPCHECK(ctx, hipEventRecord(tm.t1, ss));
-        HIPCHECK(ctx, hipEventRecord(S.path_end, ss));
-        if (host_values) {  // [spp][H][W] (whole frames: per_pass == W * H)
-            HIPCHECK(ctx, hipMemcpyAsync(host_values + (size_t)s0 * per_pass, S.d_values, sizeof(float) * ns * per_pass,
-                                         hipMemcpyDeviceToHost, ss));
-            HIPCHECK(ctx, hipMemcpyAsync(host_codes + (size_t)s0 * per_pass, S.d_codes, ns * per_pass,
-                                         hipMemcpyDeviceToHost, ss));
-        }
-        if (host_kinds)
-            HIPCHECK(ctx, hipMemcpyAsync(host_kinds + (size_t)s0 * per_pass, S.d_kinds, ns * per_pass, hipMemcpyDeviceToHost, ss));
-        if (host_hits)
-            HIPCHECK(ctx, hipMemcpyAsync(host_hits + (size_t)s0 * per_pass * 6, S.d_hits, sizeof(float) * 6 * ns * per_pass,
-                                         hipMemcpyDeviceToHost, ss));
-        if (guides) {
-            // (one pass, whole frame: unit = iy * W + ix) the scatter runs on
-            // the caller's stream, in call order, after the preview kernel;
-            // the slot's buffers are free again once it has run
-            HIPCHECK(ctx, hipStreamWaitEvent(st, tm.t1, 0));
-            HIPCHECK(ctx, ipt_internal::launch_guide_scatter(st, S.d_kinds, S.d_hits, guides, W, H, kp.plane == kPlaneGui));
-            HIPCHECK(ctx, hipEventRecord(S.done, st));
-        } else if (!img) {
-            HIPCHECK(ctx, hipEventRecord(S.done, ss));
-        }
-        if (img) {
-            // the render plane's replay: on the caller's stream, in call order,
-            // after this launch's path kernel
-            HIPCHECK(ctx, hipStreamWaitEvent(st, tm.t1, 0));
-            HIPCHECK(ctx, hipEventRecord(tm.a0, st));
-            unsigned long long* clk = nullptr;
-            if (ctx->d_clk) {
-                tmq.clk = (int)(ctx->next_clk++ % kClkRing);
-                clk = ctx->d_clk + 2 * tmq.clk;
-                HIPCHECK(ctx, hipMemsetAsync(clk, 0xff, sizeof(unsigned long long), st));
-                HIPCHECK(ctx, hipMemsetAsync(clk + 1, 0, sizeof(unsigned long long), st));
-            }
-            AParams ap{};
-            ap.W = W;
-            ap.H = H;
-            ap.spp = ns;
-            ap.n_cand = n_cand;
-            ap.cand_of_row = S.d_cand_of_row;
-            ap.values = S.d_values;
-            ap.codes = S.d_codes;
-            ap.flags = S.d_flags;
-            ap.tile_rows = p->tile_rows;
-            ap.n_shards = p->n_shards;
-            ap.shard_id = p->shard_id;
-            ap.pixels = img->pixels;
-            ap.counters = img->counters;
-            ap.sums = img->sums;
-            ap.pixel_max = img->pixel_max;
-            ap.clk = clk ? clk : ctx->d_clk_dummy;
-            dim3 grid((W + 255) / 256, H), block(256);
-            if (adapt) {
-                AParamsAdapt aa{};
-                static_cast<AParams&>(aa) = ap;
-                aa.mask = adapt->mask;
-                aa.m2 = adapt->m2;
-                if (kp.plane == kPlaneGui)
-                    hipLaunchKernelGGL((accumulate_kernel<kPlaneGui, true>), grid, block, 0, st, aa);
-                else
-                    hipLaunchKernelGGL((accumulate_kernel<kPlaneGrid, true>), grid, block, 0, st, aa);
-            } else if (kp.plane == kPlaneGui)
-                hipLaunchKernelGGL((accumulate_kernel<kPlaneGui, false>), grid, block, 0, st, ap);
-            else
-                hipLaunchKernelGGL((accumulate_kernel<kPlaneGrid, false>), grid, block, 0, st, ap);
-            HIPCHECK(ctx, hipGetLastError());
-            HIPCHECK(ctx, hipEventRecord(tm.a1, st));
-            HIPCHECK(ctx, hipEventRecord(S.done, st));
-        }
-        tmq.recorded = true;
-        if (probe) return probe->rc;
+        tm.units = kp.total_units;
+        return IPT_OK;
+    }
+    // classify / scan / scatter / preset in raygen_kernel's place, the path
+    // kernel over the compact range of the same records with the compact
+    // values as its output, then the values back to their dense places:
+    // everything after reads the launch as an uncompacted one leaves it
+    CompactProbe* probe = c.rq.probe;
+    tm.uring = (int)(ctx->next_uring++ % kClkRing);
+    const CompactBufs cb{S.d_cblk, S.d_src, S.d_cvalues, S.d_values, ctx->d_uring + 2 * tm.uring};
+    KParams kc = kp;
+    if (probe) kc.count = 0;
+    hipLaunchKernelGGL(compact_classify_kernel, dim3(nblk), dim3(256), 0, ss, kc, cb.blocks);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(256), 0, ss, cb.blocks, nblk);
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3(nblk), dim3(256), 0, ss, kc, (const unsigned int*)cb.blocks, cb.src);
+    hipLaunchKernelGGL(compact_preset_kernel, dim3(1), dim3(64), 0, ss, (const unsigned int*)cb.blocks, nblk,
+                       kp.total_units, S.d_unit, cb.ring);
+    HIPCHECK(ctx, hipGetLastError());
+    if (probe) {
+        // ipt_compact_plan: the plan of the call's first launch, no path kernel
+        unsigned long long h[2] = {0, 0};
+        HIPCHECK(ctx, hipStreamSynchronize(ss));
+        HIPCHECK(ctx, hipMemcpy(h, cb.ring, sizeof h, hipMemcpyDeviceToHost));
+        probe->start = h[0];
+        probe->n_active = h[1];
+        if (h[1] > kp.total_units || h[1] > probe->cap)
+            probe->rc = fail(ctx, IPT_E_INVALID, "ipt_compact_plan: host_src holds fewer than n_active entries");
+        else if (h[1])
+            HIPCHECK(ctx, hipMemcpy(probe->host_src, cb.src + (kp.total_units - h[1]), h[1] * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost));
+        return IPT_OK;
+    }
+    kc.values = cb.cvalues;
+    if (const int rc = launch_path(ctx, kc, ss, c.m)) return rc;
+    S.seq = kp.drain_seq;
+    hipLaunchKernelGGL(compact_expand_kernel, dim3(nblk), dim3(256), 0, ss, cb, nblk, kp.total_units);
+    HIPCHECK(ctx, hipGetLastError());
+    tm.units = kp.total_units;
+    return IPT_OK;
+}
+
+// The call's host outputs of passes [s0, s0 + ns), [spp][H][W] (whole frames:
+// per_pass == W * H), copied on the slot stream after the samples.
+int queue_host_copies(ipt_ctx* ctx, const Call& c, const WorkSlot& S, int s0, int ns) {
+    const LaunchRequest& rq = c.rq;
+    const size_t off = (size_t)s0 * c.per_pass, n = (size_t)ns * c.per_pass;
+    const hipStream_t ss = S.st;
+    if (rq.host_values) {
+        HIPCHECK(ctx, hipMemcpyAsync(rq.host_values + off, S.d_values, sizeof(float) * n, hipMemcpyDeviceToHost, ss));
+        HIPCHECK(ctx, hipMemcpyAsync(rq.host_codes + off, S.d_codes, n, hipMemcpyDeviceToHost, ss));
+    }
+    if (rq.host_kinds) HIPCHECK(ctx, hipMemcpyAsync(rq.host_kinds + off, S.d_kinds, n, hipMemcpyDeviceToHost, ss));
+    if (rq.host_hits)
+        HIPCHECK(ctx, hipMemcpyAsync(rq.host_hits + off * 6, S.d_hits, sizeof(float) * 6 * n, hipMemcpyDeviceToHost, ss));
+    return IPT_OK;
+}
+
+// ipt_guides_device (one pass, whole frame: unit = iy * W + ix): the scatter
+// runs on the caller's stream, in call order, after the preview kernel; the
+// slot's buffers are free again once it has run.
+int queue_guide_scatter(ipt_ctx* ctx, const Call& c, WorkSlot& S, const ChunkTiming& tm) {
+    const hipStream_t st = c.rq.st;
+    HIPCHECK(ctx, hipStreamWaitEvent(st, tm.t1, 0));
+    HIPCHECK(ctx, ipt_internal::launch_guide_scatter(st, S.d_kinds, S.d_hits, c.rq.guides, c.p->width, c.p->height,
+                                                     plane_of(c.p) == kPlaneGui));
+    HIPCHECK(ctx, hipEventRecord(S.done, st));
+    return IPT_OK;
+}
+
+// The render plane's replay of the launch's ns passes: on the caller's stream,
+// in call order, after this launch's path kernel.
+int queue_accumulate(ipt_ctx* ctx, const Call& c, WorkSlot& S, int ns, ChunkTiming& tm) {
+    const ipt_params* p = c.p;
+    const LaunchRequest& rq = c.rq;
+    const hipStream_t st = rq.st;
+    HIPCHECK(ctx, hipStreamWaitEvent(st, tm.t1, 0));
+    HIPCHECK(ctx, hipEventRecord(tm.a0, st));
+    unsigned long long* clk = nullptr;
+    if (ctx->d_clk) {
+        tm.clk = (int)(ctx->next_clk++ % kClkRing);
+        clk = ctx->d_clk + 2 * tm.clk;
+        HIPCHECK(ctx, hipMemsetAsync(clk, 0xff, sizeof(unsigned long long), st));
+        HIPCHECK(ctx, hipMemsetAsync(clk + 1, 0, sizeof(unsigned long long), st));
+    }
+    // (AParams' members in their order, then the ADAPT instances' two)
+    const ipt_image& img = *rq.img;
+    const AParamsAdapt aa{{p->width, p->height, ns, c.n_cand, S.d_cand_of_row, S.d_values, S.d_codes, S.d_flags,
+                           p->tile_rows, p->n_shards, p->shard_id, img.pixels, img.counters, img.sums, img.pixel_max,
+                           clk ? clk : ctx->d_clk_dummy},
+                          rq.mask, rq.m2};
+    const AParams& ap = aa;
+    const dim3 grid((p->width + 255) / 256, p->height), block(256);
+    const bool gui = plane_of(p) == kPlaneGui;
+    if (c.m.adapt) {
+        if (gui)
+            hipLaunchKernelGGL((accumulate_kernel<kPlaneGui, true>), grid, block, 0, st, aa);
+        else
+            hipLaunchKernelGGL((accumulate_kernel<kPlaneGrid, true>), grid, block, 0, st, aa);
+    } else if (gui)
+        hipLaunchKernelGGL((accumulate_kernel<kPlaneGui, false>), grid, block, 0, st, ap);
+    else
+        hipLaunchKernelGGL((accumulate_kernel<kPlaneGrid, false>), grid, block, 0, st, ap);
+    HIPCHECK(ctx, hipGetLastError());
+    HIPCHECK(ctx, hipEventRecord(tm.a1, st));
+    HIPCHECK(ctx, hipEventRecord(S.done, st));
+    return IPT_OK;
+}
+
+// One launch: passes [s0, s0 + ns) of the call on the next slot.
+int queue_launch(ipt_ctx* ctx, Call& c, int s0, int ns) {
+    const LaunchRequest& rq = c.rq;
+    WorkSlot* slot = nullptr;
+    int rc = take_slot(ctx, c, slot);
+    if (rc) return rc;
+    WorkSlot& S = *slot;
+    const unsigned sidx = (unsigned)(slot - ctx->slot);
+    const KParams kp = launch_params(ctx, c, S, s0, ns);
+    if (kp.total_units >= (1ull << 32)) return fail(ctx, IPT_E_INVALID, "more than 2^32 work units in one launch");
+    // bounded timing backlog: settle launches far behind (they are done or
+    // nearly so; the queue of launches ahead is untouched)
+    while (ctx->pending.size() >= 8) {
+        rc = settle_oldest(ctx);
+        if (rc) return rc;
+    }
+    ChunkTiming ev;
+    ev.t0 = pool_event(ctx);
+    ev.t1 = pool_event(ctx);
+    if (rq.img) {
+        ev.a0 = pool_event(ctx);
+        ev.a1 = pool_event(ctx);
+    }
+    if (!ev.t0 || !ev.t1 || (rq.img && (!ev.a0 || !ev.a1))) {
+        pool_return(ctx, ev);
+        return fail(ctx, IPT_E_DEVICE, "hipEventCreate failed");
+    }
+    // pushed before the first fallible call: drain settles it also on an error
+    // below (unrecorded, untimed)
+    ctx->pending.push_back(ev);
+    ChunkTiming& tm = ctx->pending.back();
+    S.used = true;
+    S.idle = false;
+    S.total = 0;  // (until its kernel is queued: a successor must not wait on a launch that failed)
+    // the slot stream: t0..t1 is the path's per-sample work, raygen_kernel
+    // (render_sample's jitter, camera ray, Philox block 0; ~0.2 % of a C2
+    // launch) and path_kernel
+    const hipStream_t ss = S.st;
+    if (kp.mask && !c.mask_waited[sidx]) {
+        // raygen reads caller memory: this slot stream's launches of the
+        // call run after what the caller's stream holds at the call
+        if (!S.mask_ready) HIPCHECK(ctx, hipEventCreateWithFlags(&S.mask_ready, hipEventDisableTiming));
+        HIPCHECK(ctx, hipEventRecord(S.mask_ready, rq.st));
+        HIPCHECK(ctx, hipStreamWaitEvent(ss, S.mask_ready, 0));
+        c.mask_waited[sidx] = true;
+    }
+    // (a compacting launch's counter is set by compact_preset_kernel)
+    if (!c.m.compact) HIPCHECK(ctx, hipMemsetAsync(S.d_unit, 0, sizeof(unsigned long long), ss));
+    HIPCHECK(ctx, hipMemsetAsync(S.d_flags, 0, (size_t)kp.W * kp.H, ss));
+    HIPCHECK(ctx, hipEventRecord(tm.t0, ss));
+    rc = queue_samples(ctx, c, S, kp, s0, tm);
+    if (rc) return rc;
+    S.total = kp.total_units;
+    HIPCHECK(ctx, hipEventRecord(tm.t1, ss));
+    HIPCHECK(ctx, hipEventRecord(S.path_end, ss));
+    rc = queue_host_copies(ctx, c, S, s0, ns);
+    if (rc) return rc;
+    // S.done: after the slot's last reader, the guide scatter, the accumulate or the host copies
+    if (rq.guides)
+        rc = queue_guide_scatter(ctx, c, S, tm);
+    else if (!rq.img)
+        HIPCHECK(ctx, hipEventRecord(S.done, ss));
+    if (!rc && rq.img) rc = queue_accumulate(ctx, c, S, ns, tm);
+    if (rc) return rc;
+    tm.recorded = true;
+    return IPT_OK;
+}
+
+// Queues the call's passes as launches of equal chunks, each on the next work
+// slot (WorkSlot): the samples on the slot's stream, their readers -- the
+// plane's replay or the guide scatter on the caller's stream, the host copies
+// on the slot's -- after them. With a mask, each slot stream the call uses
+// first waits for the caller's stream as it stands at the call (the mask is
+// caller memory, written there). The probe's call ends after its first launch.
+int render_chunks(ipt_ctx* ctx, const ipt_params* p, const LaunchRequest& rq) {
+    Call c{p, rq, mode_of(p, rq)};
+    candidate_rows(p, c.rows, c.of_row);
+    c.n_cand = (int)c.rows.size();
+    c.per_pass = (size_t)c.n_cand * p->width;
+    if (c.per_pass == 0 || p->spp == 0) return IPT_OK;
+    c.chunk = chunk_passes(ctx, c);
+    // (the preview and the replay read neither table: a context that only
+    // renders previews never builds them)
+    if (c.m.traced) {
+        int rc = ensure_cos_tables(ctx, rq.st);
+        if (!rc && frame_table_user(ctx->scene.kp.geometry_kind)) rc = ensure_frame_table(ctx, rq.st);  // path_kernel's frame builds
+        if (rc) return rc;
+    }
+    for (int s0 = 0; s0 < p->spp; s0 += c.chunk) {
+        const int rc = queue_launch(ctx, c, s0, std::min(c.chunk, p->spp - s0));
+        if (rc) return rc;
+        if (rq.probe) return rq.probe->rc;
     }
     return IPT_OK;
 }
@@ -4157,8 +4157,7 @@ int ipt_create(int hip_device, ipt_ctx** out) {
             if (S.d_drained) hipFree(S.d_drained);
             S.d_drained = nullptr;
         }
-    if (hipMalloc(&ctx->d_counters, sizeof(unsigned long long) * (kNumCounters + 2 * kProfPhases + kStamps)) != hipSuccess ||
-        hipMalloc(&ctx->d_wall, sizeof(Frame) * 5) != hipSuccess) {
+    if (hipMalloc(&ctx->d_counters, sizeof(unsigned long long) * (kNumCounters + 2 * kProfPhases + kStamps)) != hipSuccess) {
         ipt_destroy(ctx);
         return fail(nullptr, IPT_E_OOM, "hipMalloc failed");
     }
@@ -4183,24 +4182,13 @@ void ipt_destroy(ipt_ctx* ctx) {
     hipSetDevice(ctx->device);
     (void)drain(ctx);  // nothing queued may still use the buffers
     ipt_internal::post_release(ctx);
-    void* bufs[] = {ctx->d_cdf_lo, ctx->d_lgrid, ctx->d_lax, ctx->d_bvh_nodes, ctx->d_bvh_prims, ctx->d_light_nodes, ctx->d_lights, ctx->d_weights, ctx->d_cdf, ctx->d_wall, ctx->d_spheres,
-                    ctx->d_counters, ctx->d_cos_a, ctx->d_cos_b, ctx->d_clk, ctx->d_uring,
-                    ctx->d_grid_start, ctx->d_grid_items, ctx->d_grid_c4, ctx->d_frame_sc};
-    for (void* b : bufs)
+    // the context's own tables and rings (the scene's buffers go with its record)
+    for (void* b : {(void*)ctx->d_counters, (void*)ctx->d_cos_a, (void*)ctx->d_cos_b, (void*)ctx->d_clk,
+                    (void*)ctx->d_uring, (void*)ctx->d_frame_sc})
         if (b) hipFree(b);
-    for (WorkSlot& S : ctx->slot) {
-        void* sb[] = {S.d_values, S.d_codes, S.d_rg, S.d_kinds, S.d_hits, S.d_flags, S.d_cand_rows, S.d_cand_of_row, S.d_unit, S.d_drained,
-                      S.d_cvalues, S.d_src, S.d_cblk};
-        for (void* b : sb)
-            if (b) hipFree(b);
-        if (S.done) hipEventDestroy(S.done);
-        if (S.path_end) hipEventDestroy(S.path_end);
-        if (S.mask_ready) hipEventDestroy(S.mask_ready);
-        if (S.st) hipStreamDestroy(S.st);
-    }
+    for (WorkSlot& S : ctx->slot) S.release();
     for (hipEvent_t e : ctx->ev_pool) hipEventDestroy(e);
-    for (void* b : {(void*)ctx->rp.d_pixels, (void*)ctx->rp.d_counters, (void*)ctx->rp.d_sums, (void*)ctx->rp.d_pmax})
-        if (b) hipFree(b);
+    ctx->rp.release();
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -4220,7 +4208,6 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
         return fail(ctx, IPT_E_UNSUPPORTED, "n_lights out of range");
     if (s->n_spheres < 0 || (s->n_spheres > 0 && !s->spheres))
         return fail(ctx, IPT_E_INVALID, "bad sphere array");
-    hipSetDevice(ctx->device);
     const int nl = s->n_lights;
     std::vector<LightDev> L(std::max(nl, 1));
     std::vector<float> powers(std::max(nl, 1));
@@ -4326,15 +4313,14 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     bool cdf_mono = true;
     for (int i = 0; i <= nl; ++i)
         if (!(cdf[i] == cdf[i]) || (i > 0 && !(cdf[i - 1] <= cdf[i]))) cdf_mono = false;
-    // Device phase, transactional: every buffer of the new scene is allocated
-    // and filled in a temporary first. Until all of them succeeded the context
-    // has no scene (renders fail with IPT_E_NOSCENE, never launch on a
-    // half-built one); on success the old buffers are freed and the new ones
-    // swapped in. IPT_TEST_FAIL_UPLOAD_ALLOC=k makes the k-th allocation of an
-    // upload fail (tests/test_gpu_parity.py exercises the failure path).
-    ctx->has_scene = false;
-    int n_alloc = 0;
-    int fail_at = 0;
+    // Device phase, transactional: the new scene is built in a fresh record,
+    // every buffer allocated and filled there first. Until all of them
+    // succeeded the context has no scene (renders fail with IPT_E_NOSCENE,
+    // never launch on a half-built one); on success the record is swapped in
+    // and the old one frees its buffers. IPT_TEST_FAIL_UPLOAD_ALLOC=k makes the
+    // k-th allocation of an upload fail (tests/test_gpu_parity.py exercises
+    // the failure path).
+    int n_alloc = 0, fail_at = 0;
     if (const char* e = std::getenv("IPT_TEST_FAIL_UPLOAD_ALLOC")) fail_at = std::atoi(e);
     auto upload = [&](auto& buf, const auto* src, size_t count) -> int {
         using T = std::remove_pointer_t<decltype(buf.p)>;
@@ -4343,72 +4329,101 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
         if (count) HIPCHECK(ctx, hipMemcpy(buf.p, src, sizeof(T) * count, hipMemcpyHostToDevice));
         return IPT_OK;
     };
-    DevBuf<int> n_grid_start, n_lgrid, n_cdf_lo;
-    DevBuf<LightAx> n_lax;
-    DevBuf<BvhSphere> n_grid_items, n_bvh_prims;
-    DevBuf<float4> n_grid_c4;
-    DevBuf<BvhNode> n_light_nodes, n_bvh_nodes;
-    DevBuf<LightDev> n_lights;
-    DevBuf<float> n_weights, n_cdf;
-    DevBuf<float4> n_spheres;
-    DevBuf<Frame> n_wall;
+    Scene sc;  // (kp all zero: what this scene does not set, no kernel reads -- DESIGN.md 5)
+    Scene::Bufs& b = sc.bufs;
+    KParams& k = sc.kp;
     int rc = IPT_OK;
-    if (use_grid && !rc) rc = upload(n_grid_start, grid.start.data(), grid.start.size());
-    if (use_grid && !rc) rc = upload(n_grid_items, grid.items.data(), grid.items.size());
+    if (use_grid && !rc) rc = upload(b.grid_start, grid.start.data(), grid.start.size());
+    if (use_grid && !rc) rc = upload(b.grid_items, grid.items.data(), grid.items.size());
     // the wave walk's items: [items] centre/radius, then [items] original indices
+    const size_t n_items = use_grid ? grid.items.size() : 0;
     if (use_grid && !rc) {
-        const size_t ni = grid.items.size();
-        std::vector<float4> c4(ni + (ni + 3) / 4);
-        int* idx = reinterpret_cast<int*>(c4.data() + ni);
-        for (size_t k = 0; k < ni; ++k) {
-            const BvhSphere& b = grid.items[k];
-            c4[k] = make_float4(b.c[0], b.c[1], b.c[2], b.r);
-            idx[k] = b.index;
+        std::vector<float4> c4(n_items + (n_items + 3) / 4);
+        int* idx = reinterpret_cast<int*>(c4.data() + n_items);
+        for (size_t i = 0; i < n_items; ++i) {
+            const BvhSphere& it = grid.items[i];
+            c4[i] = make_float4(it.c[0], it.c[1], it.c[2], it.r);
+            idx[i] = it.index;
         }
-        rc = upload(n_grid_c4, c4.data(), c4.size());
+        rc = upload(b.grid_c4, c4.data(), c4.size());
     }
-    if (!lnodes.empty() && !rc) rc = upload(n_light_nodes, lnodes.data(), lnodes.size());
-    if (lg.pattern && !rc) rc = upload(n_lgrid, lg.cells.data(), lg.cells.size());
+    if (!lnodes.empty() && !rc) rc = upload(b.light_nodes, lnodes.data(), lnodes.size());
+    if (lg.pattern && !rc) rc = upload(b.lgrid, lg.cells.data(), lg.cells.size());
     std::vector<LightAx> laxr;
     if (lg.pattern)
         for (int i = 0; i < nl; ++i) laxr.push_back(light_ax_record(L[i], lg.pattern, wts[i]));
-    if (lg.pattern && !rc) rc = upload(n_lax, laxr.data(), laxr.size());
-    if (use_cdf_lo && !rc) rc = upload(n_cdf_lo, cdf_lo.data(), cdf_lo.size());
-    if (!bnodes.empty() && !rc) rc = upload(n_bvh_nodes, bnodes.data(), bnodes.size());
-    if (!bnodes.empty() && !rc) rc = upload(n_bvh_prims, bprims.data(), bprims.size());
-    if (!rc) rc = upload(n_lights, L.data(), L.size());
-    if (!rc) rc = upload(n_weights, wts.data(), (size_t)nl + 1);
-    if (!rc) rc = upload(n_cdf, cdf.data(), (size_t)nl + 1);
-    if (!rc) rc = upload(n_wall, wall, 5);
-    if (!rc) rc = upload(n_spheres, sph.data(), sph.size());
-    if (rc) return rc;  // the temporaries free themselves; the context keeps no scene
-    void* old[] = {ctx->d_lights, ctx->d_weights, ctx->d_cdf, ctx->d_spheres, ctx->d_bvh_nodes, ctx->d_bvh_prims,
-                   ctx->d_light_nodes, ctx->d_grid_start, ctx->d_grid_items, ctx->d_grid_c4, ctx->d_wall, ctx->d_lgrid, ctx->d_lax,
-                   ctx->d_cdf_lo};
-    for (void* b : old)
-        if (b) hipFree(b);
-    ctx->d_grid_start = n_grid_start.release();
-    ctx->d_grid_items = n_grid_items.release();
-    ctx->d_grid_c4 = n_grid_c4.release();
-    ctx->n_grid = 0;
+    if (lg.pattern && !rc) rc = upload(b.lax, laxr.data(), laxr.size());
+    if (use_cdf_lo && !rc) rc = upload(b.cdf_lo, cdf_lo.data(), cdf_lo.size());
+    if (!bnodes.empty() && !rc) rc = upload(b.bvh_nodes, bnodes.data(), bnodes.size());
+    if (!bnodes.empty() && !rc) rc = upload(b.bvh_prims, bprims.data(), bprims.size());
+    if (!rc) rc = upload(b.lights, L.data(), L.size());
+    if (!rc) rc = upload(b.weights, wts.data(), (size_t)nl + 1);
+    if (!rc) rc = upload(b.cdf, cdf.data(), (size_t)nl + 1);
+    if (!rc) rc = upload(b.wall, wall, 5);
+    if (!rc) rc = upload(b.spheres, sph.data(), sph.size());
+    if (rc) return rc;  // the record frees what it holds; the context keeps no scene
+    k.geometry_kind = s->geometry_kind;
+    k.n_lights = nl;
+    k.lights = b.lights.p;
+    k.weights = b.weights.p;
+    k.cdf = b.cdf.p;
+    k.wall_frames = b.wall.p;
+    const ipt_camera& c = s->camera;
+    k.cam_pos = v3(c.position[0], c.position[1], c.position[2]);
+    k.cam_dir = v3(c.direction[0], c.direction[1], c.direction[2]);
+    k.cam_right = v3(c.right[0], c.right[1], c.right[2]);
+    k.cam_up = v3(c.up[0], c.up[1], c.up[2]);
+    k.n_spheres = s->n_spheres;
+    k.spheres = b.spheres.p;
     if (use_grid) {
-        ctx->n_grid = (int)(grid.start.size() - 1);
-        ctx->grid_n_items = grid.items.size();
-        ctx->bvh_tmargin = grid.tmargin;
-        grid.start.clear();
-        grid.items.clear();
-        ctx->grid = grid;
+        k.n_grid = (int)(grid.start.size() - 1);
+        k.bvh_tmargin = grid.tmargin;
+        for (int a = 0; a < 3; ++a) {
+            k.grid_g0[a] = grid.g0[a];
+            k.grid_h[a] = grid.h[a];
+            k.grid_inv_h[a] = grid.inv_h[a];
+            k.grid_n[a] = grid.n[a];
+            k.grid_g1[a] = grid.g0[a] + (float)grid.n[a] * grid.h[a];
+        }
+        k.grid_m = grid.m;
+        k.grid_start = b.grid_start.p;
+        k.grid_items = b.grid_items.p;
+        k.grid_c4 = b.grid_c4.p;
+        k.grid_idx = reinterpret_cast<const int*>(b.grid_c4.p + n_items);
     }
-    ctx->d_light_nodes = n_light_nodes.release();
-    ctx->n_light_nodes = lnodes.empty() ? 0 : n_lnodes;
-    ctx->d_lgrid = n_lgrid.release();
-    ctx->d_lax = n_lax.release();
-    ctx->d_cdf_lo = n_cdf_lo.release();
-    lg.cells.clear();
-    ctx->lgrid = lg;
-    ctx->cdf_bsearch = cdf_mono ? 1 : 0;
-    ctx->pk_u0 = word_threshold(cdf[0]);
-    ctx->pk_u1 = word_threshold(nl >= 1 ? cdf[1] : 0.0f);
+    if (!bnodes.empty()) {
+        k.bvh_nodes = b.bvh_nodes.p;
+        k.bvh_prims = b.bvh_prims.p;
+        k.n_nodes = per_order;  // nodes per octant order; buffer holds kBvhOrders of them
+        k.bvh_tmargin = tmargin;
+    }
+    k.light_nodes = b.light_nodes.p;
+    k.n_light_nodes = lnodes.empty() ? 0 : n_lnodes;
+    // light BVH staged in LDS (IPT_LNODES_LDS=0 at ipt_create keeps it in
+    // global memory): the resumable light walk runs at 3 workgroups/CU, which
+    // the extra LDS keeps, and gains 10 % on C5 (43.8 vs 40.2 Mpaths/s)
+    k.lnodes_lds = (ctx->lnodes_lds && k.n_light_nodes > 0 && k.n_light_nodes <= kLdsLightNodesMax) ? 1 : 0;
+    k.lgrid = b.lgrid.p;
+    k.lax = reinterpret_cast<const float4*>(b.lax.p);
+    k.cdf_lo = b.cdf_lo.p;
+    sc.light_pattern = lg.pattern;
+    k.lg_nu = lg.nu;
+    k.lg_nv = lg.nv;
+    k.lg_u0 = lg.u0;
+    k.lg_v0 = lg.v0;
+    k.lg_icw = lg.icw;
+    k.lg_ich = lg.ich;
+    k.lg_e = lg.e;
+    k.lg_pn = lg.pn;
+    k.lg_nn = lg.nn;
+    k.cdf_bsearch = cdf_mono ? 1 : 0;
+    k.pk_u0 = word_threshold(cdf[0]);
+    k.pk_u1 = word_threshold(nl >= 1 ? cdf[1] : 0.0f);
+    // cdf[nl]'s threshold in every scene: the lattice instances' pre-skip
+    // compares the next pick word with it in every step (pre_ft), also where
+    // no leaf is taken (cdf_p2 == 0) -- there a taken word picks a light, below
+    // cdf[nl - 1] <= cdf[nl], and must read as three draws
+    k.cdf_end_t = (uint32_t)(word_threshold(cdf[nl]) >> 8);
     // nearly equal lights (e.g. 256 of one power: weights within rounding of
     // 0.5/256 = 2^-9): with w = 2^-e and every light's |cdf[i] - (i+1) w| <= d
     // < w/2 on a non-decreasing cdf, the first c with r < cdf[c] is ce - 1, ce
@@ -4416,44 +4431,32 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
     // <= (ce-1) w + d < ce w <= r and cdf[ce+1] >= (ce+2) w - d > r + w - d > r.
     // Past the lights (ce >= nl) the scan's answer is ce's clamp to nl - 1, then
     // cdf[nl]. The kernel reads cdf[ce-1] and cdf[ce] only.
-    ctx->cdf_p2 = 0;
-    // cdf[nl]'s threshold in every scene, not a previous scene's: the lattice
-    // instances' pre-skip compares the next pick word with it in every step
-    // (pre_ft), also where no leaf is taken (cdf_p2 == 0) -- there a taken
-    // word picks a light, below cdf[nl - 1] <= cdf[nl], and must read as
-    // three draws
-    ctx->cdf_end = cdf[nl];
-    for (int e = 1; cdf_mono && nl > kLdsLights && !any_round && e <= 20 && !ctx->cdf_p2; ++e) {
+    for (int e = 1; cdf_mono && nl > kLdsLights && !any_round && e <= 20 && !k.cdf_p2; ++e) {
         const double w = std::ldexp(1.0, -e);
         bool ok = (double)nl * w <= 1.0;
         for (int i = 0; ok && i < nl; ++i) ok = std::fabs((double)cdf[i] - (double)(i + 1) * w) < 0.25 * w;
-        if (ok) {
-            ctx->cdf_p2 = 1;
-            // exactly uniform on the draw's 24-bit integer: every light's
-            // ceil(cdf[i] 2^24) is (i+1) 2^(24-e) (C5's 256 equal emitters),
-            // so the integer pick reads no cdf entry at all (KParams::cdf_p2 2)
-            if (e <= 24) {
-                bool exact = true;
-                for (int i = 0; exact && i < nl; ++i)
-                    exact = (word_threshold(cdf[i]) >> 8) == ((unsigned long long)(i + 1) << (24 - e));
-                if (exact) ctx->cdf_p2 = 2;
-            }
-            ctx->cdf_p2e = e;
-            ctx->cdf_end = cdf[nl];
-        }
+        if (!ok) continue;
+        k.cdf_p2 = 1;
+        k.cdf_p2e = e;
+        // exactly uniform on the draw's 24-bit integer: every light's
+        // ceil(cdf[i] 2^24) is (i+1) 2^(24-e) (C5's 256 equal emitters),
+        // so the integer pick reads no cdf entry at all (KParams::cdf_p2 2)
+        bool exact = true;
+        for (int i = 0; exact && i < nl; ++i)
+            exact = (word_threshold(cdf[i]) >> 8) == ((unsigned long long)(i + 1) << (24 - e));
+        if (exact) k.cdf_p2 = 2;
     }
-    ctx->any_round_light = any_round;
+    sc.any_round_light = any_round;
     // the axis-aligned single-light instances also take the range-free roots
     // and quotients: only where their ranges are proven (sphere-in-box scenes)
-    ctx->light_axis = (nl == 1 && !any_round) ? axis_aligned_light(L[0]) : 0;
-    if (ctx->light_axis && !(s->geometry_kind == IPT_GEOM_SPHERE_IN_BOX && light_ranges_box(L[0], 2, cam)))
-        ctx->light_axis = 0;
+    sc.light_axis = (nl == 1 && !any_round) ? axis_aligned_light(L[0]) : 0;
+    if (sc.light_axis && !(s->geometry_kind == IPT_GEOM_SPHERE_IN_BOX && light_ranges_box(L[0], 2, cam)))
+        sc.light_axis = 0;
     // skip-ahead plane: one area light (or a lattice, whose lights share P.z
     // and n.z bit for bit) whose axes have zero z components, so that every
     // sampled point (x*u1 + y*u2) + P has z = P.z exactly, and whose normal is
     // (+-0, +-0, n.z): a light sample's cosinus then has the sign of
     // n.z * (o.z - P.z) whatever the draws (lighting.cpp:93-104, 125-134)
-    ctx->sa_on = 0;
     {
         auto zero = [](float f) { return (f2u(f) & 0x7fffffffu) == 0u; };
         bool ok = nl >= 1 && !any_round && (nl == 1 || lg.pattern != 0);
@@ -4464,56 +4467,31 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
                  f2u(L[i].P.z) == f2u(L[0].P.z) && f2u(L[i].n.z) == f2u(L[0].n.z);
         float sa_cl = 0.0f;
         if (ok) {
-            ctx->sa_on = 1;
-            ctx->sa_pz = L[0].P.z;
-            ctx->sa_nz = L[0].n.z;
+            k.sa_on = 1;
+            k.sa_pz = L[0].P.z;
+            k.sa_nz = L[0].n.z;
             // UnionDdf::sample picks a light (c < nl) iff r < cdf[c] for some
             // c < nl, i.e. iff r < cdf[nl - 1] on a non-decreasing cdf
             sa_cl = (nl == 1 || cdf_mono) ? cdf[nl - 1] : 0.0f;
         }
-        ctx->sa_u = word_threshold(sa_cl);
+        k.sa_u = word_threshold(sa_cl);
     }
-    ctx->d_bvh_nodes = n_bvh_nodes.release();
-    ctx->d_bvh_prims = n_bvh_prims.release();
-    ctx->n_nodes = 0;
-    if (!bnodes.empty()) {
-        ctx->n_nodes = per_order;  // nodes per octant order; buffer holds kBvhOrders of them
-        ctx->bvh_tmargin = tmargin;
-    }
-    ctx->d_lights = n_lights.release();
-    ctx->d_weights = n_weights.release();
-    ctx->d_cdf = n_cdf.release();
-    ctx->d_wall = n_wall.release();
-    ctx->d_spheres = n_spheres.release();
-    ctx->geometry_kind = s->geometry_kind;
-    ctx->n_lights = nl;
-    ctx->n_spheres = s->n_spheres;
-    const ipt_camera& c = s->camera;
-    ctx->cam_pos = v3(c.position[0], c.position[1], c.position[2]);
-    ctx->cam_dir = v3(c.direction[0], c.direction[1], c.direction[2]);
-    ctx->cam_right = v3(c.right[0], c.right[1], c.right[2]);
-    ctx->cam_up = v3(c.up[0], c.up[1], c.up[2]);
     // every ray origin (camera, surface points within B) inside 2^39: the box
     // planes may use the range-free division (box_plane_t<true>)
     const float lim = 549755813888.0f;  // 2^39
-    ctx->box_inrange = B < lim && std::fabs(cam[0]) < lim && std::fabs(cam[1]) < lim && std::fabs(cam[2]) < lim;
+    k.box_inrange = B < lim && std::fabs(cam[0]) < lim && std::fabs(cam[1]) < lim && std::fabs(cam[2]) < lim;
+    std::swap(ctx->scene, sc);  // (sc, now the previous scene, frees its buffers on return)
     ctx->has_scene = true;
     return IPT_OK;
 }
 
 int ipt_render_device_async(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, void* hip_stream) {
-    int rc = validate(ctx, p);
-    if (rc) return rc;
-    if (!img || !img->pixels || !img->counters) return fail(ctx, IPT_E_INVALID, "image pixels/counters are NULL");
-    hipSetDevice(ctx->device);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-    return render_chunks(ctx, p, img, st, nullptr, nullptr);
+    return ipt_render_masked_device_async(ctx, p, img, nullptr, nullptr, hip_stream);  // (the unmasked launches)
 }
 
 int ipt_render_masked_device_async(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, const uint8_t* dev_mask,
                                    float* dev_m2, void* hip_stream) {
-    int rc = validate(ctx, p);
-    if (rc) return rc;
+    if (const int rc = validate(ctx, p)) return rc;
     if (!img || !img->pixels || !img->counters) return fail(ctx, IPT_E_INVALID, "image pixels/counters are NULL");
     {
         // the mask and m2 may not share a byte with an image buffer (or each other)
@@ -4528,10 +4506,12 @@ int ipt_render_masked_device_async(ipt_ctx* ctx, const ipt_params* p, ipt_image*
             }
     }
     hipSetDevice(ctx->device);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-    if (!dev_mask && !dev_m2) return render_chunks(ctx, p, img, st, nullptr, nullptr);  // the unmasked launches
-    const AdaptArgs adapt{dev_mask, dev_m2};
-    return render_chunks(ctx, p, img, st, nullptr, nullptr, false, nullptr, nullptr, nullptr, &adapt);
+    LaunchRequest rq;
+    rq.img = img;
+    rq.st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    rq.mask = dev_mask;
+    rq.m2 = dev_m2;
+    return render_chunks(ctx, p, rq);
 }
 
 int ipt_render_masked_device(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, const uint8_t* dev_mask, float* dev_m2,
@@ -4613,9 +4593,7 @@ int ipt_render_wait(ipt_ctx* ctx) {
 }
 
 int ipt_render_device(ipt_ctx* ctx, const ipt_params* p, ipt_image* img, void* hip_stream) {
-    const int rc = ipt_render_device_async(ctx, p, img, hip_stream);
-    const int rw = ctx ? drain(ctx) : IPT_OK;
-    return rc ? rc : rw;
+    return ipt_render_masked_device(ctx, p, img, nullptr, nullptr, hip_stream);
 }
 
 int ipt_render(ipt_ctx* ctx, const ipt_params* p, ipt_image* himg) {
@@ -4628,9 +4606,7 @@ int ipt_render(ipt_ctx* ctx, const ipt_params* p, ipt_image* himg) {
     const int W = p->width, H = p->height;
     const bool has_sums = himg->sums != nullptr, has_pmax = himg->pixel_max != nullptr;
     if (R.W != W || R.H != H || R.has_sums != has_sums || R.has_pmax != has_pmax || !R.d_pixels) {
-        for (void* b : {(void*)R.d_pixels, (void*)R.d_counters, (void*)R.d_sums, (void*)R.d_pmax})
-            if (b) hipFree(b);
-        R = ResidentPlane{};
+        R.release();
         const size_t npix = (size_t)W * H;
         HIPCHECK(ctx, hipMalloc(&R.d_pixels, npix * 4));
         HIPCHECK(ctx, hipMalloc(&R.d_counters, npix * 4));
@@ -4684,7 +4660,10 @@ int ipt_render(ipt_ctx* ctx, const ipt_params* p, ipt_image* himg) {
     }
     R.shadow_ok = false;  // (valid again only once this call's rows are back)
     ipt_image d{R.d_pixels, R.d_counters, R.d_sums, R.d_pmax};
-    rc = render_chunks(ctx, p, &d, st, nullptr, nullptr);
+    LaunchRequest rq;
+    rq.img = &d;
+    rq.st = st;
+    rc = render_chunks(ctx, p, rq);
     if (rc) {
         (void)drain(ctx);  // nothing queued may still use the buffers
         (void)hipStreamSynchronize(st);
@@ -4718,47 +4697,56 @@ int ipt_transfer_bytes(ipt_ctx* ctx, uint64_t* host_to_device, uint64_t* device_
     return IPT_OK;
 }
 
-int ipt_render_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t* codes) {
-    int rc = validate(ctx, p);
+// A call with host outputs: queued on the context's stream, then waited for.
+static int render_to_host(ipt_ctx* ctx, const ipt_params* p, LaunchRequest rq) {
+    rq.st = ctx->stream;
+    const int rc = render_chunks(ctx, p, rq);
+    const int rw = drain(ctx);  // the host copies run on the slot streams
     if (rc) return rc;
+    if (rw) return rw;
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return IPT_OK;
+}
+
+int ipt_render_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t* codes) {
+    if (const int rc = validate(ctx, p)) return rc;
     if (!values || !codes) return fail(ctx, IPT_E_INVALID, "values/codes are NULL");
     if (p->n_shards > 1) return fail(ctx, IPT_E_UNSUPPORTED, "ipt_render_values renders whole frames");
     hipSetDevice(ctx->device);
-    rc = render_chunks(ctx, p, nullptr, ctx->stream, values, codes);
-    const int rw = drain(ctx);  // the host copies run on the slot streams
-    if (rc) return rc;
-    if (rw) return rw;
-    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return IPT_OK;
+    LaunchRequest rq;
+    rq.host_values = values;
+    rq.host_codes = codes;
+    return render_to_host(ctx, p, rq);
 }
 
 int ipt_preview_values(ipt_ctx* ctx, const ipt_params* p, float* values, uint8_t* codes, uint8_t* kinds, float* hits) {
-    int rc = validate(ctx, p, true);
-    if (rc) return rc;
+    if (const int rc = validate(ctx, p, true)) return rc;
     if (!values || !codes) return fail(ctx, IPT_E_INVALID, "values/codes are NULL");
     if (p->n_shards > 1) return fail(ctx, IPT_E_UNSUPPORTED, "ipt_preview_values renders whole frames");
     hipSetDevice(ctx->device);
-    rc = render_chunks(ctx, p, nullptr, ctx->stream, values, codes, true, kinds, hits);
-    const int rw = drain(ctx);  // the host copies run on the slot streams
-    if (rc) return rc;
-    if (rw) return rw;
-    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return IPT_OK;
+    LaunchRequest rq;
+    rq.host_values = values;
+    rq.host_codes = codes;
+    rq.host_kinds = kinds;
+    rq.host_hits = hits;
+    rq.preview = true;
+    return render_to_host(ctx, p, rq);
 }
 
 int ipt_guides_device(ipt_ctx* ctx, const ipt_params* p, ipt_guide* dev_guides, void* hip_stream) {
-    int rc = validate(ctx, p, true);
-    if (rc) return rc;
+    if (const int rc = validate(ctx, p, true)) return rc;
     if (!dev_guides) return fail(ctx, IPT_E_INVALID, "ipt_guides_device: dev_guides is NULL");
     if (p->spp != 1) return fail(ctx, IPT_E_INVALID, "ipt_guides_device: spp must be 1 (one sample per pixel)");
     if (p->n_shards > 1) return fail(ctx, IPT_E_UNSUPPORTED, "ipt_guides_device writes whole frames");
     if (p->flags & ~(uint32_t)(IPT_FLAG_GUI_PLANE | IPT_FLAG_PREVIEW))
         return fail(ctx, IPT_E_UNSUPPORTED, "ipt_guides_device takes IPT_FLAG_GUI_PLANE and IPT_FLAG_PREVIEW alone");
     hipSetDevice(ctx->device);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     // (tile_rows without shards: the call owns the whole frame)
-    return render_chunks(ctx, p, nullptr, st, nullptr, nullptr, true, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         dev_guides);
+    LaunchRequest rq;
+    rq.st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    rq.preview = true;
+    rq.guides = dev_guides;
+    return render_chunks(ctx, p, rq);
 }
 
 int ipt_guides(ipt_ctx* ctx, const ipt_params* p, ipt_guide* guides) {
@@ -4821,8 +4809,11 @@ int ipt_replay_samples(ipt_ctx* ctx, const ipt_params* p, const float* values, c
     HIPCHECK(ctx, hipMalloc(&dc.p, (size_t)n));
     HIPCHECK(ctx, hipMemcpy(dv.p, values, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     HIPCHECK(ctx, hipMemcpy(dc.p, codes, (size_t)n, hipMemcpyHostToDevice));
-    const ReplaySrc src{dv.p, dc.p};
-    const int rc = render_chunks(ctx, p, img, st, nullptr, nullptr, false, nullptr, nullptr, &src);
+    LaunchRequest rq;
+    rq.img = img;
+    rq.st = st;
+    rq.replay = ReplaySrc{dv.p, dc.p};
+    const int rc = render_chunks(ctx, p, rq);
     // (nothing queued may still read the source when it is freed)
     const int rw = drain(ctx);
     const hipError_t e = hipStreamSynchronize(st);
@@ -4908,9 +4899,11 @@ int ipt_compact_plan(ipt_ctx* ctx, const ipt_params* p, const uint8_t* dev_mask,
     if (rc) return rc;
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the mask is the caller's, written on any stream before the call)
     CompactProbe probe{host_src, cap};
-    const AdaptArgs adapt{dev_mask, nullptr};
-    rc = render_chunks(ctx, p, nullptr, ctx->stream, nullptr, nullptr, false, nullptr, nullptr, nullptr,
-                       dev_mask ? &adapt : nullptr, &probe);
+    LaunchRequest rq;
+    rq.st = ctx->stream;
+    rq.mask = dev_mask;
+    rq.probe = &probe;
+    rc = render_chunks(ctx, p, rq);
     const int rw = drain(ctx);
     *n_active = probe.n_active;
     *start = probe.start;
@@ -4984,7 +4977,8 @@ static int ddf_call(ipt_ctx* ctx, int value_mode, int kind, const float* params,
         if (rc) return rc;
     }
     if (!ctx->has_scene) return fail(ctx, IPT_E_INVALID, "ipt_ddf: no scene uploaded");
-    if (kind == 1 && (params[3] < 0.0f || params[3] >= (float)ctx->n_lights || params[3] != (float)(int)params[3]))
+    const KParams& scene = ctx->scene.kp;
+    if (kind == 1 && (params[3] < 0.0f || params[3] >= (float)scene.n_lights || params[3] != (float)(int)params[3]))
         return fail(ctx, IPT_E_INVALID, "ipt_ddf: light index out of range");
     hipSetDevice(ctx->device);
     const size_t in_w = 3, out_w = value_mode ? 1 : 3;
@@ -4998,7 +4992,7 @@ static int ddf_call(ipt_ctx* ctx, int value_mode, int kind, const float* params,
     HIPCHECK(ctx, hipMemcpy(din.p, in, n * in_w * sizeof(float), hipMemcpyHostToDevice));
     if (n > 0)
         hipLaunchKernelGGL(ddf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, value_mode, kind,
-                           dp.p, ctx->d_lights, ctx->d_weights, ctx->d_cdf, ctx->n_lights, din.p, (long long)n, dout.p,
+                           dp.p, scene.lights, scene.weights, scene.cdf, scene.n_lights, din.p, (long long)n, dout.p,
                            ctx->d_cos_a, ctx->d_cos_b);
     HIPCHECK(ctx, hipGetLastError());
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));

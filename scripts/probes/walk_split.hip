@@ -114,22 +114,7 @@ __global__ __launch_bounds__(256, WPS) void walk_split_kernel(KParams kp, const 
 template <int WPS, bool COUNT>
 static int run_walk(ipt_ctx* ctx, unsigned long long n, int wgs_per_cu, int budget, float* ms,
                     unsigned long long* out_h) {
-    KParams kp{};
-    kp.box_inrange = ctx->box_inrange;
-    kp.bvh_tmargin = ctx->bvh_tmargin;
-    kp.n_grid = ctx->n_grid;
-    for (int a = 0; a < 3; ++a) {
-        kp.grid_g0[a] = ctx->grid.g0[a];
-        kp.grid_h[a] = ctx->grid.h[a];
-        kp.grid_inv_h[a] = ctx->grid.inv_h[a];
-        kp.grid_n[a] = ctx->grid.n[a];
-        kp.grid_g1[a] = ctx->grid.g0[a] + (float)ctx->grid.n[a] * ctx->grid.h[a];
-    }
-    kp.grid_m = ctx->grid.m;
-    kp.grid_start = ctx->d_grid_start;
-    kp.grid_items = ctx->d_grid_items;
-    kp.grid_c4 = ctx->d_grid_c4;
-    kp.grid_idx = ctx->d_grid_c4 ? reinterpret_cast<const int*>(ctx->d_grid_c4 + ctx->grid_n_items) : nullptr;
+    const KParams kp = ctx->scene.kp;  // the uploaded scene's fields (box_inrange, the grid)
     if (kp.n_grid <= 0) return -3;
     unsigned long long *next = nullptr, *out = nullptr;
     if (hipMalloc(&next, 8) != hipSuccess || hipMalloc(&out, 32) != hipSuccess) return -1;

@@ -533,6 +533,54 @@ def test_failed_upload_leaves_no_scene(gpu_ctx, oracle, monkeypatch, fail_at):
     assert np.array_equal(_bits(gv), _bits(ov))
 
 
+def test_scene_sequence_leaves_nothing_behind(oracle):
+    """Every upload builds the context's scene record afresh: what a scene
+    does not use (sphere grid, sphere BVH and its margin, light lattice, light
+    BVH, cdf bucket starts, the near-uniform pick's exponent, the skip-ahead
+    plane) is zero, not the previous scene's. One context takes a sequence in
+    which each scene follows one that populated what it leaves unset, then the
+    same sequence backwards; after every upload values and codes are the
+    oracle's, bit for bit.
+    (make_scene_box_lights(5), the smallest lattice of test_light_grid_bit_exact,
+    has 25 lights -- no power of two, so its pick is not the near-uniform one;
+    make_scene_box_lights(8), the next of that list, is: it sets cdf_p2 and
+    cdf_p2e for make_scene_random_lights to leave unset.)"""
+    base = scenes.make_scene_box()
+    round_lights = dict(base)
+    round_lights["lights"] = list(base["lights"]) + [
+        scenes.sphere_light((0.3, 0.2, 0.4), 0.15, 0.7),
+        scenes.point_light((-0.4, 0.3, -0.2), 0.05, 0.5),
+        scenes.outer_light(9.0, 0.05),
+        scenes.sphere_light((-0.5, -0.6, 0.5), 0.2, 1.3),
+    ]
+    sequence = [
+        ("spheres400 (uniform grid)", scenes.make_scene_spheres(400, seed=1)),
+        ("spheres50 (sphere BVH)", scenes.make_scene_spheres(50, seed=1)),
+        ("box (one axis-aligned light, skip-ahead)", base),
+        ("box_lights5 (lattice)", scenes.make_scene_box_lights(5)),
+        ("box_lights8 (lattice, near-uniform pick)", scenes.make_scene_box_lights(8)),
+        ("random17 (light BVH, cdf bucket starts)", scenes.make_scene_random_lights(17, seed=7)),
+        ("round lights", round_lights),
+    ]
+    p = capi.make_params(16, 12, 2, n_rays=4, depth_max=4)
+    want = [ob.render_values(desc, p, 0) for _, desc in sequence]
+    order = list(range(len(sequence)))
+    ctx = capi.Context(0)
+    try:
+        prev = "a fresh context"
+        for i in order + order[::-1]:
+            name, desc = sequence[i]
+            ctx.upload_scene(desc)
+            gv, gc = ctx.render_values(p)
+            ov, oc = want[i]
+            assert np.array_equal(gc, oc), f"{name} after {prev}: codes differ"
+            assert np.array_equal(_bits(gv), _bits(ov)), (
+                f"{name} after {prev}: {int((_bits(gv) != _bits(ov)).sum())} of {gv.size} samples differ")
+            prev = name
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("light", [
     # x along y, y along x, facing down: sample_scenes[0]'s pattern (kLightsOneA10)
     {"position": [-0.3, 0.2, 0.7], "x_axis": [0.0, 0.3, 0.0], "y_axis": [0.25, 0.0, 0.0], "power": 2.0, "type": 0},
