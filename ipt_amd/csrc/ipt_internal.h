@@ -15,20 +15,35 @@ hipStream_t ctx_stream(ipt_ctx* ctx);
 int ctx_device(ipt_ctx* ctx);
 int ctx_cus(ipt_ctx* ctx);
 
-// The display pipeline's scratch (ipt_post.hip), owned by the context: grows to
-// the largest image seen, freed by ipt_destroy. `done` is recorded on the
-// caller's stream after each ipt_display_device; the context's drain waits
-// for it (ipt_render_wait, ipt_upload_scene, ipt_destroy).
+// One buffer of the post-processing scratch: `cap` elements of `elem` bytes.
+// What the elements are is ipt_post.hip's business (its record types and the
+// casts stay there); a failed growth leaves {nullptr, 0}.
+struct ScratchBuf {
+    void* p = nullptr;
+    size_t cap = 0, elem = 0;
+};
+
+// The post-processing scratch (ipt_post.hip), owned by the context and shared
+// by every queued entry point of that file (display, display statistics,
+// smooth / PGM, adapt, denoise): each buffer grows to the largest frame seen
+// and is freed by ipt_destroy. `done` is recorded on the caller's stream after
+// each queued call; the next call on another stream waits for it on the
+// device, and the context's drain waits for it on the host (ipt_render_wait,
+// ipt_upload_scene, ipt_destroy).
 struct PostScratch {
-    void* bright = nullptr;        // bright-pixel records, one per pixel at most
-    unsigned int* blocks = nullptr;  // per-block bright counts, then their exclusive scan
-    void* scalars = nullptr;       // bright count, image max key, tone min / max
-    void* stats = nullptr;         // ipt_display_stats_device: mx, white point, radix prefix, digit counts
-    void* pgm = nullptr;           // ipt_smooth_device / ipt_pgm_device: the maxima, max_value, logf(contrast)
-    float* processed = nullptr;    // glare output (smooth output, in-place copy) when the caller passes none
-    float* tone = nullptr;         // tone-mapped image when the caller passes none
-    void* denoise = nullptr;       // ipt_denoise_device: two planes of 32 B records (denoise_cap pixels each)
-    size_t bright_cap = 0, blocks_cap = 0, processed_cap = 0, tone_cap = 0, denoise_cap = 0;
+    // (in the order the buffers grow; the first three hold one record)
+    enum Buf {
+        kScalars,    // bright count, image max key, tone min / max
+        kStats,      // ipt_display_stats_device: mx, white point, radix prefix, digit counts
+        kPgm,        // ipt_smooth_device / ipt_pgm_device: the maxima, max_value, logf(contrast)
+        kBright,     // bright-pixel records, one per pixel at most
+        kBlocks,     // per-block bright counts, then their exclusive scan
+        kProcessed,  // glare output (smooth output, in-place copy) when the caller passes none
+        kTone,       // tone-mapped image when the caller passes none
+        kDenoise,    // ipt_denoise_device: per pixel, one record of each of the two planes
+        kBufs
+    };
+    ScratchBuf buf[kBufs];
     // ipt_denoise_pass_ms (IPT_DENOISE_PROFILE=1): events around the last call's passes
     hipEvent_t denoise_ev[8] = {};
     int denoise_timed = 0;  // iterations of the last profiled call, 0: none

@@ -3274,7 +3274,7 @@ struct ipt_ctx {
     bool box_generic = false;   // IPT_BOX_GENERIC=1: the box instances' generic range form (tests)
     bool lattice_lds = true;    // IPT_LATTICE_LDS=0: the lattice instances with global records (tests)
     size_t max_lds = 160 * 1024;  // the device's LDS per workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock)
-    ipt_internal::PostScratch post;  // ipt_display_device's scratch and completion event (ipt_post.hip)
+    ipt_internal::PostScratch post;  // the queued post-processing calls' scratch and completion event (ipt_post.hip)
 };
 
 namespace {

@@ -921,7 +921,8 @@ __global__ __launch_bounds__(kPostBlock) void denoise_tiled_kernel(const DnArgs 
 // powf_'s stated domain for y (ipt_math.h)
 bool powf_y_ok(float y) { return isfinite_(y) && y > 0.0f && y != std::trunc(y); }
 
-using ipt_internal::DevBuf;
+using ipt_internal::PostScratch;
+using ipt_internal::ScratchBuf;
 
 #define POSTCHECK(ctx, expr)                                                                            \
     do {                                                                                                 \
@@ -930,54 +931,52 @@ using ipt_internal::DevBuf;
             return ipt_internal::ctx_fail(ctx, IPT_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-// (Re)allocates one of the context's display scratch buffers: the old one is
-// dropped first, and a failure leaves a null pointer with capacity 0.
-template <class T>
-int post_grow(ipt_ctx* ctx, T*& ptr, size_t& cap, size_t count, size_t elem_bytes) {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, count * elem_bytes);
-    if (e != hipSuccess)
-        return ipt_internal::ctx_fail(ctx, e == hipErrorOutOfMemory ? IPT_E_OOM : IPT_E_DEVICE,
-                                      std::string("display scratch: ") + hipGetErrorString(e));
-    ptr = static_cast<T*>(q);
-    cap = count;
+// grids: one thread per element, four elements per thread
+unsigned int blocks_for(long long n) { return (unsigned int)((n + kPostBlock - 1) / kPostBlock); }
+unsigned int quads_for(long long n) { return (unsigned int)((n + 4ll * kPostBlock - 1) / (4ll * kPostBlock)); }
+
+// the frame rules the two display entry points share, under `name`'s prefix
+// (the caller has tested ctx and the pointers)
+int frame_check(ipt_ctx* ctx, const char* name, int W, int H, float glare_cutoff, uint32_t flags) {
+    const std::string pre = std::string(name) + ": ";
+    if (W <= 0 || H <= 0 || !(glare_cutoff >= 0.0f))
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, pre + "bad arguments");
+    if (glare_cutoff > 0.0f && (W > 4096 || H > 4096))  // ipt_glare's limit (the hypot equivalence)
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, pre + "glare on images up to 4096 x 4096");
+    if ((long long)W * H > (1ll << 31) || flags != 0 || !isfinite_(glare_cutoff))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, pre + "at most 2^31 pixels, finite cutoff, flags 0");
     return IPT_OK;
 }
 
 // the argument rules of ipt_display / ipt_display_device (ipt_capi.h)
 int display_check(ipt_ctx* ctx, const ipt_display_params* p, const float* pixels, const uint8_t* gray8) {
     if (!ctx) return IPT_E_INVALID;
-    if (!p || !pixels || !gray8 || p->width <= 0 || p->height <= 0 || !(p->glare_cutoff >= 0.0f))
-        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_display: bad arguments");
-    if (p->glare_cutoff > 0.0f && (p->width > 4096 || p->height > 4096))  // ipt_glare's limit (the hypot equivalence)
-        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_display: glare on images up to 4096 x 4096");
-    if ((long long)p->width * p->height > (1ll << 31) || p->flags != 0 || !isfinite_(p->glare_cutoff))
-        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_display: at most 2^31 pixels, finite cutoff, flags 0");
-    return IPT_OK;
+    if (!p || !pixels || !gray8) return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_display: bad arguments");
+    return frame_check(ctx, "ipt_display", p->width, p->height, p->glare_cutoff, p->flags);
 }
 
 // the argument rules of ipt_display_stats / ipt_display_stats_device:
 // display_check's (no output is mandatory here) and the histogram's
 int stats_check(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* pixels, const uint32_t* hist) {
     if (!ctx) return IPT_E_INVALID;
-    if (!p || !pixels || p->width <= 0 || p->height <= 0 || !(p->glare_cutoff >= 0.0f) || p->hist_buckets < 0 ||
-        p->hist_buckets > kHistMaxBuckets || (p->hist_buckets > 0 && !hist))
+    if (!p || !pixels || p->hist_buckets < 0 || p->hist_buckets > kHistMaxBuckets || (p->hist_buckets > 0 && !hist))
         return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_display_stats: bad arguments");
-    if (p->glare_cutoff > 0.0f && (p->width > 4096 || p->height > 4096))
-        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_display_stats: glare on images up to 4096 x 4096");
-    if ((long long)p->width * p->height > (1ll << 31) || p->flags != 0 || !isfinite_(p->glare_cutoff))
-        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
-                                      "ipt_display_stats: at most 2^31 pixels, finite cutoff, flags 0");
-    return IPT_OK;
+    return frame_check(ctx, "ipt_display_stats", p->width, p->height, p->glare_cutoff, p->flags);
 }
 
 // [a, a + na) and [b, b + nb) share a byte (a NULL range shares none)
 bool overlap_(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return a && b && x < y + nb && y < x + na;
+}
+
+// some pair of the n buffers overlaps, the pairs among the inputs (those before
+// first_output) apart
+bool any_overlap(const void* const* bufs, const size_t* lens, int n, int first_output) {
+    for (int a = 0; a < n; ++a)
+        for (int b = std::max(a + 1, first_output); b < n; ++b)
+            if (overlap_(bufs[a], lens[a], bufs[b], lens[b])) return true;
+    return false;
 }
 
 constexpr int kSmoothMaxSide = 64;  // 64^2 adds per pixel bound a queued kernel
@@ -1010,10 +1009,8 @@ int pgm_check(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const 
     const size_t n = (size_t)p->width * (size_t)p->height;
     const void* buf[5] = {pixels, pixel_max, smoothed, gray8, stats};
     const size_t len[5] = {n * sizeof(float), n * sizeof(float), n * sizeof(float), n, 4 * sizeof(float)};
-    for (int a = 0; a < 5; ++a)
-        for (int b = std::max(a + 1, 2); b < 5; ++b)  // every pair but the two inputs
-            if (overlap_(buf[a], len[a], buf[b], len[b]))
-                return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_pgm: the buffers overlap");
+    if (any_overlap(buf, len, 5, 2))  // every pair but the two inputs
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_pgm: the buffers overlap");
     if (side_unsupported_(p->smooth_side) || side_unsupported_(p->max_side) || p->flags != 0 ||
         (long long)p->width * p->height > (1ll << 31))
         return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
@@ -1038,10 +1035,8 @@ int denoise_check(ipt_ctx* ctx, const ipt_denoise_params* p, const float* pixels
     const size_t n = (size_t)p->width * (size_t)p->height;
     const void* buf[6] = {pixels, counters, m2, guides, out, var_out};
     const size_t len[6] = {n * 4, n * 4, n * 4, n * sizeof(ipt_guide), n * 4, n * 4};
-    for (int a = 0; a < 6; ++a)
-        for (int b = std::max(a + 1, 4); b < 6; ++b)  // every pair with an output in it
-            if (overlap_(buf[a], len[a], buf[b], len[b]))
-                return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_denoise: an output overlaps another buffer");
+    if (any_overlap(buf, len, 6, 4))  // every pair with an output in it
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_denoise: an output overlaps another buffer");
     return IPT_OK;
 }
 
@@ -1059,28 +1054,64 @@ struct DnRecord {
     float4 a, b;
 };
 
-// The PGM path's share of the context's scratch: the scalars and, where a call
-// needs a plane of its own, `processed`. Only the first call or a larger image
-// allocates or waits; then the call is ordered behind the previous one.
-int pgm_scratch(ipt_ctx* ctx, size_t need_processed, hipStream_t st) {
-    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
-    if (!S.done || !S.pgm || need_processed > S.processed_cap) {
-        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
-        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-        size_t one = 0;
-        if (!S.pgm)
-            if (const int rc = post_grow(ctx, S.pgm, one, 1, sizeof(PgmScalars))) return rc;
-        if (need_processed > S.processed_cap)
-            if (const int rc = post_grow(ctx, S.processed, S.processed_cap, need_processed, sizeof(float))) return rc;
-    }
-    // the scratch is shared: a call on another stream runs after the previous one
-    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
-    POSTCHECK(ctx, hipMemsetAsync(S.pgm, 0, sizeof(PgmScalars), st));
+// ---- the queued-call protocol ------------------------------------------------
+// Every queued entry point is: check the arguments (before any HIP call), say
+// what it needs of the context's scratch, post_begin, its memsets and launches
+// on the stream post_begin chose, post_queued.
+
+// what a call needs of each scratch buffer, in elements (0: not used)
+struct PostNeeds {
+    size_t n[PostScratch::kBufs] = {};
+};
+
+// the buffers' element sizes; kDenoise holds both planes' records of a pixel
+constexpr size_t kPostElem[PostScratch::kBufs] = {sizeof(DisplayScalars), sizeof(StatsScalars), sizeof(PgmScalars),
+                                                  sizeof(Bright),         sizeof(unsigned int), sizeof(float),
+                                                  sizeof(float),          2 * sizeof(DnRecord)};
+
+template <class T>
+T* scratch(PostScratch& S, PostScratch::Buf b) {
+    return static_cast<T*>(S.buf[b].p);
+}
+
+// (Re)allocates a scratch buffer: the old one is dropped first, and a failure
+// leaves a null pointer with capacity 0, so that the next call tries again.
+int post_grow(ipt_ctx* ctx, ScratchBuf& b, size_t count, size_t elem_bytes) {
+    if (b.p) (void)hipFree(b.p);
+    b = ScratchBuf{};
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, count * elem_bytes);
+    if (e != hipSuccess)
+        return ipt_internal::ctx_fail(ctx, e == hipErrorOutOfMemory ? IPT_E_OOM : IPT_E_DEVICE,
+                                      std::string("display scratch: ") + hipGetErrorString(e));
+    b = ScratchBuf{q, count, elem_bytes};
     return IPT_OK;
 }
 
-int pgm_queued(ipt_ctx* ctx, hipStream_t st) {
-    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
+// Picks the stream (*st: the caller's, or the context's), makes the scratch
+// hold what the call needs and orders the call behind the previous one. Only
+// the first call or a larger frame allocates or waits on the host.
+int post_begin(ipt_ctx* ctx, void* hip_stream, const PostNeeds& needs, hipStream_t* st) {
+    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
+    *st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
+    PostScratch& S = ipt_internal::ctx_post(ctx);
+    bool grow = !S.done;
+    for (int b = 0; b < PostScratch::kBufs; ++b) grow |= needs.n[b] > S.buf[b].cap;
+    if (grow) {
+        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
+        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+        for (int b = 0; b < PostScratch::kBufs; ++b)  // (in the enum's order)
+            if (needs.n[b] > S.buf[b].cap)
+                if (const int rc = post_grow(ctx, S.buf[b], needs.n[b], kPostElem[b])) return rc;
+    }
+    // the scratch is shared: a call on another stream runs after the previous one
+    if (S.used && S.last_stream != *st) POSTCHECK(ctx, hipStreamWaitEvent(*st, S.done, 0));
+    return IPT_OK;
+}
+
+// after the call's last launch: the event the next call and the context's drain wait for
+int post_queued(ipt_ctx* ctx, hipStream_t st) {
+    PostScratch& S = ipt_internal::ctx_post(ctx);
     POSTCHECK(ctx, hipGetLastError());
     POSTCHECK(ctx, hipEventRecord(S.done, st));
     S.used = true;
@@ -1088,20 +1119,119 @@ int pgm_queued(ipt_ctx* ctx, hipStream_t st) {
     return IPT_OK;
 }
 
+// smooth(side) moves some pixel (side 0, or larger than the image: none qualifies)
+bool smooth_filters(int W, int H, int side) { return side >= 2 && side <= W && side <= H; }
+
 // smooth(side) of `in` into `out` (the whole plane; NULL: the maximum alone),
 // max_value's bits into *max_bits (zeroed by the caller). in != out.
-// side 0 or larger than the image: no pixel qualifies, the plane is copied and
-// the maximum stays 0.
+// Where no pixel qualifies the plane is copied and the maximum stays 0.
 hipError_t launch_smooth(hipStream_t st, const float* in, float* out, int W, int H, int side,
                          unsigned int* max_bits) {
-    if (side < 2 || side > W || side > H)
+    if (!smooth_filters(W, H, side))
         return out ? hipMemcpyAsync(out, in, (size_t)W * H * sizeof(float), hipMemcpyDeviceToDevice, st) : hipSuccess;
-    dim3 grid((W + kPostBlock - 1) / kPostBlock, H);
+    dim3 grid(blocks_for(W), H);
     if (out)
         hipLaunchKernelGGL(smooth_kernel<true>, grid, dim3(kPostBlock), 0, st, in, out, W, H, side, max_bits);
     else
         hipLaunchKernelGGL(smooth_kernel<false>, grid, dim3(kPostBlock), 0, st, in, out, W, H, side, max_bits);
     return hipSuccess;
+}
+
+// what a glare stage on n pixels needs of the scratch
+void glare_needs(PostNeeds& need, long long n, bool own_plane) {
+    need.n[PostScratch::kBright] = (size_t)n;
+    need.n[PostScratch::kBlocks] = (size_t)((n + kCompactSpan - 1) / kCompactSpan);
+    need.n[PostScratch::kProcessed] = own_plane ? (size_t)n : 0;
+}
+
+// The glare stage of the two display entry points (`run`: bright count, scan,
+// scatter, glare, into dev_processed or the context's plane), or the copy a
+// caller's dev_processed gets without one. *plane: what the later stages read.
+hipError_t queue_glare(hipStream_t st, PostScratch& S, DisplayScalars* sc, const float* dev_pixels,
+                       float* dev_processed, int W, int H, float cutoff, bool run, const float** plane) {
+    const long long n = (long long)W * H;
+    *plane = dev_pixels;
+    if (!run && !dev_processed) return hipSuccess;
+    if (!run) return hipMemcpyAsync(dev_processed, dev_pixels, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st);
+    Bright* bright = scratch<Bright>(S, PostScratch::kBright);
+    unsigned int* blocks = scratch<unsigned int>(S, PostScratch::kBlocks);
+    float* out = dev_processed ? dev_processed : scratch<float>(S, PostScratch::kProcessed);
+    const unsigned int nblk = (unsigned int)((n + kCompactSpan - 1) / kCompactSpan);
+    hipLaunchKernelGGL(bright_count_kernel, dim3(nblk), dim3(kPostBlock), 0, st, dev_pixels, n, cutoff, blocks);
+    hipLaunchKernelGGL(bright_scan_kernel, dim3(1), dim3(kPostBlock), 0, st, blocks, (int)nblk, sc);
+    hipLaunchKernelGGL(bright_scatter_kernel, dim3(nblk), dim3(kPostBlock), 0, st, dev_pixels, W, n, cutoff,
+                       (const unsigned int*)blocks, bright);
+    hipLaunchKernelGGL(glare_kernel, dim3(blocks_for(W), H), dim3(kPostBlock), 0, st, dev_pixels, out, W, H,
+                       (const Bright*)bright, 0, cutoff, (const unsigned int*)&sc->nb);
+    *plane = out;
+    return hipSuccess;
+}
+
+// tone_map's exponent (gui.cpp:11-16)
+float tone_gamma() {
+    const float inv_gamma = 2.2f;
+    return (float)(double)(1.0f / inv_gamma);
+}
+
+// ---- host round trips ----------------------------------------------------------
+// A host wrapper's device temporaries on the context's stream: in() allocates
+// and uploads, out() allocates and remembers the download (at_least: elements
+// to allocate where count may be 0), finish() queues the downloads in out()'s
+// order and waits. A NULL host pointer gives NULL and no work. The first
+// failure sticks (rc, with the context's message) and makes the later calls
+// no-ops: a wrapper tests rc before it launches. The temporaries go with the
+// stage, on every return path.
+struct HostStage {
+    struct Out {
+        void* host;
+        const void* dev;
+        size_t bytes;
+    };
+    ipt_ctx* ctx;
+    hipStream_t st;
+    int rc = IPT_OK;
+    std::vector<ipt_internal::DevBuf<void>> bufs;
+    std::vector<Out> outs;
+
+    explicit HostStage(ipt_ctx* c) : ctx(c), st(ipt_internal::ctx_stream(c)) {
+        (void)hipSetDevice(ipt_internal::ctx_device(c));
+    }
+    void check(hipError_t e, const char* what) {
+        if (e != hipSuccess && rc == IPT_OK)
+            rc = ipt_internal::ctx_fail(ctx, IPT_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    void* scratch(size_t bytes) {
+        bufs.emplace_back();
+        if (rc == IPT_OK) check(hipMalloc(&bufs.back().p, bytes), "hipMalloc");
+        return bufs.back().p;
+    }
+    template <class T>
+    T* in(const T* host, size_t count, size_t at_least = 0) {
+        T* p = host ? static_cast<T*>(scratch(std::max(count, at_least) * sizeof(T))) : nullptr;
+        if (p) check(hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, st), "hipMemcpyAsync (upload)");
+        return p;
+    }
+    template <class T>
+    T* out(T* host, size_t count, size_t at_least = 0) {
+        T* p = host ? static_cast<T*>(scratch(std::max(count, at_least) * sizeof(T))) : nullptr;
+        if (p) outs.push_back({host, p, count * sizeof(T)});
+        return p;
+    }
+    int finish() {
+        for (const Out& o : outs)
+            if (rc == IPT_OK) check(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, st), "hipMemcpyAsync (download)");
+        if (rc == IPT_OK) check(hipStreamSynchronize(st), "hipStreamSynchronize");
+        return rc;
+    }
+};
+
+// fn(lo, hi) over [0, n) on up to 16 threads, a contiguous range each
+template <class Fn>
+void parallel_for(int64_t n, Fn fn) {
+    const int nt = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; ++t) th.emplace_back([=]() { fn(n * t / nt, n * (t + 1) / nt); });
+    for (auto& t : th) t.join();
 }
 
 }  // namespace
@@ -1115,27 +1245,22 @@ int ipt_smooth(ipt_ctx* ctx, float* pixels, int width, int height, int side, int
     if (side == 1)  // GridRenderPlane.cpp:14: `y >= side-1` with size_t never fails, the loop runs past row 0
         return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
                                       "ipt_smooth: side 1 is undefined behaviour in the reference");
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = ipt_internal::ctx_stream(ctx);
+    HostStage hs(ctx);
+    hipStream_t st = hs.st;
     const size_t n = (size_t)width * height;
-    DevBuf<float> din, dout;
-    DevBuf<unsigned int> dmax;
-    POSTCHECK(ctx, hipMalloc(&din.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMalloc(&dmax.p, sizeof(unsigned int)));
-    if (in_place) POSTCHECK(ctx, hipMalloc(&dout.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMemcpyAsync(din.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (in_place) POSTCHECK(ctx, hipMemcpyAsync(dout.p, din.p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    POSTCHECK(ctx, hipMemsetAsync(dmax.p, 0, sizeof(unsigned int), st));
-    if (side >= 2 && side <= width && side <= height) {
-        dim3 grid((width + kPostBlock - 1) / kPostBlock, height);
-        hipLaunchKernelGGL(smooth_kernel<false>, grid, dim3(kPostBlock), 0, st, din.p, dout.p, width, height, side,
-                           dmax.p);
+    unsigned int mb = 0;
+    const float* din = hs.in(pixels, n);
+    unsigned int* dmax = hs.out(&mb, 1);
+    float* dout = hs.out(in_place ? pixels : nullptr, n);
+    if (hs.rc) return hs.rc;
+    if (in_place) POSTCHECK(ctx, hipMemcpyAsync(dout, din, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    POSTCHECK(ctx, hipMemsetAsync(dmax, 0, sizeof(unsigned int), st));
+    if (smooth_filters(width, height, side)) {  // (its own launch: side up to 4096 here, 64 in ipt_smooth_device)
+        hipLaunchKernelGGL(smooth_kernel<false>, dim3(blocks_for(width), height), dim3(kPostBlock), 0, st, din, dout,
+                           width, height, side, dmax);
         POSTCHECK(ctx, hipGetLastError());
     }
-    unsigned int mb = 0;
-    POSTCHECK(ctx, hipMemcpyAsync(&mb, dmax.p, sizeof mb, hipMemcpyDeviceToHost, st));
-    if (in_place) POSTCHECK(ctx, hipMemcpyAsync(pixels, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipStreamSynchronize(st));
+    if (const int rc = hs.finish()) return rc;
     *max_value = __builtin_bit_cast(float, mb);
     return IPT_OK;
 }
@@ -1146,8 +1271,6 @@ int ipt_glare(ipt_ctx* ctx, const float* in, float* out, int width, int height, 
         return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_glare: bad arguments");
     if (width > 4096 || height > 4096)  // the hypot equivalence is proven for |dx|, |dy| < 4096
         return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_glare: images up to 4096 x 4096");
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = ipt_internal::ctx_stream(ctx);
     // bright pixels in raster order (gui.cpp:40-47); `val <= cutoff` false for NaN too
     std::vector<Bright> b;
     for (int y = 0; y < height; ++y)
@@ -1158,21 +1281,15 @@ int ipt_glare(ipt_ctx* ctx, const float* in, float* out, int width, int height, 
             b.push_back(Bright{x, y, cutoff * coef, 0});
         }
     const size_t n = (size_t)width * height;
-    DevBuf<float> din, dout;
-    DevBuf<Bright> db;
-    POSTCHECK(ctx, hipMalloc(&din.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMalloc(&dout.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMalloc(&db.p, std::max<size_t>(b.size(), 1) * sizeof(Bright)));
-    POSTCHECK(ctx, hipMemcpyAsync(din.p, in, n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (!b.empty())
-        POSTCHECK(ctx, hipMemcpyAsync(db.p, b.data(), b.size() * sizeof(Bright), hipMemcpyHostToDevice, st));
-    dim3 grid((width + kPostBlock - 1) / kPostBlock, height);
-    hipLaunchKernelGGL(glare_kernel, grid, dim3(kPostBlock), 0, st, din.p, dout.p, width, height, db.p, (int)b.size(),
-                       cutoff, (const unsigned int*)nullptr);
+    HostStage hs(ctx);
+    const float* din = hs.in(in, n);
+    float* dout = hs.out(out, n);
+    const Bright* db = b.empty() ? static_cast<const Bright*>(hs.scratch(sizeof(Bright))) : hs.in(b.data(), b.size());
+    if (hs.rc) return hs.rc;
+    hipLaunchKernelGGL(glare_kernel, dim3(blocks_for(width), height), dim3(kPostBlock), 0, hs.st, din, dout, width,
+                       height, db, (int)b.size(), cutoff, (const unsigned int*)nullptr);
     POSTCHECK(ctx, hipGetLastError());
-    POSTCHECK(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipStreamSynchronize(st));
-    return IPT_OK;
+    return hs.finish();
 }
 
 int ipt_display_device(ipt_ctx* ctx, const ipt_display_params* p, const float* dev_pixels, float* dev_processed,
@@ -1180,84 +1297,39 @@ int ipt_display_device(ipt_ctx* ctx, const ipt_display_params* p, const float* d
     if (const int rc = display_check(ctx, p, dev_pixels, dev_gray8)) return rc;
     const bool glare = p->glare_cutoff > 0.0f;
     const long long n = (long long)p->width * p->height;
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
-    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
-    const size_t nblk = (size_t)((n + kCompactSpan - 1) / kCompactSpan);
-    const size_t need_bright = glare ? (size_t)n : 0, need_blocks = glare ? nblk : 0;
-    const size_t need_processed = glare && !dev_processed ? (size_t)n : 0, need_tone = dev_tone ? 0 : (size_t)n;
-    if (!S.done || !S.scalars || need_bright > S.bright_cap || need_blocks > S.blocks_cap ||
-        need_processed > S.processed_cap || need_tone > S.tone_cap) {
-        // (first call or a larger image: the only path that allocates or waits)
-        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
-        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-        size_t one = 0;
-        if (!S.scalars)
-            if (const int rc = post_grow(ctx, S.scalars, one, 1, sizeof(DisplayScalars))) return rc;
-        if (need_bright > S.bright_cap)
-            if (const int rc = post_grow(ctx, S.bright, S.bright_cap, need_bright, sizeof(Bright))) return rc;
-        if (need_blocks > S.blocks_cap)
-            if (const int rc = post_grow(ctx, S.blocks, S.blocks_cap, need_blocks, sizeof(unsigned int))) return rc;
-        if (need_processed > S.processed_cap)
-            if (const int rc = post_grow(ctx, S.processed, S.processed_cap, need_processed, sizeof(float))) return rc;
-        if (need_tone > S.tone_cap)
-            if (const int rc = post_grow(ctx, S.tone, S.tone_cap, need_tone, sizeof(float))) return rc;
-    }
-    // the scratch is shared: a call on another stream runs after the previous one
-    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
-    DisplayScalars* sc = static_cast<DisplayScalars*>(S.scalars);
+    PostNeeds need;
+    need.n[PostScratch::kScalars] = 1;
+    if (glare) glare_needs(need, n, !dev_processed);
+    need.n[PostScratch::kTone] = dev_tone ? 0 : (size_t)n;
+    hipStream_t st;
+    if (const int rc = post_begin(ctx, hip_stream, need, &st)) return rc;
+    PostScratch& S = ipt_internal::ctx_post(ctx);
+    DisplayScalars* sc = scratch<DisplayScalars>(S, PostScratch::kScalars);
     POSTCHECK(ctx, hipMemsetAsync(sc, 0, sizeof(DisplayScalars), st));
-    const float* processed = dev_pixels;
-    if (glare) {
-        Bright* bright = static_cast<Bright*>(S.bright);
-        float* out = dev_processed ? dev_processed : S.processed;
-        const float cutoff = p->glare_cutoff;
-        hipLaunchKernelGGL(bright_count_kernel, dim3((unsigned)nblk), dim3(kPostBlock), 0, st, dev_pixels, n, cutoff,
-                           S.blocks);
-        hipLaunchKernelGGL(bright_scan_kernel, dim3(1), dim3(kPostBlock), 0, st, S.blocks, (int)nblk, sc);
-        hipLaunchKernelGGL(bright_scatter_kernel, dim3((unsigned)nblk), dim3(kPostBlock), 0, st, dev_pixels, p->width, n,
-                           cutoff, (const unsigned int*)S.blocks, bright);
-        dim3 grid((p->width + kPostBlock - 1) / kPostBlock, p->height);
-        hipLaunchKernelGGL(glare_kernel, grid, dim3(kPostBlock), 0, st, dev_pixels, out, p->width, p->height,
-                           (const Bright*)bright, 0, cutoff, (const unsigned int*)&sc->nb);
-        processed = out;
-    } else if (dev_processed) {
-        POSTCHECK(ctx, hipMemcpyAsync(dev_processed, dev_pixels, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    float* tone = dev_tone ? dev_tone : S.tone;
-    const unsigned int quads = (unsigned int)((n + 4ll * kPostBlock - 1) / (4ll * kPostBlock));
-    const float inv_gamma = 2.2f;
-    const float gamma = (float)(double)(1.0f / inv_gamma);  // tone_map's exponent (gui.cpp:11-16)
+    const float* processed;
+    POSTCHECK(ctx, queue_glare(st, S, sc, dev_pixels, dev_processed, p->width, p->height, p->glare_cutoff, glare,
+                               &processed));
+    float* tone = dev_tone ? dev_tone : scratch<float>(S, PostScratch::kTone);
+    const unsigned int quads = quads_for(n);
     hipLaunchKernelGGL(image_max_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, n, sc);
-    hipLaunchKernelGGL(tone_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, tone, n, gamma, sc);
+    hipLaunchKernelGGL(tone_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, tone, n, tone_gamma(), sc);
     hipLaunchKernelGGL(gray8_kernel, dim3(quads), dim3(kPostBlock), 0, st, (const float*)tone, dev_gray8, n,
                        (const DisplayScalars*)sc);
-    POSTCHECK(ctx, hipGetLastError());
-    POSTCHECK(ctx, hipEventRecord(S.done, st));
-    S.used = true;
-    S.last_stream = st;
-    return IPT_OK;
+    return post_queued(ctx, st);
 }
 
 int ipt_display(ipt_ctx* ctx, const ipt_display_params* p, const float* pixels, float* processed, float* tone,
                 uint8_t* gray8) {
     if (const int rc = display_check(ctx, p, pixels, gray8)) return rc;
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = ipt_internal::ctx_stream(ctx);
     const size_t n = (size_t)p->width * p->height;
-    DevBuf<float> din, dproc, dtone;
-    DevBuf<uint8_t> dgray;
-    POSTCHECK(ctx, hipMalloc(&din.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMalloc(&dgray.p, n));
-    if (processed) POSTCHECK(ctx, hipMalloc(&dproc.p, n * sizeof(float)));
-    if (tone) POSTCHECK(ctx, hipMalloc(&dtone.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMemcpyAsync(din.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (const int rc = ipt_display_device(ctx, p, din.p, dproc.p, dtone.p, dgray.p, st)) return rc;
-    if (processed) POSTCHECK(ctx, hipMemcpyAsync(processed, dproc.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (tone) POSTCHECK(ctx, hipMemcpyAsync(tone, dtone.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipMemcpyAsync(gray8, dgray.p, n, hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipStreamSynchronize(st));
-    return IPT_OK;
+    HostStage hs(ctx);
+    const float* din = hs.in(pixels, n);
+    float* dproc = hs.out(processed, n);
+    float* dtone = hs.out(tone, n);
+    uint8_t* dgray = hs.out(gray8, n);
+    if (hs.rc) return hs.rc;
+    if (const int rc = ipt_display_device(ctx, p, din, dproc, dtone, dgray, hs.st)) return rc;
+    return hs.finish();
 }
 
 int ipt_display_stats_device(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* dev_pixels,
@@ -1272,58 +1344,23 @@ int ipt_display_stats_device(ipt_ctx* ctx, const ipt_display_stats_params* p, co
     const bool select = p->white_rank >= 0 && p->white_rank < n && (want_tone || dev_stats);
     const bool want_max = nb > 0 || dev_stats || (want_tone && !select);
     const bool want_image = want_max || select || want_tone;  // the glare output is read at all
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
-    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
     const bool run_glare = glare && (want_image || dev_processed);
-    const size_t nblk = (size_t)((n + kCompactSpan - 1) / kCompactSpan);
-    const size_t need_bright = run_glare ? (size_t)n : 0, need_blocks = run_glare ? nblk : 0;
-    const size_t need_processed = run_glare && !dev_processed ? (size_t)n : 0;
-    const size_t need_tone = dev_gray8 && !dev_tone ? (size_t)n : 0;
-    if (!S.done || !S.scalars || !S.stats || need_bright > S.bright_cap || need_blocks > S.blocks_cap ||
-        need_processed > S.processed_cap || need_tone > S.tone_cap) {
-        // (first call or a larger image: the only path that allocates or waits)
-        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
-        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-        size_t one = 0;
-        if (!S.scalars)
-            if (const int rc = post_grow(ctx, S.scalars, one, 1, sizeof(DisplayScalars))) return rc;
-        if (!S.stats)
-            if (const int rc = post_grow(ctx, S.stats, one, 1, sizeof(StatsScalars))) return rc;
-        if (need_bright > S.bright_cap)
-            if (const int rc = post_grow(ctx, S.bright, S.bright_cap, need_bright, sizeof(Bright))) return rc;
-        if (need_blocks > S.blocks_cap)
-            if (const int rc = post_grow(ctx, S.blocks, S.blocks_cap, need_blocks, sizeof(unsigned int))) return rc;
-        if (need_processed > S.processed_cap)
-            if (const int rc = post_grow(ctx, S.processed, S.processed_cap, need_processed, sizeof(float))) return rc;
-        if (need_tone > S.tone_cap)
-            if (const int rc = post_grow(ctx, S.tone, S.tone_cap, need_tone, sizeof(float))) return rc;
-    }
-    // the scratch is shared: a call on another stream runs after the previous one
-    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
-    DisplayScalars* sc = static_cast<DisplayScalars*>(S.scalars);
-    StatsScalars* ss = static_cast<StatsScalars*>(S.stats);
+    PostNeeds need;
+    need.n[PostScratch::kScalars] = need.n[PostScratch::kStats] = 1;
+    if (run_glare) glare_needs(need, n, !dev_processed);
+    need.n[PostScratch::kTone] = dev_gray8 && !dev_tone ? (size_t)n : 0;
+    hipStream_t st;
+    if (const int rc = post_begin(ctx, hip_stream, need, &st)) return rc;
+    PostScratch& S = ipt_internal::ctx_post(ctx);
+    DisplayScalars* sc = scratch<DisplayScalars>(S, PostScratch::kScalars);
+    StatsScalars* ss = scratch<StatsScalars>(S, PostScratch::kStats);
     POSTCHECK(ctx, hipMemsetAsync(sc, 0, sizeof(DisplayScalars), st));
     if (select) POSTCHECK(ctx, hipMemsetAsync(ss->digits, 0, sizeof(ss->digits[0]) * kSelPasses, st));
     if (nb > 0) POSTCHECK(ctx, hipMemsetAsync(dev_hist, 0, (size_t)nb * sizeof(uint32_t), st));
-    const float* processed = dev_pixels;
-    if (run_glare) {
-        Bright* bright = static_cast<Bright*>(S.bright);
-        float* out = dev_processed ? dev_processed : S.processed;
-        const float cutoff = p->glare_cutoff;
-        hipLaunchKernelGGL(bright_count_kernel, dim3((unsigned)nblk), dim3(kPostBlock), 0, st, dev_pixels, n, cutoff,
-                           S.blocks);
-        hipLaunchKernelGGL(bright_scan_kernel, dim3(1), dim3(kPostBlock), 0, st, S.blocks, (int)nblk, sc);
-        hipLaunchKernelGGL(bright_scatter_kernel, dim3((unsigned)nblk), dim3(kPostBlock), 0, st, dev_pixels, p->width, n,
-                           cutoff, (const unsigned int*)S.blocks, bright);
-        dim3 grid((p->width + kPostBlock - 1) / kPostBlock, p->height);
-        hipLaunchKernelGGL(glare_kernel, grid, dim3(kPostBlock), 0, st, dev_pixels, out, p->width, p->height,
-                           (const Bright*)bright, 0, cutoff, (const unsigned int*)&sc->nb);
-        processed = out;
-    } else if (dev_processed) {
-        POSTCHECK(ctx, hipMemcpyAsync(dev_processed, dev_pixels, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    const unsigned int quads = (unsigned int)((n + 4ll * kPostBlock - 1) / (4ll * kPostBlock));
+    const float* processed;
+    POSTCHECK(ctx, queue_glare(st, S, sc, dev_pixels, dev_processed, p->width, p->height, p->glare_cutoff, run_glare,
+                               &processed));
+    const unsigned int quads = quads_for(n);
     // the histograms' grid follows the device, not the image
     const unsigned int hgrid = std::min<unsigned int>(quads, (unsigned)(std::max(ipt_internal::ctx_cus(ctx), 1) * kStatsBlocksPerCu));
     if (want_max) hipLaunchKernelGGL(image_max_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, n, sc);
@@ -1343,73 +1380,59 @@ int ipt_display_stats_device(ipt_ctx* ctx, const ipt_display_stats_params* p, co
                                pass == kSelPasses - 1 ? 1 : 0, ss);
         }
     if (want_tone) {
-        float* tone = dev_tone ? dev_tone : S.tone;
-        const float inv_gamma = 2.2f;
-        const float gamma = (float)(double)(1.0f / inv_gamma);  // tone_map's exponent (gui.cpp:11-16)
-        hipLaunchKernelGGL(tone_white_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, tone, n, gamma,
+        float* tone = dev_tone ? dev_tone : scratch<float>(S, PostScratch::kTone);
+        hipLaunchKernelGGL(tone_white_kernel, dim3(quads), dim3(kPostBlock), 0, st, processed, tone, n, tone_gamma(),
                            (const StatsScalars*)ss, sc);
         if (dev_gray8)
             hipLaunchKernelGGL(gray8_kernel, dim3(quads), dim3(kPostBlock), 0, st, (const float*)tone, dev_gray8, n,
                                (const DisplayScalars*)sc);
     }
     if (dev_stats) hipLaunchKernelGGL(stats_out_kernel, dim3(1), dim3(64), 0, st, (const StatsScalars*)ss, dev_stats);
-    POSTCHECK(ctx, hipGetLastError());
-    POSTCHECK(ctx, hipEventRecord(S.done, st));
-    S.used = true;
-    S.last_stream = st;
-    return IPT_OK;
+    return post_queued(ctx, st);
 }
 
 int ipt_display_stats(ipt_ctx* ctx, const ipt_display_stats_params* p, const float* pixels, float* processed,
                       float* tone, uint8_t* gray8, uint32_t* hist, float* stats) {
     if (const int rc = stats_check(ctx, p, pixels, hist)) return rc;
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = ipt_internal::ctx_stream(ctx);
     const size_t n = (size_t)p->width * p->height, nb = (size_t)p->hist_buckets;
-    DevBuf<float> din, dproc, dtone, dstats;
-    DevBuf<uint8_t> dgray;
-    DevBuf<uint32_t> dhist;
-    POSTCHECK(ctx, hipMalloc(&din.p, n * sizeof(float)));
-    if (processed) POSTCHECK(ctx, hipMalloc(&dproc.p, n * sizeof(float)));
-    if (tone) POSTCHECK(ctx, hipMalloc(&dtone.p, n * sizeof(float)));
-    if (gray8) POSTCHECK(ctx, hipMalloc(&dgray.p, n));
-    if (nb) POSTCHECK(ctx, hipMalloc(&dhist.p, nb * sizeof(uint32_t)));
-    if (stats) POSTCHECK(ctx, hipMalloc(&dstats.p, 4 * sizeof(float)));
-    POSTCHECK(ctx, hipMemcpyAsync(din.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (const int rc = ipt_display_stats_device(ctx, p, din.p, dproc.p, dtone.p, dgray.p, dhist.p, dstats.p, st))
-        return rc;
-    if (processed) POSTCHECK(ctx, hipMemcpyAsync(processed, dproc.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (tone) POSTCHECK(ctx, hipMemcpyAsync(tone, dtone.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (gray8) POSTCHECK(ctx, hipMemcpyAsync(gray8, dgray.p, n, hipMemcpyDeviceToHost, st));
-    if (nb) POSTCHECK(ctx, hipMemcpyAsync(hist, dhist.p, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (stats) POSTCHECK(ctx, hipMemcpyAsync(stats, dstats.p, 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipStreamSynchronize(st));
-    return IPT_OK;
+    HostStage hs(ctx);
+    const float* din = hs.in(pixels, n);
+    float* dproc = hs.out(processed, n);
+    float* dtone = hs.out(tone, n);
+    uint8_t* dgray = hs.out(gray8, n);
+    uint32_t* dhist = hs.out(nb ? hist : nullptr, nb);  // (a buffer passed with hist_buckets 0 is not written)
+    float* dstats = hs.out(stats, 4);
+    if (hs.rc) return hs.rc;
+    if (const int rc = ipt_display_stats_device(ctx, p, din, dproc, dtone, dgray, dhist, dstats, hs.st)) return rc;
+    return hs.finish();
 }
 
 int ipt_smooth_device(ipt_ctx* ctx, const float* dev_in, float* dev_out, int width, int height, int side,
                       float* dev_max, void* hip_stream) {
     if (const int rc = smooth_check(ctx, dev_in, dev_out, width, height, side, dev_max)) return rc;
     const size_t n = (size_t)width * (size_t)height;
-    const bool filters = side >= 2 && side <= width && side <= height;  // some pixel qualifies
+    const bool filters = smooth_filters(width, height, side);
     const bool in_place = dev_out == dev_in;
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
-    if (const int rc = pgm_scratch(ctx, in_place && filters ? n : 0, st)) return rc;
-    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
-    PgmScalars* ps = static_cast<PgmScalars*>(S.pgm);
+    PostNeeds need;
+    need.n[PostScratch::kPgm] = 1;
+    need.n[PostScratch::kProcessed] = in_place && filters ? n : 0;
+    hipStream_t st;
+    if (const int rc = post_begin(ctx, hip_stream, need, &st)) return rc;
+    PostScratch& S = ipt_internal::ctx_post(ctx);
+    PgmScalars* ps = scratch<PgmScalars>(S, PostScratch::kPgm);
+    POSTCHECK(ctx, hipMemsetAsync(ps, 0, sizeof(PgmScalars), st));
     if (in_place) {  // the filter reads the context's copy (nothing changes when no pixel qualifies)
         if (filters) {
-            POSTCHECK(ctx, hipMemcpyAsync(S.processed, dev_in, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-            dim3 grid((width + kPostBlock - 1) / kPostBlock, height);
-            hipLaunchKernelGGL(smooth_kernel<false>, grid, dim3(kPostBlock), 0, st, (const float*)S.processed, dev_out,
-                               width, height, side, &ps->smooth_max);
+            float* copy = scratch<float>(S, PostScratch::kProcessed);
+            POSTCHECK(ctx, hipMemcpyAsync(copy, dev_in, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(smooth_kernel<false>, dim3(blocks_for(width), height), dim3(kPostBlock), 0, st,
+                               (const float*)copy, dev_out, width, height, side, &ps->smooth_max);
         }
     } else {
         POSTCHECK(ctx, launch_smooth(st, dev_in, dev_out, width, height, side, &ps->smooth_max));
     }
     if (dev_max) POSTCHECK(ctx, hipMemcpyAsync(dev_max, &ps->smooth_max, sizeof(float), hipMemcpyDeviceToDevice, st));
-    return pgm_queued(ctx, st);
+    return post_queued(ctx, st);
 }
 
 int ipt_pgm_device(ipt_ctx* ctx, const ipt_pgm_params* p, const float* dev_pixels, const float* dev_pixel_max,
@@ -1419,23 +1442,26 @@ int ipt_pgm_device(ipt_ctx* ctx, const ipt_pgm_params* p, const float* dev_pixel
     const long long n = (long long)W * H;
     const bool smooth = p->smooth_side >= 2, window = p->max_side >= 2;
     const int which = window ? kPgmMaxWindow : smooth ? kPgmMaxSmooth : dev_pixel_max ? kPgmMaxFold : kPgmMaxGiven;
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
     // a stage nobody reads is not run: smooth's pixels feed the bytes, the
     // window maximum and dev_smoothed, its maximum only rule 2
     const bool run_smooth = smooth && (dev_smoothed || dev_gray8 || window || dev_stats);
-    if (const int rc = pgm_scratch(ctx, run_smooth && !dev_smoothed ? (size_t)n : 0, st)) return rc;
-    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
-    PgmScalars* ps = static_cast<PgmScalars*>(S.pgm);
+    PostNeeds need;
+    need.n[PostScratch::kPgm] = 1;
+    need.n[PostScratch::kProcessed] = run_smooth && !dev_smoothed ? (size_t)n : 0;
+    hipStream_t st;
+    if (const int rc = post_begin(ctx, hip_stream, need, &st)) return rc;
+    PostScratch& S = ipt_internal::ctx_post(ctx);
+    PgmScalars* ps = scratch<PgmScalars>(S, PostScratch::kPgm);
+    POSTCHECK(ctx, hipMemsetAsync(ps, 0, sizeof(PgmScalars), st));
     const float* plane = dev_pixels;  // the pixels n_val reads
     if (run_smooth) {
-        float* out = dev_smoothed ? dev_smoothed : S.processed;
+        float* out = dev_smoothed ? dev_smoothed : scratch<float>(S, PostScratch::kProcessed);
         POSTCHECK(ctx, launch_smooth(st, dev_pixels, out, W, H, p->smooth_side, &ps->smooth_max));
         plane = out;
     } else if (dev_smoothed) {
         POSTCHECK(ctx, hipMemcpyAsync(dev_smoothed, dev_pixels, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
-    const unsigned int quads = (unsigned int)((n + 4ll * kPostBlock - 1) / (4ll * kPostBlock));
+    const unsigned int quads = quads_for(n);
     if (dev_gray8 || dev_stats) {
         if (window) POSTCHECK(ctx, launch_smooth(st, plane, nullptr, W, H, p->max_side, &ps->window_max));
         if (which == kPgmMaxFold)
@@ -1445,7 +1471,7 @@ int ipt_pgm_device(ipt_ctx* ctx, const ipt_pgm_params* p, const float* dev_pixel
     if (dev_gray8)
         hipLaunchKernelGGL(n_val_kernel, dim3(quads), dim3(kPostBlock), 0, st, plane, dev_gray8, n, p->contrast,
                            p->gamma, (const PgmScalars*)ps);
-    return pgm_queued(ctx, st);
+    return post_queued(ctx, st);
 }
 
 int ipt_adapt_device(ipt_ctx* ctx, const ipt_adapt_params* p, const float* dev_pixels, const uint32_t* dev_counters,
@@ -1460,31 +1486,24 @@ int ipt_adapt_device(ipt_ctx* ctx, const ipt_adapt_params* p, const float* dev_p
                                       "ipt_adapt_device: IPT_FLAG_GUI_PLANE alone, at most 2^31 pixels");
     const long long n = (long long)p->width * p->height;
     {
-        const void* in[3] = {dev_pixels, dev_counters, dev_m2};
-        for (int a = 0; a < 3; ++a)
-            if (overlap_(in[a], (size_t)n * 4, dev_mask, (size_t)n) || overlap_(in[a], (size_t)n * 4, dev_stats, 16))
-                return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_adapt_device: an output overlaps an input");
+        const size_t len[5] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n, 16};
+        const void* with_mask[4] = {dev_pixels, dev_counters, dev_m2, dev_mask};
+        const void* with_stats[5] = {dev_pixels, dev_counters, dev_m2, nullptr, dev_stats};
+        if (any_overlap(with_mask, len, 4, 3) || any_overlap(with_stats, len, 5, 3))
+            return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_adapt_device: an output overlaps an input");
         if (overlap_(dev_mask, (size_t)n, dev_stats, 16))
             return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_adapt_device: the outputs overlap");
     }
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
-    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
     // (no scratch of its own: the event alone, so that the context's waits cover the call)
-    if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
+    hipStream_t st;
+    if (const int rc = post_begin(ctx, hip_stream, PostNeeds{}, &st)) return rc;
     // the Grid map's row H-1 (H >= 2) is no sample's nominal destination
     const bool gui = (p->flags & IPT_FLAG_GUI_PLANE) != 0;
     const long long no_source = (!gui && p->height >= 2) ? (long long)(p->height - 1) * p->width : n;
     if (dev_stats) POSTCHECK(ctx, hipMemsetAsync(dev_stats, 0, 4 * sizeof(uint32_t), st));
-    const unsigned int blocks = (unsigned int)((n + kPostBlock - 1) / kPostBlock);
-    hipLaunchKernelGGL(adapt_kernel, dim3(blocks), dim3(kPostBlock), 0, st, dev_pixels, dev_counters, dev_m2, dev_mask,
-                       n, no_source, p->min_count, p->rel_tol, p->abs_tol, dev_stats);
-    POSTCHECK(ctx, hipGetLastError());
-    POSTCHECK(ctx, hipEventRecord(S.done, st));
-    S.used = true;
-    S.last_stream = st;
-    return IPT_OK;
+    hipLaunchKernelGGL(adapt_kernel, dim3(blocks_for(n)), dim3(kPostBlock), 0, st, dev_pixels, dev_counters, dev_m2,
+                       dev_mask, n, no_source, p->min_count, p->rel_tol, p->abs_tol, dev_stats);
+    return post_queued(ctx, st);
 }
 
 int ipt_denoise_device(ipt_ctx* ctx, const ipt_denoise_params* p, const float* dev_pixels, const uint32_t* dev_counters,
@@ -1494,19 +1513,14 @@ int ipt_denoise_device(ipt_ctx* ctx, const ipt_denoise_params* p, const float* d
         return rc;
     const int W = p->width, H = p->height;
     const size_t n = (size_t)W * (size_t)H;
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ipt_internal::ctx_stream(ctx);
-    ipt_internal::PostScratch& S = ipt_internal::ctx_post(ctx);
-    if (!S.done || n > S.denoise_cap) {
-        // (first call or a larger frame: the only path that allocates or waits)
-        if (const int rc = ipt_internal::post_wait(ctx)) return rc;
-        if (!S.done) POSTCHECK(ctx, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-        if (n > S.denoise_cap)
-            if (const int rc = post_grow(ctx, S.denoise, S.denoise_cap, n, 2 * sizeof(DnRecord))) return rc;
-    }
-    // the scratch is shared: a call on another stream runs after the previous one
-    if (S.used && S.last_stream != st) POSTCHECK(ctx, hipStreamWaitEvent(st, S.done, 0));
-    float4* rec[2] = {static_cast<float4*>(S.denoise), static_cast<float4*>(S.denoise) + 2 * S.denoise_cap};
+    PostNeeds need;
+    need.n[PostScratch::kDenoise] = n;
+    hipStream_t st;
+    if (const int rc = post_begin(ctx, hip_stream, need, &st)) return rc;
+    PostScratch& S = ipt_internal::ctx_post(ctx);
+    // the two record planes, one after the other
+    float4* rec[2] = {scratch<float4>(S, PostScratch::kDenoise),
+                      scratch<float4>(S, PostScratch::kDenoise) + 2 * S.buf[PostScratch::kDenoise].cap};
     // (diagnostics: an event after every pass, read by ipt_denoise_pass_ms)
     const char* prof = std::getenv("IPT_DENOISE_PROFILE");
     const bool timed = prof && std::atoi(prof) != 0;
@@ -1516,9 +1530,8 @@ int ipt_denoise_device(ipt_ctx* ctx, const ipt_denoise_params* p, const float* d
             if (!e) POSTCHECK(ctx, hipEventCreate(&e));
         POSTCHECK(ctx, hipEventRecord(S.denoise_ev[0], st));
     }
-    hipLaunchKernelGGL(denoise_prepare_kernel, dim3((unsigned)((n + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0,
-                       st, dev_pixels, dev_counters, dev_m2, reinterpret_cast<const uint32_t*>(dev_guides), rec[0],
-                       (long long)n);
+    hipLaunchKernelGGL(denoise_prepare_kernel, dim3(blocks_for((long long)n)), dim3(kPostBlock), 0, st, dev_pixels,
+                       dev_counters, dev_m2, reinterpret_cast<const uint32_t*>(dev_guides), rec[0], (long long)n);
     if (timed) POSTCHECK(ctx, hipEventRecord(S.denoise_ev[1], st));
     const int form = denoise_form();
     for (int k = 0; k < p->iterations; ++k) {
@@ -1558,11 +1571,7 @@ int ipt_denoise_device(ipt_ctx* ctx, const ipt_denoise_params* p, const float* d
         if (timed) POSTCHECK(ctx, hipEventRecord(S.denoise_ev[2 + k], st));
     }
     if (timed) S.denoise_timed = p->iterations;
-    POSTCHECK(ctx, hipGetLastError());
-    POSTCHECK(ctx, hipEventRecord(S.done, st));
-    S.used = true;
-    S.last_stream = st;
-    return IPT_OK;
+    return post_queued(ctx, st);
 }
 
 int ipt_denoise_pass_ms(ipt_ctx* ctx, float* ms) {
@@ -1582,95 +1591,62 @@ int ipt_denoise_pass_ms(ipt_ctx* ctx, float* ms) {
 int ipt_denoise(ipt_ctx* ctx, const ipt_denoise_params* p, const float* pixels, const uint32_t* counters,
                 const float* m2, const ipt_guide* guides, float* out, float* var_out) {
     if (const int rc = denoise_check(ctx, p, pixels, counters, m2, guides, out, var_out)) return rc;
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = ipt_internal::ctx_stream(ctx);
     const size_t n = (size_t)p->width * p->height;
-    DevBuf<float> dpx, dm2, dout, dvar;
-    DevBuf<uint32_t> dcnt;
-    DevBuf<ipt_guide> dg;
-    POSTCHECK(ctx, hipMalloc(&dpx.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMalloc(&dcnt.p, n * sizeof(uint32_t)));
-    POSTCHECK(ctx, hipMalloc(&dm2.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMalloc(&dg.p, n * sizeof(ipt_guide)));
-    POSTCHECK(ctx, hipMalloc(&dout.p, n * sizeof(float)));
-    if (var_out) POSTCHECK(ctx, hipMalloc(&dvar.p, n * sizeof(float)));
-    POSTCHECK(ctx, hipMemcpyAsync(dpx.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
-    POSTCHECK(ctx, hipMemcpyAsync(dcnt.p, counters, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    POSTCHECK(ctx, hipMemcpyAsync(dm2.p, m2, n * sizeof(float), hipMemcpyHostToDevice, st));
-    POSTCHECK(ctx, hipMemcpyAsync(dg.p, guides, n * sizeof(ipt_guide), hipMemcpyHostToDevice, st));
-    if (const int rc = ipt_denoise_device(ctx, p, dpx.p, dcnt.p, dm2.p, dg.p, dout.p, dvar.p, st)) return rc;
-    POSTCHECK(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (var_out) POSTCHECK(ctx, hipMemcpyAsync(var_out, dvar.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipStreamSynchronize(st));
-    return IPT_OK;
+    HostStage hs(ctx);
+    const float* dpx = hs.in(pixels, n);
+    const uint32_t* dcnt = hs.in(counters, n);
+    const float* dm2 = hs.in(m2, n);
+    const ipt_guide* dg = hs.in(guides, n);
+    float* dout = hs.out(out, n);
+    float* dvar = hs.out(var_out, n);
+    if (hs.rc) return hs.rc;
+    if (const int rc = ipt_denoise_device(ctx, p, dpx, dcnt, dm2, dg, dout, dvar, hs.st)) return rc;
+    return hs.finish();
 }
 
 int ipt_pgm(ipt_ctx* ctx, const ipt_pgm_params* p, const float* pixels, const float* pixel_max, float* smoothed,
             uint8_t* gray8, float* stats) {
     if (const int rc = pgm_check(ctx, p, pixels, pixel_max, smoothed, gray8, stats)) return rc;
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = ipt_internal::ctx_stream(ctx);
     const size_t n = (size_t)p->width * p->height;
     const bool need_fold = pixel_max && p->smooth_side < 2 && p->max_side < 2;  // the only rule that reads it
-    DevBuf<float> din, dpmax, dsm, dstats;
-    DevBuf<uint8_t> dgray;
-    POSTCHECK(ctx, hipMalloc(&din.p, n * sizeof(float)));
-    if (need_fold) POSTCHECK(ctx, hipMalloc(&dpmax.p, n * sizeof(float)));
-    if (smoothed) POSTCHECK(ctx, hipMalloc(&dsm.p, n * sizeof(float)));
-    if (gray8) POSTCHECK(ctx, hipMalloc(&dgray.p, n));
-    if (stats) POSTCHECK(ctx, hipMalloc(&dstats.p, 4 * sizeof(float)));
-    POSTCHECK(ctx, hipMemcpyAsync(din.p, pixels, n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (need_fold) POSTCHECK(ctx, hipMemcpyAsync(dpmax.p, pixel_max, n * sizeof(float), hipMemcpyHostToDevice, st));
-    if (const int rc = ipt_pgm_device(ctx, p, din.p, dpmax.p, dsm.p, dgray.p, dstats.p, st)) return rc;
-    if (smoothed) POSTCHECK(ctx, hipMemcpyAsync(smoothed, dsm.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (gray8) POSTCHECK(ctx, hipMemcpyAsync(gray8, dgray.p, n, hipMemcpyDeviceToHost, st));
-    if (stats) POSTCHECK(ctx, hipMemcpyAsync(stats, dstats.p, 4 * sizeof(float), hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipStreamSynchronize(st));
-    return IPT_OK;
+    HostStage hs(ctx);
+    const float* din = hs.in(pixels, n);
+    const float* dpmax = hs.in(need_fold ? pixel_max : nullptr, n);
+    float* dsm = hs.out(smoothed, n);
+    uint8_t* dgray = hs.out(gray8, n);
+    float* dstats = hs.out(stats, 4);
+    if (hs.rc) return hs.rc;
+    if (const int rc = ipt_pgm_device(ctx, p, din, dpmax, dsm, dgray, dstats, hs.st)) return rc;
+    return hs.finish();
 }
 
 int ipt_logf_host(const float* x, float* out, int64_t n) {
     if (!x || !out || n < 0) return IPT_E_INVALID;
-    const int nt = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t)
-        th.emplace_back([=]() {
-            const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-            for (int64_t i = lo; i < hi; ++i) out[i] = logf_(x[i]);
-        });
-    for (auto& t : th) t.join();
+    parallel_for(n, [=](int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) out[i] = logf_(x[i]);
+    });
     return IPT_OK;
 }
 
 int ipt_logf_device(ipt_ctx* ctx, const float* x, float* out, int64_t n) {
     if (!ctx) return IPT_E_INVALID;
     if (!x || !out || n < 0) return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_logf_device: bad arguments");
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = ipt_internal::ctx_stream(ctx);
-    DevBuf<float> din, dout;
-    POSTCHECK(ctx, hipMalloc(&din.p, std::max<int64_t>(n, 1) * sizeof(float)));
-    POSTCHECK(ctx, hipMalloc(&dout.p, std::max<int64_t>(n, 1) * sizeof(float)));
-    POSTCHECK(ctx, hipMemcpyAsync(din.p, x, n * sizeof(float), hipMemcpyHostToDevice, st));
+    HostStage hs(ctx);
+    const float* din = hs.in(x, (size_t)n, 1);  // (at least one element: n may be 0)
+    float* dout = hs.out(out, (size_t)n, 1);
+    if (hs.rc) return hs.rc;
     if (n > 0)
-        hipLaunchKernelGGL(logf_kernel, dim3((unsigned)((n + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0, st,
-                           (const float*)din.p, dout.p, (long long)n);
+        hipLaunchKernelGGL(logf_kernel, dim3(blocks_for(n)), dim3(kPostBlock), 0, hs.st, din, dout, (long long)n);
     POSTCHECK(ctx, hipGetLastError());
-    POSTCHECK(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipStreamSynchronize(st));
-    return IPT_OK;
+    return hs.finish();
 }
 
 int ipt_powf_host(const float* x, float y, float* out, int64_t n) {
     if (!x || !out || n < 0) return IPT_E_INVALID;
     if (!powf_y_ok(y)) return IPT_E_UNSUPPORTED;
-    const int nt = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t)
-        th.emplace_back([=]() {
-            const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-            for (int64_t i = lo; i < hi; ++i) out[i] = powf_(x[i], y);
-        });
-    for (auto& t : th) t.join();
+    parallel_for(n, [=](int64_t lo, int64_t hi) {
+        for (int64_t i = lo; i < hi; ++i) out[i] = powf_(x[i], y);
+    });
     return IPT_OK;
 }
 
@@ -1679,19 +1655,15 @@ int ipt_powf_device(ipt_ctx* ctx, const float* x, float y, float* out, int64_t n
     if (!x || !out || n < 0) return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_powf_device: bad arguments");
     if (!powf_y_ok(y))
         return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED, "ipt_powf_device: y must be finite, > 0 and no integer");
-    (void)hipSetDevice(ipt_internal::ctx_device(ctx));
-    hipStream_t st = ipt_internal::ctx_stream(ctx);
-    DevBuf<float> din, dout;
-    POSTCHECK(ctx, hipMalloc(&din.p, std::max<int64_t>(n, 1) * sizeof(float)));
-    POSTCHECK(ctx, hipMalloc(&dout.p, std::max<int64_t>(n, 1) * sizeof(float)));
-    POSTCHECK(ctx, hipMemcpyAsync(din.p, x, n * sizeof(float), hipMemcpyHostToDevice, st));
+    HostStage hs(ctx);
+    const float* din = hs.in(x, (size_t)n, 1);  // (at least one element: n may be 0)
+    float* dout = hs.out(out, (size_t)n, 1);
+    if (hs.rc) return hs.rc;
     if (n > 0)
-        hipLaunchKernelGGL(powf_kernel, dim3((unsigned)((n + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0, st,
-                           (const float*)din.p, y, dout.p, (long long)n);
+        hipLaunchKernelGGL(powf_kernel, dim3(blocks_for(n)), dim3(kPostBlock), 0, hs.st, din, y, dout,
+                           (long long)n);
     POSTCHECK(ctx, hipGetLastError());
-    POSTCHECK(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    POSTCHECK(ctx, hipStreamSynchronize(st));
-    return IPT_OK;
+    return hs.finish();
 }
 
 }  // extern "C"
@@ -1708,8 +1680,8 @@ int post_wait(ipt_ctx* ctx) {
 
 void post_release(ipt_ctx* ctx) {
     PostScratch& S = ctx_post(ctx);
-    for (void* b : {S.bright, (void*)S.blocks, S.scalars, S.stats, S.pgm, (void*)S.processed, (void*)S.tone, S.denoise})
-        if (b) (void)hipFree(b);
+    for (const ScratchBuf& b : S.buf)
+        if (b.p) (void)hipFree(b.p);
     if (S.done) (void)hipEventDestroy(S.done);
     for (hipEvent_t e : S.denoise_ev)
         if (e) (void)hipEventDestroy(e);
@@ -1719,8 +1691,8 @@ void post_release(ipt_ctx* ctx) {
 hipError_t launch_guide_scatter(hipStream_t st, const uint8_t* kinds, const float* hits, ipt_guide* dev_guides, int W,
                                 int H, bool gui) {
     const long long n = (long long)W * H;
-    hipLaunchKernelGGL(guide_scatter_kernel, dim3((unsigned)((n + kPostBlock - 1) / kPostBlock)), dim3(kPostBlock), 0, st,
-                       kinds, hits, reinterpret_cast<uint32_t*>(dev_guides), W, H, gui ? 1 : 0, n);
+    hipLaunchKernelGGL(guide_scatter_kernel, dim3(blocks_for(n)), dim3(kPostBlock), 0, st, kinds, hits,
+                       reinterpret_cast<uint32_t*>(dev_guides), W, H, gui ? 1 : 0, n);
     return hipGetLastError();
 }
 }  // namespace ipt_internal
