@@ -475,6 +475,19 @@ int ipt_last_kernel_ms(ipt_ctx* ctx, float* path_ms, float* accumulate_ms);
    such launch leaves the previous values. */
 int ipt_last_units(ipt_ctx* ctx, uint64_t out[3]);
 
+/* ABI 7 addition, a test probe: which path_kernel instance the context's most
+   recent path-kernel launch took, as the kernel's template arguments:
+   out = {MAXSUSP, COUNT, LMODE, GEOM, BOXIN, FIXED} (MAXSUSP 4 or 8 suspended
+   levels; COUNT 1 with IPT_FLAG_COUNTERS; LMODE 1 one light, 2 lights in LDS,
+   3 light BVH, 4 any light type, 5/6 one axis-aligned light A10/A01, 7/8
+   lattice A10/A01 with records in global memory, 9/10 with records in LDS;
+   GEOM an IPT_GEOM_* value; BOXIN 1 for the box planes' in-range form; FIXED
+   0, -1 for n_rays a power of two, 4 for the fixed four-level tree). Recorded
+   at the launch, so valid as soon as a render call has returned.
+   IPT_E_INVALID if the context has launched no path kernel (a new context, or
+   one that made preview and replay calls only). */
+int ipt_last_instance(ipt_ctx* ctx, int32_t out[6]);
+
 /* ABI 7 addition, a test probe: the compaction plan of the call's FIRST
    launch (p as for a render, IPT_FLAG_COMPACT implied; dev_mask [H][W] on the
    device as for ipt_render_masked_device, or NULL). Runs the launch's

@@ -139,7 +139,7 @@ EXPORTED_SYMBOLS = (
     "ipt_smooth_device", "ipt_pgm_device", "ipt_pgm", "ipt_logf_host", "ipt_logf_device",
     "ipt_preview_values", "ipt_replay_samples",
     "ipt_render_masked_device_async", "ipt_render_masked_device", "ipt_adapt_device", "ipt_render_adaptive",
-    "ipt_last_units", "ipt_compact_plan",
+    "ipt_last_units", "ipt_compact_plan", "ipt_last_instance",
     "ipt_guides_device", "ipt_guides", "ipt_denoise_device", "ipt_denoise", "ipt_denoise_pass_ms",
 )
 
@@ -241,6 +241,8 @@ def load(path: str | os.PathLike | None = None):
         lib.ipt_last_units.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.ipt_compact_plan.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(lib, "ipt_last_instance"):  # ABI 7 addition (instance probe)
+        lib.ipt_last_instance.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     if hasattr(lib, "ipt_denoise_device"):  # ABI 7 additions (denoising)
         lib.ipt_guides_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p]
         lib.ipt_guides.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p]
@@ -693,6 +695,13 @@ class Context:
         out = (C.c_uint64 * 3)()
         _check(self.lib, self.h, self.lib.ipt_last_units(self.h, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def last_instance(self):
+        """(MAXSUSP, COUNT, LMODE, GEOM, BOXIN, FIXED): the path_kernel instance
+        of the context's most recent path-kernel launch (ipt_last_instance)."""
+        out = (C.c_int32 * 6)()
+        _check(self.lib, self.h, self.lib.ipt_last_instance(self.h, out))
+        return tuple(int(v) for v in out)
 
     def compact_plan(self, p: Params, mask_ptr=None):
         """The compaction plan of the call's first launch (ipt_compact_plan):

@@ -3271,6 +3271,8 @@ struct ipt_ctx {
     float2* d_frame_sc = nullptr;  // frame_table_kernel, 1 GiB
     float last_path_ms = 0.0f, last_acc_ms = 0.0f;
     int blocks_per_cu = 0;      // of the last path-kernel launch
+    // its template arguments {MAXSUSP, COUNT, LMODE, GEOM, BOXIN, FIXED} (ipt_last_instance; MAXSUSP 0: none yet)
+    int32_t last_instance[6] = {0, 0, 0, 0, 0, 0};
     bool box_generic = false;   // IPT_BOX_GENERIC=1: the box instances' generic range form (tests)
     bool lattice_lds = true;    // IPT_LATTICE_LDS=0: the lattice instances with global records (tests)
     size_t max_lds = 160 * 1024;  // the device's LDS per workgroup (hipDeviceAttributeMaxSharedMemoryPerBlock)
@@ -3578,6 +3580,8 @@ int launch_path5(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     bpc = std::max(1, std::min(bpc, 2048 / kBlock));  // (at most 32 waves per CU)
     if (ctx->bpc_override > 0) bpc = std::min(bpc, ctx->bpc_override);  // IPT_BLOCKS_PER_CU (profiling)
     ctx->blocks_per_cu = bpc;
+    const int32_t inst[6] = {MAXSUSP, COUNT ? 1 : 0, LMODE, GEOM, BOXIN ? 1 : 0, FIXED};
+    std::copy(inst, inst + 6, ctx->last_instance);
     dim3 grid(ctx->n_cu * bpc), block(kBlock);
     hipLaunchKernelGGL((path_kernel<MAXSUSP, COUNT, LMODE, GEOM, BOXIN, FIXED>), grid, block, lds, st, kp);
     HIPCHECK(ctx, hipGetLastError());
@@ -4885,6 +4889,13 @@ int ipt_last_kernel_ms(ipt_ctx* ctx, float* path_ms, float* accumulate_ms) {
 int ipt_last_units(ipt_ctx* ctx, uint64_t out[3]) {
     if (!ctx || !out) return IPT_E_INVALID;
     for (int i = 0; i < 3; ++i) out[i] = ctx->last_units[i];
+    return IPT_OK;
+}
+
+int ipt_last_instance(ipt_ctx* ctx, int32_t out[6]) {
+    if (!ctx || !out) return IPT_E_INVALID;
+    if (ctx->last_instance[0] == 0) return fail(ctx, IPT_E_INVALID, "ipt_last_instance: no path-kernel launch yet");
+    std::copy(ctx->last_instance, ctx->last_instance + 6, out);
     return IPT_OK;
 }
 
