@@ -42,134 +42,21 @@
 #include "ipt_path.h"
 #include "ipt_knobs.h"
 #include "ipt_diag.h"
+#include "ipt_kparams.h"     // KParams, the instances' launch shape and LDS layout
+#include "ipt_scene_plan.h"  // plan_scene: what ipt_upload_scene decides (host only)
+#include "ipt_select.h"      // select_path: which path_kernel instance a launch takes (host only)
 
 using namespace ipt;
 
 namespace {
 
-constexpr int kBlock = IPT_BLOCK;  // threads per workgroup (4 waves; ipt_knobs.h)
 template <typename T>
 __device__ __forceinline__ void keep_alive(const T& v) {
     const float* p = reinterpret_cast<const float*>(&v);
     for (int i = 0; i < (int)(sizeof(T) / 4); ++i) asm volatile("" ::"v"(p[i]));
 }
-constexpr int kStackFields = 6;   // pos3, res, mult, meta(i | kind<<8)
 constexpr int kPoolChunk = 256;   // work units per global atomic
 constexpr int kNumCounters = 15;
-
-// Unread fields: the fields marked (unread) below lost their last reader when
-// the build switches that selected their code were retired; the host leaves
-// them zero. They keep their places because KParams' layout decides how the
-// compiler groups the kernel-argument loads: taking any of them out regroups
-// those loads in some kernel and changes its register assignment or its
-// instruction count (DESIGN.md §9 has the counts per field group). Removing
-// them is a change of device code, to be measured as one.
-struct KParams {
-    int W, H, spp, spp_offset, n_rays, depth_max;
-    int meta_shift;  // a suspended level's meta word: ti | kind << meta_shift (8, or 16 for n_rays > 255)
-    uint32_t key0, key1;
-    int n_cand;              // candidate source rows
-    const int* __restrict__ cand_rows;    // [n_cand] source row index
-    int tile_rows, n_shards, shard_id;
-    unsigned long long total_units;
-    unsigned long long* unit_counter;
-    // the launch's pool-drained flag (signal memory, hipStreamWaitValue64's
-    // operand): the wave that takes the last chunk stores drain_seq there
-    unsigned long long* drained;
-    unsigned long long drain_seq;
-#if IPT_RAYLOG
-    RayLogRec* raylog;               // [raylog_cap]
-    unsigned long long* raylog_n;    // finished traces seen
-    unsigned long long raylog_cap;
-    unsigned raylog_every;
-#endif
-    float* __restrict__ values;           // [spp][n_cand][W]
-    uint8_t* __restrict__ codes;          // [spp][n_cand][W]
-    uint8_t* __restrict__ flags;          // [H][W]
-    unsigned long long* counters;
-    int geometry_kind;
-    int n_lights;
-    const LightDev* __restrict__ lights;  // [n_lights]
-    const float* __restrict__ weights;    // [n_lights+1]
-    const float* __restrict__ cdf;        // [n_lights+1] sequential prefix sums of weights
-    const Frame* __restrict__ wall_frames;  // [5]
-    vec3 cam_pos, cam_dir, cam_right, cam_up;
-    int n_spheres;
-    const float4* __restrict__ spheres;   // (c.xyz, r)
-    float bvh_tmargin;                    // sphere BVH / grid: additive pruning margin (1e-3 D, ipt_bvh.h)
-    int n_grid;                           // > 0: uniform sphere grid (ipt_bvh.h SphereGrid) instead of the BVH
-    float grid_g0[3], grid_h[3], grid_inv_h[3], grid_m;
-    float grid_g1[3];                     // g0 + (float)n * h, the grid's far corner (host-computed)
-    int grid_n[3];
-    const int* __restrict__ grid_start;   // [cells + 1]
-    // (unread: see the note on unread fields above KParams)
-    const int* __restrict__ grid_packed;
-    int grid_packed_words, grid_packed_nb;
-    const void* __restrict__ grid_cells;
-    const BvhSphere* __restrict__ grid_items;
-    // the same items packed for the wave walk: centre and radius as one float4
-    // per item (16-byte stride: a cell's items share lines), original indices
-    // in a separate array
-    const float4* __restrict__ grid_c4;
-    const int* __restrict__ grid_idx;
-    const BvhNode* __restrict__ bvh_nodes;     // n_nodes > 0: sphere BVH (ipt_bvh.h)
-    const BvhSphere* __restrict__ bvh_prims;
-    int n_nodes;
-    const BvhNode* __restrict__ light_nodes;   // n_light_nodes > 0: light BVH over index ranges
-    int n_light_nodes;
-    int lnodes_lds;                       // light BVH staged in LDS (kLightsGlobal)
-    // kLightsGridA10/A01: coplanar axis-aligned lights on a lattice (LightGrid)
-    const int* __restrict__ lgrid;        // [lg_nu * lg_nv] light index per cell, -1 = none
-    const float4* __restrict__ lax;       // [n_lights][3] LightAx records
-    int lg_nu, lg_nv;
-    float lg_u0, lg_v0, lg_icw, lg_ich;   // cell coordinates: (q - u0) * icw
-    float lg_e;                           // candidate margin in cells (LightGrid::e)
-    // skip-ahead (prologue): every light sample's point lies on the plane z =
-    // sa_pz and the light normal is (+-0, +-0, sa_nz): light picks at nodes
-    // with sa_nz * (sa_pz - z) >= 0 are certain skips (sa_on, host-checked)
-    // u01(w) < c  <=>  w < (ceil(c 2^24) << 8) (clamped to [0, 2^32]) for the
-    // draw word w: the single light's cdf[0], cdf[1] (pk_u0, pk_u1) and the
-    // light-pick bound (sa_u: one light: cdf[0]; a lattice with a non-decreasing
-    // cdf: cdf[nl - 1]; else 0, never) as word thresholds (host: word_threshold)
-    unsigned long long pk_u0, pk_u1, sa_u;
-    int sa_on;
-    float sa_pz, sa_nz;
-    float sa_cl;                          // (unread)
-    float lg_pn, lg_nn;                   // the lights' shared plane: P[na], n[na]
-    int cdf_bsearch;                      // cdf non-decreasing: pick by binary search
-    // |cdf[i] - (i+1) 2^-e| < 2^-e/2 for every light i and a non-decreasing
-    // cdf (host-checked): the pick is floor(r 2^e) - 1, + 0 or + 1 by two cdf
-    // entries, then cdf[nl] decides past the lights. It is taken on the draw's
-    // 24-bit integer g = w >> 8: floor(r 2^e) = g >> (24 - e) and r < c <=> g <
-    // ceil(c 2^24); the staged cdf then holds those integer thresholds
-    // (cdf_end_t: cdf[nl]'s)
-    int cdf_p2;  // 1: near-uniform as above; 2: every threshold exact, no cdf read
-    float cdf_p2s, cdf_end;               // (unread)
-    int cdf_p2e;
-    uint32_t cdf_end_t;
-    // (unread)
-    int lpf_calc, lc_shift;
-    float lc_x0, lc_y0, lc_dx, lc_dy, lc_ax, lc_ay;
-    int ltr_calc, lg_ident;
-    float lc_ix, lc_iy, lc_area, lc_spow;
-    const int* __restrict__ cdf_lo;       // [kCdfBuckets] or null: first c with cdf[c] > b/256
-    double inv_per_pass, inv_w;           // 1/(n_cand*W), 1/W (exact 32-bit unit decomposition)
-    uint32_t per_pass32;                  // n_cand*W (< 2^32)
-    int box_inrange;                      // camera and sphere list within 2^39 (box_plane_t<true>): the sphere-list
-                                          // and preview kernels (the box path instances: BOXIN)
-    const float* __restrict__ cos_a;      // [2^24] CosineDdf table by u1's 24 bits: sin(acos(sqrt(u1)))
-    const float2* __restrict__ cos_b;     // (unread)
-    const float2* __restrict__ frame_sc;  // frame_table_kernel: RotateDdf angle (sin, cos) by to.z
-    const uint4* __restrict__ rg;         // [total_units][2] raygen_kernel records
-    int count;                            // raygen_kernel: accumulate the drift counter
-    int plane;                            // new_path_setup: kPlaneGrid / kPlaneGui (IPT_FLAG_GUI_PLANE)
-    // new_path_setup: the caller's sample mask [H][W] by nominal destination
-    // pixel, or null (ipt_render_masked_device). Appended: no other field moves,
-    // and path_kernel, which never reads it, keeps its instructions
-    const uint8_t* __restrict__ mask;
-};
-// The render plane's index map: GridRenderPlane::addRay's or Gui::addRay's.
-enum { kPlaneGrid = 0, kPlaneGui = 1 };
 
 // floor(n / d) for 32-bit n, d >= 1 from a double reciprocal: the estimate's
 // error is below (n/d) * 2^-51 < 1/d (n < 2^32), i.e. below the distance of a
@@ -702,77 +589,6 @@ __device__ __forceinline__ float trace_geometry(const KParams& kp, vec3 o, vec3 
     return best;
 }
 
-// Scene data staged once per workgroup (never re-read from HBM/L2 inside the
-// step loop): wall frames, lights (<= kLdsLights), mixture weights + CDF and
-// the candidate-row table live in LDS after the DFS stack.
-constexpr int kLdsLights = 16;
-constexpr int kLightWords = (int)(sizeof(LightDev) / 4);
-// LDS after the DFS stack: frames, [LMODE 2: lights, weights, cdf],
-// [sharded: candidate rows], [LMODE 3: weights, cdf, light BVH].
-// Frames live in LDS, [12][kFrameStride]: column tid is the lane's current
-// sphere-node frame, columns kBlock..kBlock+4 the five wall frames.
-// CosineDdf samples come from exact tables (cos_table_kernel).
-// Column stride: single-light instances use kBlock + 64 words (a multiple of
-// 64 dwords, so a column's 12 words pair into ds_read2st64/ds_write2st64;
-// 2.7 KiB more, still 4 workgroups/CU); the others keep kBlock + 8 so that
-// their light data fits 4 workgroups as well.
-// Threads per workgroup of a path-kernel instance: kBlock, or one 1024-thread
-// workgroup per CU for the light lattices with their records in LDS
-// (kLightsGridA10L/A01L: the per-lane LDS is the same, the shared tables and
-// records are held once per CU instead of once per 256-thread workgroup).
-constexpr int kLatticeBlock = 1024;
-__host__ __device__ constexpr bool resumable_geom(int geom);
-// The sphere-list (resumable) instances run 64-thread workgroups: a persistent
-// launch's tail frees a CU slot per finished wave instead of per finished
-// 4-wave workgroup, so the next launch fills it sooner (C3 +2.2 %, 16-spp
-// progressive calls 0.964 -> 0.985 of one call); C2 keeps 256 (its frame
-// columns' ds_read2st64 stride, -1.2 % at 64).
-__host__ __device__ constexpr int block_of(int lmode, int geom) {
-    return (lmode == 9 || lmode == 10) ? kLatticeBlock : (resumable_geom(geom) ? IPT_RES_BLOCK : kBlock);
-}
-// the wave-spread grid walk's per-lane LDS: an 8-byte slot
-__host__ __device__ constexpr int walk_lds_words(int lmode, int geom) {
-    return resumable_geom(geom) ? 2 * block_of(lmode, geom) : 0;
-}
-__host__ __device__ constexpr int frame_stride(int lmode, int geom) {
-    return ((lmode == 1 || lmode == 5 || lmode == 6) && walk_lds_words(lmode, geom) == 0 && block_of(lmode, geom) >= 256)
-               ? block_of(lmode, geom) + 64
-               : block_of(lmode, geom) + 8;
-}
-__host__ __device__ constexpr size_t scene_lds_words(int lmode, int geom) {
-    return (size_t)walk_lds_words(lmode, geom) + 12 * (size_t)frame_stride(lmode, geom) +
-           (lmode == 2 ? (size_t)kLdsLights * kLightWords + 2 * (kLdsLights + 1) : 0);
-}
-// kLightsGlobal: mixture weights + CDF (and, when small, the light BVH) are
-// staged in LDS after the fixed layout: their global copies would be evicted
-// from L2 by the CosineDdf gathers, and the pick / walk are chains of
-// dependent loads.
-constexpr int kLdsLightNodesMax = 512;
-// [weights | cdf | cdf bucket starts (kCdfBuckets)] then the light BVH nodes or
-// the lattice cells, 16-byte aligned
-constexpr int kCdfBuckets = 256;
-// The lattice instances leave the weights in global memory (read once per hit
-// light) so that C5's 256 emitters fit 4 workgroups per CU: [cdf | buckets].
-__host__ __device__ inline int global_light_prefix_words(int nl, bool grid = false) {
-    return ((grid ? 1 : 2) * (nl + 1) + kCdfBuckets + 3) & ~3;
-}
-__host__ __device__ inline size_t global_light_lds_words(int nl, int n_nodes_lds, bool grid = false) {
-    return (size_t)global_light_prefix_words(nl, grid) + 8 * (size_t)n_nodes_lds;
-}
-
-// Where the lights live during the step loop (compile time, so that no
-// generic/flat pointer is ever formed: a flat load would make the compiler
-// wait for every outstanding radiance store).
-enum { kLightsOne = 1, kLightsLds = 2, kLightsGlobal = 3, kLightsAny = 4, kLightsOneA10 = 5, kLightsOneA01 = 6,
-       kLightsGridA10 = 7, kLightsGridA01 = 8, kLightsGridA10L = 9, kLightsGridA01L = 10 };
-// kLightsGridA10 / A01: many AreaLights, all axis-aligned with the same axis
-// pattern, sharing their plane and lying on a lattice, one per cell
-// (light_grid_build): a ray's lights are found by its plane point's cell(s)
-// instead of the light BVH walk; weights and CDF staged as kLightsGlobal.
-// kLightsGridA10L / A01L: the same with the 48-byte records in LDS, one
-// 1024-thread workgroup per CU (block_of), chosen when the LDS fits (+5 % C5)
-__host__ __device__ constexpr bool grid_lights(int lm) { return lm >= kLightsGridA10 && lm <= kLightsGridA01L; }
-__host__ __device__ constexpr bool lattice_a10(int lm) { return lm == kLightsGridA10 || lm == kLightsGridA10L; }
 // the instances whose box trace takes the nearest-candidate planes
 // (trace_box_planes_nearest): every in-range box instance (path_kernel's
 // BOXIN), the lattice instances included since the range form is fixed per
@@ -781,24 +597,6 @@ __host__ __device__ constexpr bool lattice_a10(int lm) { return lm == kLightsGri
 // The generic box instances keep the full form (kNearest), and so do the
 // sphere-list instances' walls, which gain nothing measurable (4.10).
 __host__ __device__ constexpr bool box_nearest(int geom) { return geom == IPT_GEOM_SPHERE_IN_BOX; }
-// the box instances that exist with the step's per-launch choices fixed
-// (path_kernel's FIXED): the axis-aligned single light (sample_scenes[0]'s
-// instance, +0.8 % C2) and the light lattices (+1.1 % C5)
-__host__ __device__ constexpr bool step_fixed_mode(int lm) {
-    return lm == kLightsOneA10 || lm == kLightsOneA01 || grid_lights(lm);
-}
-// path_kernel's FIXED: 0, kFixedPow2, or the tree shape K = log2 n_rays (the
-// one compiled K: n_rays 16, every configuration of bench.py but C3)
-constexpr int kFixedPow2 = -1;
-constexpr int kTreeK = 4;
-__host__ __device__ constexpr bool lax_in_lds(int lm) { return lm == kLightsGridA10L || lm == kLightsGridA01L; }
-__host__ __device__ constexpr bool global_lights(int lm) { return lm == kLightsGlobal || grid_lights(lm); }
-// kLightsOneA10 / A01: the single light is an axis-aligned AreaLight
-// (axis_aligned_light, ipt_path.h) with x_axis along y and y_axis along x
-// (A10, sample_scenes[0]'s light) or along x and y (A01), normal along z
-__host__ __device__ constexpr bool one_light(int lm) { return lm == kLightsOne || lm == kLightsOneA10 || lm == kLightsOneA01; }
-// kLightsAny: global-memory lights of any type (sphere, point, outer lights
-// present); the other modes are AreaLight-only.
 
 template <int LMODE>
 struct LightSet {
@@ -830,12 +628,9 @@ struct LightSet {
 
 // GEOM (IPT_GEOM_*) is a template parameter so that the box instance carries
 // neither the sphere-list code nor its pointers (SGPR pressure).
-// Sphere-list instances carry the resumable walk's state (their walks are
-// bounded per step and resumed in later steps): they
+// Sphere-list instances carry the resumable walk's state (resumable_geom,
+// ipt_kparams.h: their walks are bounded per step and resumed in later steps): they
 // are given 3 waves per SIMD of registers (their LDS allows 3 workgroups).
-__host__ __device__ constexpr bool resumable_geom(int geom) {
-    return geom == IPT_GEOM_SPHERES_IN_BOX || geom == IPT_GEOM_SPHERES;
-}
 // many-light instances without a sphere list resume their light-BVH walk the same way
 __host__ __device__ constexpr bool resumable_lights(int lmode, int geom) {
     return lmode == 3 /* kLightsGlobal */ && !resumable_geom(geom);
@@ -1107,7 +902,7 @@ __global__ __launch_bounds__(256) void compact_expand_kernel(const CompactBufs c
 // two (the pop's unwind keeps its exact scaling form alone) and the lights'
 // skip-ahead plane exists (kp.sa_on: the skip-ahead and the pre-skip lose
 // their guard). Both are read from the launch's parameters by the dispatch
-// (launch_path4), so a launch without them takes the FIXED = 0 instance.
+// (select_path4, ipt_select.h), so a launch without them takes the FIXED = 0 instance.
 // FIXED = K > 0 (kTreeK; the 4-level instances): the tree's shape is the
 // launch's as well -- n_rays == 2^K, hence meta_shift, and depth_max > K + 1:
 // no node deeper than K is pushed (n_rays >> d == 0 beyond), so no ray has
@@ -3200,8 +2995,8 @@ struct ResidentPlane {
 };
 
 using ipt_internal::DevBuf;
-// The uploaded scene, kept once. ipt_upload_scene builds a fresh record and
-// swaps it in only after every upload succeeded; the record it replaces frees
+// The uploaded scene, kept once. ipt_upload_scene builds a fresh record from
+// the scene's plan (ScenePlan, ipt_scene_plan.h) and swaps it in only after every upload succeeded; the record it replaces frees
 // its buffers as it goes.
 struct Scene {
     // Every KParams field that depends only on the scene and on the context's
@@ -3503,18 +3298,6 @@ void candidate_rows(const ipt_params* p, std::vector<int>& rows, std::vector<int
     }
 }
 
-// The draw word w's u01(w) = (w >> 8) 2^-24 is below c exactly when w >> 8 <
-// T = ceil(c 2^24) (both sides exact: an integer against c scaled by a power
-// of two), i.e. when w < T << 8: T = 0 for c <= 0 or NaN (never), 2^24 for
-// c >= 1 (always, as a 64-bit bound).
-unsigned long long word_threshold(float c) {
-    const double x = (double)c * 16777216.0;
-    if (!(x > 0.0)) return 0ull;
-    if (x >= 16777216.0) return 1ull << 32;
-    return (unsigned long long)std::ceil(x) << 8;
-}
-
-int needed_susp(const ipt_params* p);
 int validate(ipt_ctx* ctx, const ipt_params* p, bool preview = false) {
     if (!ctx) return IPT_E_INVALID;
     if (!p) return fail(ctx, IPT_E_INVALID, "params is NULL");
@@ -3545,28 +3328,6 @@ int validate(ipt_ctx* ctx, const ipt_params* p, bool preview = false) {
     return IPT_OK;
 }
 
-// Number of suspended stack levels the DFS can need.
-int needed_susp(const ipt_params* p) {
-    // a node at depth d is pushed iff d < depth_max and (n_rays >> d) > 0
-    int maxpush = -1;
-    for (int d = 0; d < p->depth_max; ++d)
-        if ((p->n_rays >> d) > 0) maxpush = d;
-    return maxpush < 0 ? 0 : maxpush;  // suspended levels = depth of deepest pushed node
-}
-
-// dynamic LDS bytes of a path-kernel instance (the layout at the top of path_kernel)
-template <int MAXSUSP, int LMODE, int GEOM>
-size_t path_lds_bytes(const KParams& kp) {
-    constexpr int kBlock = block_of(LMODE, GEOM);
-    const size_t cells = (size_t)kp.lg_nu * kp.lg_nv;
-    return ((size_t)MAXSUSP * kStackFields * kBlock + scene_lds_words(LMODE, GEOM) +
-            (LMODE == kLightsGlobal ? global_light_lds_words(kp.n_lights, kp.lnodes_lds ? kp.n_light_nodes : 0) : 0) +
-            (grid_lights(LMODE) ? global_light_lds_words(kp.n_lights, 0, true) +
-                                      (lax_in_lds(LMODE) ? ((cells + 3) & ~(size_t)3) + 12 * (size_t)kp.n_lights : cells)
-                                : 0)) *
-           sizeof(float);
-}
-
 template <int MAXSUSP, bool COUNT, int LMODE, int GEOM, bool BOXIN, int FIXED>
 int launch_path5(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     constexpr int kBlock = block_of(LMODE, GEOM);
@@ -3587,79 +3348,18 @@ int launch_path5(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
     HIPCHECK(ctx, hipGetLastError());
     return IPT_OK;
 }
-// the box instances' range form (path_kernel's BOXIN): in range unless the
-// scene is not (box_inrange) or IPT_BOX_GENERIC=1 forces the generic instance;
-// and, in range, the instance with the step's per-launch choices fixed (FIXED)
-// where the launch has them: n_rays a power of two, a skip-ahead plane
-template <int MAXSUSP, bool COUNT, int LMODE, int GEOM>
-int launch_path4(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
-    if constexpr (GEOM == IPT_GEOM_SPHERE_IN_BOX) {
-        if (kp.box_inrange && !ctx->box_generic) {
-            if constexpr (step_fixed_mode(LMODE)) {
-                const uint32_t nr = (uint32_t)kp.n_rays;
-                if (kp.sa_on && nr != 0u && (nr & (nr - 1u)) == 0u) {
-                    // the tree shape as well: n_rays == 2^K and depth_max > K + 1 (then
-                    // the stack has K levels: the 4-level instances)
-                    if constexpr (MAXSUSP == kTreeK)
-                        if (nr == (1u << kTreeK) && kp.depth_max > kTreeK + 1)
-                            return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, kTreeK>(ctx, kp, st);
-                    return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, kFixedPow2>(ctx, kp, st);
-                }
-            }
-            return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, true, 0>(ctx, kp, st);
-        }
-    }
-    return launch_path5<MAXSUSP, COUNT, LMODE, GEOM, false, 0>(ctx, kp, st);
-}
-// -DIPT_AB_BUILD -DIPT_C2_ONLY=1: experiment builds (scripts/variants.sh)
-// instantiate the sample_scenes[0] kernel alone (ipt_knobs.h).
-template <int MAXSUSP, bool COUNT, int LMODE>
-int launch_path3(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
-    if constexpr (IPT_C2_ONLY != 0) {
-        if (MAXSUSP != 4 || LMODE != IPT_C2_LMODE || kp.geometry_kind != IPT_GEOM_SPHERE_IN_BOX)
-            return fail(ctx, IPT_E_UNSUPPORTED, "IPT_C2_ONLY experiment build");
-        return launch_path4<4, COUNT, IPT_C2_LMODE, IPT_GEOM_SPHERE_IN_BOX>(ctx, kp, st);
-    } else {
-    switch (kp.geometry_kind) {
-        case IPT_GEOM_SPHERES_IN_BOX: return launch_path4<MAXSUSP, COUNT, LMODE, IPT_GEOM_SPHERES_IN_BOX>(ctx, kp, st);
-        case IPT_GEOM_FLOOR: return launch_path4<MAXSUSP, COUNT, LMODE, IPT_GEOM_FLOOR>(ctx, kp, st);
-        case IPT_GEOM_CORNER: return launch_path4<MAXSUSP, COUNT, LMODE, IPT_GEOM_CORNER>(ctx, kp, st);
-        case IPT_GEOM_SPHERES: return launch_path4<MAXSUSP, COUNT, LMODE, IPT_GEOM_SPHERES>(ctx, kp, st);
-        case IPT_GEOM_SMALLPT: return launch_path4<MAXSUSP, COUNT, LMODE, IPT_GEOM_SMALLPT>(ctx, kp, st);
-        default: return launch_path4<MAXSUSP, COUNT, LMODE, IPT_GEOM_SPHERE_IN_BOX>(ctx, kp, st);
-    }
-    }
-}
-template <int MAXSUSP, bool COUNT>
-int launch_path2(ipt_ctx* ctx, const KParams& kp, hipStream_t st) {
-    if (ctx->scene.any_round_light) return launch_path3<MAXSUSP, COUNT, kLightsAny>(ctx, kp, st);
-    if (kp.n_lights == 1) {
-        if (ctx->scene.light_axis == 1) return launch_path3<MAXSUSP, COUNT, kLightsOneA10>(ctx, kp, st);
-        if (ctx->scene.light_axis == 2) return launch_path3<MAXSUSP, COUNT, kLightsOneA01>(ctx, kp, st);
-        return launch_path3<MAXSUSP, COUNT, kLightsOne>(ctx, kp, st);
-    }
-    if (kp.n_lights <= kLdsLights) return launch_path3<MAXSUSP, COUNT, kLightsLds>(ctx, kp, st);
-    if constexpr (IPT_C2_ONLY == 0) {
-        // (the lattice is only built for sphere-in-box scenes)
-        // the records-in-LDS instance wherever its LDS fits one workgroup per CU
-        constexpr int G = IPT_GEOM_SPHERE_IN_BOX;
-        if (ctx->scene.light_pattern == 1 && kp.geometry_kind == G) {
-            if (ctx->lattice_lds && path_lds_bytes<MAXSUSP, kLightsGridA10L, G>(kp) <= ctx->max_lds)
-                return launch_path4<MAXSUSP, COUNT, kLightsGridA10L, G>(ctx, kp, st);
-            return launch_path4<MAXSUSP, COUNT, kLightsGridA10, G>(ctx, kp, st);
-        }
-        if (ctx->scene.light_pattern == 2 && kp.geometry_kind == G) {
-            if (ctx->lattice_lds && path_lds_bytes<MAXSUSP, kLightsGridA01L, G>(kp) <= ctx->max_lds)
-                return launch_path4<MAXSUSP, COUNT, kLightsGridA01L, G>(ctx, kp, st);
-            return launch_path4<MAXSUSP, COUNT, kLightsGridA01, G>(ctx, kp, st);
-        }
-    }
-    return launch_path3<MAXSUSP, COUNT, kLightsGlobal>(ctx, kp, st);
-}
-// the instances for the call's stack depth (4 or 8 suspended levels) and counting flag
+// The launch's instance by select_path (ipt_select.h), launched by launch_path5.
 int launch_path(ipt_ctx* ctx, const KParams& kp, hipStream_t st, const LaunchMode& m) {
-    if (m.susp <= 4) return m.count ? launch_path2<4, true>(ctx, kp, st) : launch_path2<4, false>(ctx, kp, st);
-    return m.count ? launch_path2<8, true>(ctx, kp, st) : launch_path2<8, false>(ctx, kp, st);
+    const Scene& sc = ctx->scene;
+    const SelectIn in{kp, m.susp, m.count, sc.any_round_light, sc.light_axis, sc.light_pattern,
+                      ctx->box_generic, ctx->lattice_lds, ctx->max_lds};
+    bool launched = false;
+    const int rc = select_path(in, [&](auto ms, auto cnt, auto lm, auto g, auto boxin, auto fixed) {
+        launched = true;
+        return launch_path5<decltype(ms)::value, decltype(cnt)::value, decltype(lm)::value, decltype(g)::value,
+                            decltype(boxin)::value, decltype(fixed)::value>(ctx, kp, st);
+    });
+    return launched ? rc : fail(ctx, rc, "IPT_C2_ONLY experiment build");
 }
 
 template <bool FULL>
@@ -4205,118 +3905,12 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
         if (rc) return rc;
     }
     ctx->has_scene = false;  // any failure below leaves no scene (ipt_capi.h)
-    if (!s) return fail(ctx, IPT_E_INVALID, "scene is NULL");
-    if (s->geometry_kind < IPT_GEOM_SPHERE_IN_BOX || s->geometry_kind > IPT_GEOM_SMALLPT)
-        return fail(ctx, IPT_E_UNSUPPORTED, "unknown geometry_kind");
-    if (s->n_lights < 0 || s->n_lights > kMaxLights || (s->n_lights > 0 && !s->lights))
-        return fail(ctx, IPT_E_UNSUPPORTED, "n_lights out of range");
-    if (s->n_spheres < 0 || (s->n_spheres > 0 && !s->spheres))
-        return fail(ctx, IPT_E_INVALID, "bad sphere array");
-    const int nl = s->n_lights;
-    std::vector<LightDev> L(std::max(nl, 1));
-    std::vector<float> powers(std::max(nl, 1));
-    bool any_round = false;
-    for (int i = 0; i < nl; ++i) {
-        const ipt_area_light& a = s->lights[i];
-        if (a.type < IPT_LIGHT_AREA_DIAMOND || a.type > IPT_LIGHT_OUTER_SPHERE)
-            return fail(ctx, IPT_E_UNSUPPORTED, "unknown light type");
-        if (a.type >= IPT_LIGHT_SPHERE) any_round = true;
-        L[i] = make_light(v3(a.position[0], a.position[1], a.position[2]),
-                          v3(a.x_axis[0], a.x_axis[1], a.x_axis[2]),
-                          v3(a.y_axis[0], a.y_axis[1], a.y_axis[2]), a.power, a.type);
-        powers[i] = a.power;
+    ScenePlan plan;  // everything the scene decides, on the host (ipt_scene_plan.h)
+    {
+        std::string err;
+        const int rc = plan_scene(s, PlanSettings{ctx->lnodes_lds != 0, ctx->light_grid_on != 0}, plan, err);
+        if (rc) return fail(ctx, rc, err);
     }
-    std::vector<float> wts(nl + 1), cdf(nl + 1);
-    mixture_weights(powers.data(), nl, wts.data());
-    float acc = 0.0f;
-    for (int i = 0; i <= nl; ++i) {
-        acc += wts[i];  // UnionDdf::sample's running sum (ddf.cpp:145-146)
-        cdf[i] = acc;
-    }
-    // plane frames, indexed by the plane primitive the geometry trace returns:
-    // box: RotateDdf(CosineDdf, -plane) for planes {+x,+y,+z,-x,-z};
-    // corner: RotateDdf(CosineDdf, n) for n = +x, +y, +z (GeometryCorner.cpp:16-28);
-    // floor: its unrotated CosineDdf == make_frame((0,0,1)), which is exactly
-    // the identity (axis falls back to +x, angle acos(1) = 0, sin 0 = 0, cos 0 = 1)
-    const vec3 planes[5] = {v3(1, 0, 0), v3(0, 1, 0), v3(0, 0, 1), v3(-1, 0, 0), v3(0, 0, -1)};
-    Frame wall[5];
-    for (int i = 0; i < 5; ++i) wall[i] = make_frame(-planes[i]);
-    if (s->geometry_kind == IPT_GEOM_CORNER)
-        for (int i = 0; i < 3; ++i) wall[i] = make_frame(planes[i]);
-    if (s->geometry_kind == IPT_GEOM_FLOOR) wall[0] = make_frame(v3(0, 0, 1));
-    std::vector<float4> sph(std::max(s->n_spheres, 1));
-    for (int i = 0; i < s->n_spheres; ++i)
-        sph[i] = make_float4(s->spheres[i].center[0], s->spheres[i].center[1], s->spheres[i].center[2], s->spheres[i].radius);
-    // Bound of every surface point a ray can start from: the box [-1,1]^3 and
-    // the spheres (ipt_bvh.h pads item boxes from it and the camera).
-    float B = 1.0f;
-    for (int i = 0; i < s->n_spheres; ++i)
-        B = std::max(B, std::max(std::fabs(sph[i].x), std::max(std::fabs(sph[i].y), std::fabs(sph[i].z))) +
-                            std::fabs(sph[i].w));
-    const float cam[3] = {s->camera.position[0], s->camera.position[1], s->camera.position[2]};
-    std::vector<BvhNode> bnodes;
-    std::vector<BvhSphere> bprims;
-    int per_order = 0;
-    float tmargin = 0.0f;
-    // many spheres inside the box: a uniform grid; otherwise (and if the grid
-    // cannot be built) the BVH
-    SphereGrid grid;
-    bool use_grid = s->geometry_kind == IPT_GEOM_SPHERES_IN_BOX && s->n_spheres > 256 &&
-                    grid_build_spheres(reinterpret_cast<const float*>(sph.data()), s->n_spheres, cam, B, grid);
-    if (!use_grid && (s->geometry_kind == IPT_GEOM_SPHERES_IN_BOX || s->geometry_kind == IPT_GEOM_SPHERES) &&
-        s->n_spheres > 16)
-        bvh_build_spheres(reinterpret_cast<const float*>(sph.data()), s->n_spheres, cam, B, bnodes, bprims,
-                          &per_order, &tmargin);
-    // light BVH: only for the global-memory light mode (n_lights > kLdsLights)
-    std::vector<BvhNode> lnodes;
-    int n_lnodes = 0;
-    if (nl > kLdsLights && !any_round) {  // the light BVH indexes AreaLights only
-        std::vector<std::array<float, 3>> lp(nl), lx(nl), ly(nl);
-        std::vector<std::array<float, 9>> li(nl);
-        for (int i = 0; i < nl; ++i) {
-            lp[i] = {L[i].P.x, L[i].P.y, L[i].P.z};
-            lx[i] = {L[i].x.x, L[i].x.y, L[i].x.z};
-            ly[i] = {L[i].y.x, L[i].y.y, L[i].y.z};
-            for (int c = 0; c < 3; ++c) {
-                li[i][3 * c + 0] = L[i].inv.c[c].x;
-                li[i][3 * c + 1] = L[i].inv.c[c].y;
-                li[i][3 * c + 2] = L[i].inv.c[c].z;
-            }
-        }
-        if (!bvh_build_lights(nl, reinterpret_cast<const float(*)[3]>(lp.data()),
-                              reinterpret_cast<const float(*)[3]>(lx.data()),
-                              reinterpret_cast<const float(*)[3]>(ly.data()),
-                              reinterpret_cast<const float(*)[9]>(li.data()), cam, B, lnodes, &n_lnodes)) {
-            lnodes.clear();
-            n_lnodes = 0;
-        }
-    }
-    LightGrid lg;
-    const bool use_lgrid = ctx->light_grid_on && nl > kLdsLights && !any_round &&
-                           s->geometry_kind == IPT_GEOM_SPHERE_IN_BOX && light_grid_build(L.data(), nl, lg);
-    // (the lattice instances take the range-free light arithmetic: every
-    // light's ranges proven as for the single light)
-    bool lg_inr = use_lgrid;
-    for (int i = 0; lg_inr && i < nl; ++i) lg_inr = light_ranges_box(L[i], 2, cam);
-    if (!use_lgrid || !lg_inr) lg = LightGrid{};
-    // bucket starts of the pick's scan: lo[b] = first c with cdf[c] > b/256
-    // (the float compare the scan makes; nl+1 if none); kept when no bucket
-    // spans more than 8 entries
-    std::vector<int> cdf_lo(kCdfBuckets);
-    bool use_cdf_lo = nl > kLdsLights && !any_round;
-    for (int b = 0; use_cdf_lo && b < kCdfBuckets; ++b) {
-        const float start = (float)b / (float)kCdfBuckets;
-        int c = 0;
-        while (c <= nl && !(start < cdf[c])) ++c;
-        cdf_lo[b] = c;
-        const float end = (float)(b + 1) / (float)kCdfBuckets;
-        int e = c;
-        while (e <= nl && !(end < cdf[e])) ++e;
-        if (e - c > 8) use_cdf_lo = false;
-    }
-    bool cdf_mono = true;
-    for (int i = 0; i <= nl; ++i)
-        if (!(cdf[i] == cdf[i]) || (i > 0 && !(cdf[i - 1] <= cdf[i]))) cdf_mono = false;
     // Device phase, transactional: the new scene is built in a fresh record,
     // every buffer allocated and filled there first. Until all of them
     // succeeded the context has no scene (renders fail with IPT_E_NOSCENE,
@@ -4333,157 +3927,46 @@ int ipt_upload_scene(ipt_ctx* ctx, const ipt_scene* s) {
         if (count) HIPCHECK(ctx, hipMemcpy(buf.p, src, sizeof(T) * count, hipMemcpyHostToDevice));
         return IPT_OK;
     };
-    Scene sc;  // (kp all zero: what this scene does not set, no kernel reads -- DESIGN.md 5)
+    auto upload_v = [&](auto& buf, const auto& v) { return upload(buf, v.data(), v.size()); };
+    Scene sc;
     Scene::Bufs& b = sc.bufs;
-    KParams& k = sc.kp;
+    const bool use_grid = plan.kp.n_grid > 0, use_bvh = !plan.bvh_nodes.empty(), lattice = plan.light_pattern != 0;
     int rc = IPT_OK;
-    if (use_grid && !rc) rc = upload(b.grid_start, grid.start.data(), grid.start.size());
-    if (use_grid && !rc) rc = upload(b.grid_items, grid.items.data(), grid.items.size());
-    // the wave walk's items: [items] centre/radius, then [items] original indices
-    const size_t n_items = use_grid ? grid.items.size() : 0;
-    if (use_grid && !rc) {
-        std::vector<float4> c4(n_items + (n_items + 3) / 4);
-        int* idx = reinterpret_cast<int*>(c4.data() + n_items);
-        for (size_t i = 0; i < n_items; ++i) {
-            const BvhSphere& it = grid.items[i];
-            c4[i] = make_float4(it.c[0], it.c[1], it.c[2], it.r);
-            idx[i] = it.index;
-        }
-        rc = upload(b.grid_c4, c4.data(), c4.size());
-    }
-    if (!lnodes.empty() && !rc) rc = upload(b.light_nodes, lnodes.data(), lnodes.size());
-    if (lg.pattern && !rc) rc = upload(b.lgrid, lg.cells.data(), lg.cells.size());
-    std::vector<LightAx> laxr;
-    if (lg.pattern)
-        for (int i = 0; i < nl; ++i) laxr.push_back(light_ax_record(L[i], lg.pattern, wts[i]));
-    if (lg.pattern && !rc) rc = upload(b.lax, laxr.data(), laxr.size());
-    if (use_cdf_lo && !rc) rc = upload(b.cdf_lo, cdf_lo.data(), cdf_lo.size());
-    if (!bnodes.empty() && !rc) rc = upload(b.bvh_nodes, bnodes.data(), bnodes.size());
-    if (!bnodes.empty() && !rc) rc = upload(b.bvh_prims, bprims.data(), bprims.size());
-    if (!rc) rc = upload(b.lights, L.data(), L.size());
-    if (!rc) rc = upload(b.weights, wts.data(), (size_t)nl + 1);
-    if (!rc) rc = upload(b.cdf, cdf.data(), (size_t)nl + 1);
-    if (!rc) rc = upload(b.wall, wall, 5);
-    if (!rc) rc = upload(b.spheres, sph.data(), sph.size());
+    if (use_grid && !rc) rc = upload_v(b.grid_start, plan.grid_start);
+    if (use_grid && !rc) rc = upload_v(b.grid_items, plan.grid_items);
+    if (use_grid && !rc) rc = upload_v(b.grid_c4, plan.grid_c4);
+    if (!plan.light_nodes.empty() && !rc) rc = upload_v(b.light_nodes, plan.light_nodes);
+    if (lattice && !rc) rc = upload_v(b.lgrid, plan.lgrid);
+    if (lattice && !rc) rc = upload_v(b.lax, plan.lax);
+    if (!plan.cdf_lo.empty() && !rc) rc = upload_v(b.cdf_lo, plan.cdf_lo);
+    if (use_bvh && !rc) rc = upload_v(b.bvh_nodes, plan.bvh_nodes);
+    if (use_bvh && !rc) rc = upload_v(b.bvh_prims, plan.bvh_prims);
+    if (!rc) rc = upload_v(b.lights, plan.lights);
+    if (!rc) rc = upload_v(b.weights, plan.weights);
+    if (!rc) rc = upload_v(b.cdf, plan.cdf);
+    if (!rc) rc = upload(b.wall, plan.wall, 5);
+    if (!rc) rc = upload_v(b.spheres, plan.spheres);
     if (rc) return rc;  // the record frees what it holds; the context keeps no scene
-    k.geometry_kind = s->geometry_kind;
-    k.n_lights = nl;
+    // (kp's scalars from the plan: what this scene does not set is zero and no kernel reads it -- DESIGN.md 5)
+    KParams& k = sc.kp = plan.kp;
     k.lights = b.lights.p;
     k.weights = b.weights.p;
     k.cdf = b.cdf.p;
     k.wall_frames = b.wall.p;
-    const ipt_camera& c = s->camera;
-    k.cam_pos = v3(c.position[0], c.position[1], c.position[2]);
-    k.cam_dir = v3(c.direction[0], c.direction[1], c.direction[2]);
-    k.cam_right = v3(c.right[0], c.right[1], c.right[2]);
-    k.cam_up = v3(c.up[0], c.up[1], c.up[2]);
-    k.n_spheres = s->n_spheres;
     k.spheres = b.spheres.p;
-    if (use_grid) {
-        k.n_grid = (int)(grid.start.size() - 1);
-        k.bvh_tmargin = grid.tmargin;
-        for (int a = 0; a < 3; ++a) {
-            k.grid_g0[a] = grid.g0[a];
-            k.grid_h[a] = grid.h[a];
-            k.grid_inv_h[a] = grid.inv_h[a];
-            k.grid_n[a] = grid.n[a];
-            k.grid_g1[a] = grid.g0[a] + (float)grid.n[a] * grid.h[a];
-        }
-        k.grid_m = grid.m;
-        k.grid_start = b.grid_start.p;
-        k.grid_items = b.grid_items.p;
-        k.grid_c4 = b.grid_c4.p;
-        k.grid_idx = reinterpret_cast<const int*>(b.grid_c4.p + n_items);
-    }
-    if (!bnodes.empty()) {
-        k.bvh_nodes = b.bvh_nodes.p;
-        k.bvh_prims = b.bvh_prims.p;
-        k.n_nodes = per_order;  // nodes per octant order; buffer holds kBvhOrders of them
-        k.bvh_tmargin = tmargin;
-    }
+    k.grid_start = b.grid_start.p;
+    k.grid_items = b.grid_items.p;
+    k.grid_c4 = b.grid_c4.p;
+    if (use_grid) k.grid_idx = reinterpret_cast<const int*>(b.grid_c4.p + plan.grid_items.size());
+    k.bvh_nodes = b.bvh_nodes.p;
+    k.bvh_prims = b.bvh_prims.p;
     k.light_nodes = b.light_nodes.p;
-    k.n_light_nodes = lnodes.empty() ? 0 : n_lnodes;
-    // light BVH staged in LDS (IPT_LNODES_LDS=0 at ipt_create keeps it in
-    // global memory): the resumable light walk runs at 3 workgroups/CU, which
-    // the extra LDS keeps, and gains 10 % on C5 (43.8 vs 40.2 Mpaths/s)
-    k.lnodes_lds = (ctx->lnodes_lds && k.n_light_nodes > 0 && k.n_light_nodes <= kLdsLightNodesMax) ? 1 : 0;
     k.lgrid = b.lgrid.p;
     k.lax = reinterpret_cast<const float4*>(b.lax.p);
     k.cdf_lo = b.cdf_lo.p;
-    sc.light_pattern = lg.pattern;
-    k.lg_nu = lg.nu;
-    k.lg_nv = lg.nv;
-    k.lg_u0 = lg.u0;
-    k.lg_v0 = lg.v0;
-    k.lg_icw = lg.icw;
-    k.lg_ich = lg.ich;
-    k.lg_e = lg.e;
-    k.lg_pn = lg.pn;
-    k.lg_nn = lg.nn;
-    k.cdf_bsearch = cdf_mono ? 1 : 0;
-    k.pk_u0 = word_threshold(cdf[0]);
-    k.pk_u1 = word_threshold(nl >= 1 ? cdf[1] : 0.0f);
-    // cdf[nl]'s threshold in every scene: the lattice instances' pre-skip
-    // compares the next pick word with it in every step (pre_ft), also where
-    // no leaf is taken (cdf_p2 == 0) -- there a taken word picks a light, below
-    // cdf[nl - 1] <= cdf[nl], and must read as three draws
-    k.cdf_end_t = (uint32_t)(word_threshold(cdf[nl]) >> 8);
-    // nearly equal lights (e.g. 256 of one power: weights within rounding of
-    // 0.5/256 = 2^-9): with w = 2^-e and every light's |cdf[i] - (i+1) w| <= d
-    // < w/2 on a non-decreasing cdf, the first c with r < cdf[c] is ce - 1, ce
-    // or ce + 1 for ce = floor(r/w) = floor(r 2^e) (exact: r = m 2^-24): cdf[ce-2]
-    // <= (ce-1) w + d < ce w <= r and cdf[ce+1] >= (ce+2) w - d > r + w - d > r.
-    // Past the lights (ce >= nl) the scan's answer is ce's clamp to nl - 1, then
-    // cdf[nl]. The kernel reads cdf[ce-1] and cdf[ce] only.
-    for (int e = 1; cdf_mono && nl > kLdsLights && !any_round && e <= 20 && !k.cdf_p2; ++e) {
-        const double w = std::ldexp(1.0, -e);
-        bool ok = (double)nl * w <= 1.0;
-        for (int i = 0; ok && i < nl; ++i) ok = std::fabs((double)cdf[i] - (double)(i + 1) * w) < 0.25 * w;
-        if (!ok) continue;
-        k.cdf_p2 = 1;
-        k.cdf_p2e = e;
-        // exactly uniform on the draw's 24-bit integer: every light's
-        // ceil(cdf[i] 2^24) is (i+1) 2^(24-e) (C5's 256 equal emitters),
-        // so the integer pick reads no cdf entry at all (KParams::cdf_p2 2)
-        bool exact = true;
-        for (int i = 0; exact && i < nl; ++i)
-            exact = (word_threshold(cdf[i]) >> 8) == ((unsigned long long)(i + 1) << (24 - e));
-        if (exact) k.cdf_p2 = 2;
-    }
-    sc.any_round_light = any_round;
-    // the axis-aligned single-light instances also take the range-free roots
-    // and quotients: only where their ranges are proven (sphere-in-box scenes)
-    sc.light_axis = (nl == 1 && !any_round) ? axis_aligned_light(L[0]) : 0;
-    if (sc.light_axis && !(s->geometry_kind == IPT_GEOM_SPHERE_IN_BOX && light_ranges_box(L[0], 2, cam)))
-        sc.light_axis = 0;
-    // skip-ahead plane: one area light (or a lattice, whose lights share P.z
-    // and n.z bit for bit) whose axes have zero z components, so that every
-    // sampled point (x*u1 + y*u2) + P has z = P.z exactly, and whose normal is
-    // (+-0, +-0, n.z): a light sample's cosinus then has the sign of
-    // n.z * (o.z - P.z) whatever the draws (lighting.cpp:93-104, 125-134)
-    {
-        auto zero = [](float f) { return (f2u(f) & 0x7fffffffu) == 0u; };
-        bool ok = nl >= 1 && !any_round && (nl == 1 || lg.pattern != 0);
-        for (int i = 0; ok && i < nl; ++i)
-            ok = (L[i].type == 0 || L[i].type == 1) && zero(L[i].x.z) && zero(L[i].y.z) && zero(L[i].n.x) &&
-                 zero(L[i].n.y) && !zero(L[i].n.z) && std::isfinite(L[i].n.z) && std::fabs(L[i].P.z) >= 0x1p-32f &&
-                 std::fabs(L[i].P.z) <= 0x1p32f &&
-                 f2u(L[i].P.z) == f2u(L[0].P.z) && f2u(L[i].n.z) == f2u(L[0].n.z);
-        float sa_cl = 0.0f;
-        if (ok) {
-            k.sa_on = 1;
-            k.sa_pz = L[0].P.z;
-            k.sa_nz = L[0].n.z;
-            // UnionDdf::sample picks a light (c < nl) iff r < cdf[c] for some
-            // c < nl, i.e. iff r < cdf[nl - 1] on a non-decreasing cdf
-            sa_cl = (nl == 1 || cdf_mono) ? cdf[nl - 1] : 0.0f;
-        }
-        k.sa_u = word_threshold(sa_cl);
-    }
-    // every ray origin (camera, surface points within B) inside 2^39: the box
-    // planes may use the range-free division (box_plane_t<true>)
-    const float lim = 549755813888.0f;  // 2^39
-    k.box_inrange = B < lim && std::fabs(cam[0]) < lim && std::fabs(cam[1]) < lim && std::fabs(cam[2]) < lim;
+    sc.any_round_light = plan.any_round_light;
+    sc.light_axis = plan.light_axis;
+    sc.light_pattern = plan.light_pattern;
     std::swap(ctx->scene, sc);  // (sc, now the previous scene, frees its buffers on return)
     ctx->has_scene = true;
     return IPT_OK;

@@ -48,12 +48,12 @@ __global__ __launch_bounds__(256) void bench(float* out, float seed) {
             int p;
             acc = sink(acc, trace_box(o, d, &p) + (float)p);
         } else if (OP == 8) {
-            vec3 h;
-            const bool hit = light_trace(L, o, d, &h);
+            vec3 h, n;
+            const bool hit = light_trace(L, o, d, &h, &n);
             acc = sink(acc, h.x + (hit ? 1.0f : 0.0f));
         } else if (OP == 9) {
             vec3 h = o + d;
-            acc = sink(acc, light_pdf(L, o, true, h));
+            acc = sink(acc, light_pdf(L, o, true, h, L.n));
         } else if (OP == 10) {
             const vec3 n = normalize(o + d);
             acc = sink(acc, n.x + n.y + n.z);

@@ -1,29 +1,29 @@
 """Which path_kernel instances a launch can take, and one small case for each.
 
 path_kernel<MAXSUSP, COUNT, LMODE, GEOM, BOXIN, FIXED> (ipt_kernels.hip) is
-compiled once for every combination the selector names (launch_path ...
-launch_path5): the list in profiles/path_instances.txt, written from a build
+compiled once for every combination the selector names (select_path ...
+select_path4, ipt_amd/csrc/ipt_select.h): the list in profiles/path_instances.txt, written from a build
 by scripts/path_instances.py. A key here is that tuple of six integers, as
 ipt_last_instance returns it; a case key is the key without COUNT.
 
 REACHABLE restates the selector over abstract launches. An abstract launch is
 
   susp      needed_susp(p): the depth of the deepest pushed node, 0 .. 8
-            (validate() refuses more); launch_path takes MAXSUSP 4 for
+            (validate() refuses more); select_path takes MAXSUSP 4 for
             susp <= 4 and 8 otherwise;
   count     IPT_FLAG_COUNTERS (mode_of);
   lights    the scene's light class, below;
-  geom      geometry_kind, 0 .. 5 (launch_path3; an unknown kind renders as 0);
+  geom      geometry_kind, 0 .. 5 (select_path3; an unknown kind renders as 0);
   generic   box scenes only: the camera or the sphere list lies outside 2^39
-            (box_inrange, set at the end of ipt_upload_scene) or the context
-            was created under IPT_BOX_GENERIC=1 (launch_path4);
-  pow2      n_rays is a power of two (launch_path4: nr != 0 && !(nr & (nr-1)));
-  tree16    n_rays == 16 and depth_max > 5 (launch_path4, kTreeK = 4);
+            (box_inrange, set at the end of plan_scene) or the context
+            was created under IPT_BOX_GENERIC=1 (select_path4);
+  pow2      n_rays is a power of two (select_path4: nr != 0 && !(nr & (nr-1)));
+  tree16    n_rays == 16 and depth_max > 5 (select_path4, kTreeK = 4);
   lds_ok    lattices only: IPT_LATTICE_LDS is not 0 and the records-in-LDS
-            layout fits the device's LDS (launch_path2, path_lds_bytes).
+            layout fits the device's LDS (select_path2, path_lds_bytes).
 
-Light classes (launch_path2 and the upload code that sets any_round_light,
-light_axis and light_pattern):
+Light classes (select_path2, and plan_scene, ipt_scene_plan.h, which sets
+any_round_light, light_axis and light_pattern):
 
   round     any sphere, point or outer light                     -> kLightsAny
   one       one area light, light_axis == 0                      -> kLightsOne
@@ -37,13 +37,13 @@ light_axis and light_pattern):
 Which abstract launches exist (constraints(), each from the source):
 
   a. light_axis is cleared unless geometry_kind is IPT_GEOM_SPHERE_IN_BOX and
-     light_ranges_box() proves the light's ranges ("if (sc.light_axis &&
+     light_ranges_box() proves the light's ranges ("if (out.light_axis &&
      !(s->geometry_kind == IPT_GEOM_SPHERE_IN_BOX && light_ranges_box(...)))
-     sc.light_axis = 0;" in ipt_upload_scene): one_a10 / one_a01 exist on
+     out.light_axis = 0;" in plan_scene): one_a10 / one_a01 exist on
      geom 0 only.
   b. the lattice is built for geom 0 only ("use_lgrid = ... s->geometry_kind
-     == IPT_GEOM_SPHERE_IN_BOX && light_grid_build(...)" in ipt_upload_scene,
-     and launch_path2 compares geometry_kind again): lat_* exist on geom 0
+     == IPT_GEOM_SPHERE_IN_BOX && light_grid_build(...)" in plan_scene,
+     and select_path2 compares geometry_kind again): lat_* exist on geom 0
      only. The same lights on another geometry are `many`.
   c. light_ranges_box() needs dmax <= 2^8, with the camera inside dmax: a
      scene whose camera is out of range (2^39) has neither light_axis nor a
@@ -112,7 +112,7 @@ from ipt_amd import capi, scenes
 
 f32 = np.float32
 
-# path_kernel's LMODE (ipt_kernels.hip's kLights* enum) and FIXED
+# path_kernel's LMODE (ipt_kparams.h's kLights* enum) and FIXED
 ONE, LDS, GLOBAL, ANY, ONE_A10, ONE_A01, GRID_A10, GRID_A01, GRID_A10L, GRID_A01L = range(1, 11)
 FIXED_POW2, TREE_K = -1, 4
 BOX = capi.IPT_GEOM_SPHERE_IN_BOX
@@ -121,9 +121,9 @@ LIGHT_CLASSES = ("round", "one", "one_a10", "one_a01", "few", "lat_a10", "lat_a0
 
 
 def select(susp, count, lights, geom, generic, pow2, tree16, lds_ok):
-    """launch_path ... launch_path5 on an abstract launch: the instance key."""
-    maxsusp = 4 if susp <= 4 else 8                                    # launch_path
-    if lights == "round":                                              # launch_path2
+    """select_path ... select_path4 (ipt_select.h) on an abstract launch: the instance key."""
+    maxsusp = 4 if susp <= 4 else 8                                    # select_path
+    if lights == "round":                                              # select_path2
         lmode = ANY
     elif lights in ("one", "one_a10", "one_a01"):
         lmode = {"one": ONE, "one_a10": ONE_A10, "one_a01": ONE_A01}[lights]
@@ -134,7 +134,7 @@ def select(susp, count, lights, geom, generic, pow2, tree16, lds_ok):
         lmode = (GRID_A10L if a10 else GRID_A01L) if lds_ok else (GRID_A10 if a10 else GRID_A01)
     else:
         lmode = GLOBAL
-    if geom == BOX and not generic:                                    # launch_path4
+    if geom == BOX and not generic:                                    # select_path4
         if lmode in (ONE_A10, ONE_A01, GRID_A10, GRID_A01, GRID_A10L, GRID_A01L) and pow2:  # step_fixed_mode, sa_on (d)
             if maxsusp == TREE_K and tree16:
                 return (maxsusp, int(count), lmode, geom, 1, TREE_K)
@@ -172,11 +172,11 @@ def _unreachable():
     out = {}
     for m, c in itertools.product((4, 8), (0, 1)):
         for lm, g in itertools.product((ONE_A10, ONE_A01), GEOMS[1:]):
-            out[(m, c, lm, g, 0, 0)] = ("ipt_upload_scene clears light_axis unless geometry_kind == "
+            out[(m, c, lm, g, 0, 0)] = ("plan_scene clears light_axis unless geometry_kind == "
                                         "IPT_GEOM_SPHERE_IN_BOX (rule a)")
     for c, lm in itertools.product((0, 1), (GRID_A10L, GRID_A01L)):
         for boxin, fixed in ((1, 0), (1, FIXED_POW2), (0, 0)):
-            out[(8, c, lm, BOX, boxin, fixed)] = ("launch_path2: path_lds_bytes<8, kLightsGridA..L> >= 192 KiB "
+            out[(8, c, lm, BOX, boxin, fixed)] = ("select_path2: path_lds_bytes<8, kLightsGridA..L> >= 192 KiB "
                                                   "> max_lds (rule f)")
     return out
 
@@ -402,7 +402,7 @@ CASES = _cases()
 # every sample of this case is 0 by construction: exempt from the liveliness conditions
 DARK = {"box/beyond"}
 # GeometryFloor is one plane seen from above: a ray leaving it meets no surface again, so no node below
-# depth 1 exists whatever depth_max. Its MAXSUSP 8 instances are reachable (launch_path goes by n_rays and
+# depth 1 exists whatever depth_max. Its MAXSUSP 8 instances are reachable (select_path goes by n_rays and
 # depth_max alone) and are rendered, but cannot suspend a fifth level.
 SINGLE_BOUNCE = {"floor"}
 

@@ -1,7 +1,8 @@
 """Every reachable path_kernel instance against the oracle, once.
 
-tests/instance_cases.py restates the selector (launch_path ... launch_path5)
-and gives every instance it can return a small case; this file renders each
+tests/instance_cases.py restates the selector (select_path, ipt_select.h; the
+CPU suite holds every case's key against the selector itself,
+tests/test_scene_plan_cpu.py) and gives every instance it can return a small case; this file renders each
 case with and without IPT_FLAG_COUNTERS and asserts, in this order,
 
   1. ipt_last_instance() is the case's key, so that a case which drifted onto

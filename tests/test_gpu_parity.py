@@ -516,7 +516,7 @@ def test_failed_upload_leaves_no_scene(gpu_ctx, oracle, monkeypatch, fail_at):
     and leaves the context with no scene, so the next render fails with
     IPT_E_NOSCENE instead of launching on freed or null scene buffers; a later
     upload recovers and renders bit-exactly."""
-    desc = scenes.make_scene_spheres(400, seed=1)  # sphere grid + lights + spheres: 7 device buffers
+    desc = scenes.make_scene_spheres(400, seed=1)  # the sphere grid's 3 device buffers + the 5 of every scene: 8 (test_scene_plan_cpu.py)
     p = capi.make_params(16, 12, 1, n_rays=8, depth_max=5)
     gpu_ctx.upload_scene(scenes.make_scene_box())
     gpu_ctx.render_values(p)

@@ -2,7 +2,7 @@
 FIXED = K): a launch whose n_rays is 2^K for the compiled K
 (4: n_rays 16) and whose depth_max exceeds K + 1 takes an instance that reads
 neither n_rays, meta_shift nor depth_max in its step; every other launch takes
-the instance it took before (launch_path4).
+the instance it took before (select_path4, ipt_select.h).
 
 Each case compares, as tests/test_gpu_box_range_instances.py does, the product
 instance's samples and drift codes bit for bit with the oracle's, the counting
