@@ -815,6 +815,93 @@ int ipt_denoise(ipt_ctx* ctx, const ipt_denoise_params* dp, const float* pixels,
    "Denoising"; the results are the same bits). */
 int ipt_denoise_pass_ms(ipt_ctx* ctx, float ms[7]);
 
+/* ---- temporal reprojection on the GPU (ABI 7 additions) ---------------------------
+   Carries an accumulated frame across a camera move: from the previous
+   camera's planes and guide plane and the new camera's guide plane to the new
+   frame's starting planes, which ipt_render_masked_device continues as any
+   preloaded plane (entry points and one struct added; no layout change). Every
+   surface of the reference is Lambertian: what ray_power_recursive returns at
+   a surface hit does not depend on the incoming direction, so the history of a
+   point that is still visible is valid data for the new frame and only has to
+   be resampled to the new pixel grid. The definition is the one below, and the
+   kernel computes it bit for bit.
+
+   All f32 adds, multiplies and IEEE divisions, no contraction, no exp / pow /
+   sqrt; every dot product is (x*x' + y*y') + z*z'; every comparison is written
+   so that a NaN falls on the rejecting side. W = width, H = height. For each
+   destination pixel d = (xd, yd) of the new frame, g = cur_guides[d], P =
+   g.pos, n = g.normal:
+   1. (g.kind & 3) != 1 or a component of P not finite: the outputs are
+      (0, 0, 0), class "not_surface".
+   2. Projection into prev_camera (SimpleCamera::sampleRay inverted; its
+      direction need not have length 1):
+        v = P - position
+        a = v.right;  b = v.up;  c = v.direction;  dd = direction.direction
+        t = c / dd                      !(t > 0): empty (0, 0, 0), "disoccluded"
+        sx = (a / t + 0.5f) * (float)W;  fx = sx - 0.5f
+        sy = (b / t + 0.5f) * (float)H;  fy = sy - 0.5f
+        !(fx >= -1.0f && fx < (float)W) or the same of fy and H: empty,
+        "disoccluded"  (a NaN or an infinity ends here, before any conversion)
+        x0 = floorf(fx);  tx = fx - x0;  y0 = floorf(fy);  ty = fy - y0
+   3. Four taps (j, i) in {0, 1}^2, j outer: source pixel (x0 + i, y0 + j),
+      bw = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty). The tap's plane index q
+      is the destination pixel whose nominal source that source pixel is
+      (ipt_guides_device's map): source row r goes to row H-2-r for r <= H-2
+      under the Grid map (row H-1 is no pixel's nominal source and is no tap;
+      H == 1: row 0), to H-1-r with IPT_FLAG_GUI_PLANE; the column stays. A tap
+      is used iff
+        the source pixel is inside the frame and has such a q
+        (prev_guides[q].kind & 3) == 1
+        c_q = prev_counters[q] >= 2
+        prev_pixels[q] is finite
+        var_q = prev_m2[q] / (nf * (nf - 1.0f)) is finite,  nf = (float)c_q
+        n.n_q >= normal_min                       (n_q = prev_guides[q].normal)
+        fabsf(n.(P_q - P)) <= sigma_z             (P_q = prev_guides[q].pos)
+      (binary: the resampling stays a plain interpolation), and then
+        cc = min(c_q, max_count);  r = (float)c_q / (float)cc;  ve = var_q * r
+        sw += bw;  sm += bw * prev_pixels[q];  sv += (bw * bw) * ve
+        sc += bw * (float)cc
+      (the history cap: a capped pixel's variance of the mean is that of cc
+      samples, so that new samples outweigh a long history after a move).
+   4. sw == 0: empty, "disoccluded". Otherwise
+        mean = sm / sw;  var = sv / (sw * sw);  cf = sc / sw
+        c' = (uint32)cf clamped to [2, max_count];  nf' = (float)c'
+        out_pixels = mean;  out_counters = c';  out_m2 = var * (nf' * (nf' - 1.0f))
+      class "reused".
+   5. dev_stats (4 uint32, may be NULL) = {reused, disoccluded, not_surface, 0}:
+      integer sums, deterministic; the call zeroes them itself, in stream order.
+   The three classes sum to W * H. Under the Grid map row H-1 of the new frame
+   (no nominal source: its guide has kind 0xff) is "not_surface". `sums` and
+   `pixel_max` are not produced: a caller that keeps them restarts them.
+   The call always takes a whole frame (a sharded caller assembles its planes
+   first, as for the denoiser). No scratch. Stream and wait rules are
+   ipt_display_device's: queued on `hip_stream` (NULL = the context's stream),
+   no value crosses to the host, a call on another stream waits on the
+   previous post-process call's event.
+   Errors, all raised before a byte is written: a NULL that is not optional, a
+   non-positive size, sigma_z not > 0 (NaN included), a NaN normal_min,
+   max_count outside 2 .. 1 << 24, an output sharing a byte with an input or
+   with another output: IPT_E_INVALID; a flag other than IPT_FLAG_GUI_PLANE or
+   more than 2^31 pixels: IPT_E_UNSUPPORTED. */
+typedef struct ipt_reproject_params {
+    int32_t width, height;
+    uint32_t flags;         /* 0 or IPT_FLAG_GUI_PLANE: the row map of BOTH frames */
+    ipt_camera prev_camera; /* the camera the previous planes and guides were taken with */
+    float sigma_z;          /* plane distance, world units, > 0 (the denoiser's meaning) */
+    float normal_min;       /* a tap's n.n' must be >= this; any value but NaN */
+    uint32_t max_count;     /* history cap, 2 .. 1 << 24 */
+} ipt_reproject_params;
+int ipt_reproject_device(ipt_ctx* ctx, const ipt_reproject_params* rp, const float* dev_prev_pixels,
+                         const uint32_t* dev_prev_counters, const float* dev_prev_m2,
+                         const ipt_guide* dev_prev_guides, const ipt_guide* dev_cur_guides, float* dev_out_pixels,
+                         uint32_t* dev_out_counters, float* dev_out_m2, uint32_t* dev_stats /* 4, may be NULL */,
+                         void* hip_stream);
+/* Host buffers: the same kernel, synchronous. */
+int ipt_reproject(ipt_ctx* ctx, const ipt_reproject_params* rp, const float* prev_pixels,
+                  const uint32_t* prev_counters, const float* prev_m2, const ipt_guide* prev_guides,
+                  const ipt_guide* cur_guides, float* out_pixels, uint32_t* out_counters, float* out_m2,
+                  uint32_t* stats /* 4, may be NULL */);
+
 /* ---- the path's DDF samplers, exactly as the kernels evaluate them -----------
    For sampler validation (the reference's chi^2 harness, check_ddf.cpp:114-203)
    and bit-exact checks. Uses the uploaded scene. kind:

@@ -112,6 +112,16 @@ class DenoiseParams(C.Structure):  # ABI 7 additions (denoising)
 DENOISE_DEFAULTS = dict(iterations=5, sigma_l=4.0, normal_pow=5, sigma_z=0.1)
 
 
+class ReprojectParams(C.Structure):  # ABI 7 additions (temporal reprojection)
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_uint32), ("prev_camera", Camera),
+                ("sigma_z", C.c_float), ("normal_min", C.c_float), ("max_count", C.c_uint32)]
+
+
+# the reprojection's defaults (DESIGN.md "Temporal reprojection"): the denoiser's
+# plane distance, normals within about 26 degrees, a history of at most 64 samples
+REPROJECT_DEFAULTS = dict(sigma_z=0.1, normal_min=0.9, max_count=64)
+
+
 ABI_VERSION = 7  # include/ipt_capi.h IPT_ABI_VERSION
 ABI_LAYOUT_COMPATIBLE = (3, 4, 5, 6, 7)  # versions with this binding's struct layouts (IPT_ABI_COMPAT only)
 
@@ -141,6 +151,7 @@ EXPORTED_SYMBOLS = (
     "ipt_render_masked_device_async", "ipt_render_masked_device", "ipt_adapt_device", "ipt_render_adaptive",
     "ipt_last_units", "ipt_compact_plan", "ipt_last_instance",
     "ipt_guides_device", "ipt_guides", "ipt_denoise_device", "ipt_denoise", "ipt_denoise_pass_ms",
+    "ipt_reproject_device", "ipt_reproject",
 )
 
 # path-kernel phases of the IPT_PROF profile (ipt_kernels.hip IPT_PHASE ids)
@@ -249,6 +260,9 @@ def load(path: str | os.PathLike | None = None):
         lib.ipt_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)] + [C.c_void_p] * 7
         lib.ipt_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)] + [C.c_void_p] * 6
         lib.ipt_denoise_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    if hasattr(lib, "ipt_reproject_device"):  # ABI 7 additions (temporal reprojection)
+        lib.ipt_reproject_device.argtypes = [C.c_void_p, C.POINTER(ReprojectParams)] + [C.c_void_p] * 10
+        lib.ipt_reproject.argtypes = [C.c_void_p, C.POINTER(ReprojectParams)] + [C.c_void_p] * 9
     if path is None:
         _lib = lib
     return lib
@@ -336,6 +350,20 @@ def make_denoise_params(width, height, iterations=DENOISE_DEFAULTS["iterations"]
     p = DenoiseParams()
     p.width, p.height, p.iterations, p.normal_pow = width, height, iterations, normal_pow
     p.sigma_l, p.sigma_z = sigma_l, sigma_z
+    return p
+
+
+def make_reproject_params(width, height, prev_camera, flags=0, sigma_z=REPROJECT_DEFAULTS["sigma_z"],
+                          normal_min=REPROJECT_DEFAULTS["normal_min"],
+                          max_count=REPROJECT_DEFAULTS["max_count"]) -> ReprojectParams:
+    """ipt_reproject_device's parameters; prev_camera: a scene description's
+    camera dict (position, direction, right, up), the one the previous planes
+    and guides were taken with; flags: 0 or IPT_FLAG_GUI_PLANE (both frames')."""
+    p = ReprojectParams()
+    p.width, p.height, p.flags, p.max_count = width, height, flags, max_count
+    p.sigma_z, p.normal_min = sigma_z, normal_min
+    for k in ("position", "direction", "right", "up"):
+        getattr(p.prev_camera, k)[:] = prev_camera[k]
     return p
 
 
@@ -527,6 +555,36 @@ class Context:
                                                       mm.ctypes.data, gd.ctypes.data, out.ctypes.data,
                                                       vo.ctypes.data if var else None))
         return out, vo
+
+    def reproject_device(self, rp: ReprojectParams, prev_pixels_ptr, prev_counters_ptr, prev_m2_ptr, prev_guides_ptr,
+                         cur_guides_ptr, out_pixels_ptr, out_counters_ptr, out_m2_ptr, stats_ptr=None, stream=None):
+        """Queue ipt_reproject_device: the previous camera's planes resampled
+        to the new frame (float32, uint32, float32 [H][W] at the out pointers)
+        and {reused, disoccluded, not_surface, 0} (uint32) at stats_ptr.
+        Complete on `stream`'s order or after wait()."""
+        _check(self.lib, self.h, self.lib.ipt_reproject_device(
+            self.h, C.byref(rp), prev_pixels_ptr, prev_counters_ptr, prev_m2_ptr, prev_guides_ptr, cur_guides_ptr,
+            out_pixels_ptr, out_counters_ptr, out_m2_ptr, stats_ptr, stream))
+
+    def reproject(self, rp: ReprojectParams, prev_pixels, prev_counters, prev_m2, prev_guides, cur_guides):
+        """Host-buffer reprojection (ipt_reproject): (pixels float32, counters
+        uint32, m2 float32, each [H*W], {reused, disoccluded, not_surface});
+        the guides are GuideRecord arrays."""
+        px = np.ascontiguousarray(prev_pixels, np.float32).reshape(-1)
+        cn = np.ascontiguousarray(prev_counters, np.uint32).reshape(-1)
+        mm = np.ascontiguousarray(prev_m2, np.float32).reshape(-1)
+        pg = np.ascontiguousarray(prev_guides, GuideRecord).reshape(-1)
+        cg = np.ascontiguousarray(cur_guides, GuideRecord).reshape(-1)
+        n = rp.width * rp.height
+        for a in (px, cn, mm, pg, cg):
+            if a.size < n:
+                raise ValueError("a buffer holds fewer than width * height elements")
+        opx, ocn, om2 = np.empty(max(n, 0), np.float32), np.empty(max(n, 0), np.uint32), np.empty(max(n, 0), np.float32)
+        st = np.zeros(4, np.uint32)
+        _check(self.lib, self.h, self.lib.ipt_reproject(
+            self.h, C.byref(rp), px.ctypes.data, cn.ctypes.data, mm.ctypes.data, pg.ctypes.data, cg.ctypes.data,
+            opx.ctypes.data, ocn.ctypes.data, om2.ctypes.data, st.ctypes.data))
+        return opx, ocn, om2, {"reused": int(st[0]), "disoccluded": int(st[1]), "not_surface": int(st[2])}
 
     def wait(self):
         _check(self.lib, self.h, self.lib.ipt_render_wait(self.h))

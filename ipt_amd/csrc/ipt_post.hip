@@ -664,6 +664,129 @@ __global__ __launch_bounds__(kPostBlock) void adapt_kernel(const float* __restri
     }
 }
 
+// ipt_reproject_device: the previous camera's planes resampled to the new
+// frame's pixels (ipt_capi.h "temporal reprojection"), one thread per
+// destination pixel, in f32 and with no contraction. A thread reads its own
+// guide, projects its hit into the previous camera and gathers up to four
+// taps of a guide and three plane values each; every tap's loads are issued
+// before the first acceptance test (a tap outside the frame reads the
+// thread's own pixel and is dropped), so that the four gathers are in flight
+// together. One dword per load and store: the caller's planes may have any
+// alignment a float has. stats = {reused, disoccluded, not_surface, 0}, added
+// per wave by ballot as adapt_kernel's.
+struct RpArgs {
+    const float* pixels;
+    const uint32_t* counters;
+    const float* m2;
+    const uint32_t* prev_guides;
+    const uint32_t* cur_guides;
+    float* out_pixels;
+    uint32_t* out_counters;
+    float* out_m2;
+    uint32_t* stats;
+    float pos[3], dir[3], right[3], up[3];  // the previous camera
+    int W, H, gui;
+    float sigma_z, normal_min;
+    uint32_t max_count;
+    long long n;
+};
+
+__device__ __forceinline__ float rp_dot_(float ax, float ay, float az, float bx, float by, float bz) {
+    return (ax * bx + ay * by) + az * bz;
+}
+
+__global__ __launch_bounds__(kPostBlock) void reproject_kernel(const RpArgs r) {
+    const long long i = (long long)blockIdx.x * kPostBlock + threadIdx.x;
+    bool reused = false, disoccluded = false, not_surface = false;
+    if (i < r.n) {
+        const uint32_t* g = r.cur_guides + 8 * i;
+        const float Px = u2f(g[0]), Py = u2f(g[1]), Pz = u2f(g[2]);
+        const uint32_t kind = g[3];
+        const float nx = u2f(g[4]), ny = u2f(g[5]), nz = u2f(g[6]);
+        float mean = 0.0f, m2o = 0.0f;
+        uint32_t co = 0;
+        if ((kind & 3u) != 1u || !isfinite_(Px) || !isfinite_(Py) || !isfinite_(Pz)) {
+            not_surface = true;
+        } else {
+            disoccluded = true;
+            const int W = r.W, H = r.H;
+            const float vx = Px - r.pos[0], vy = Py - r.pos[1], vz = Pz - r.pos[2];
+            const float a = rp_dot_(vx, vy, vz, r.right[0], r.right[1], r.right[2]);
+            const float b = rp_dot_(vx, vy, vz, r.up[0], r.up[1], r.up[2]);
+            const float c = rp_dot_(vx, vy, vz, r.dir[0], r.dir[1], r.dir[2]);
+            const float dd = rp_dot_(r.dir[0], r.dir[1], r.dir[2], r.dir[0], r.dir[1], r.dir[2]);
+            const float t = div_(c, dd);
+            const float fx = (div_(a, t) + 0.5f) * (float)W - 0.5f;
+            const float fy = (div_(b, t) + 0.5f) * (float)H - 0.5f;
+            if (t > 0.0f && fx >= -1.0f && fx < (float)W && fy >= -1.0f && fy < (float)H) {
+                const float x0f = floorf(fx), y0f = floorf(fy);
+                const float tx = fx - x0f, ty = fy - y0f;
+                const int x0 = (int)x0f, y0 = (int)y0f;
+                // the loads of all four taps, then the tests and the sums in tap order
+                bool in[4];
+                uint32_t kq[4], cq[4];
+                float pq[4], mq[4], qp[4][3], qn[4][3];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int xs = x0 + (k & 1), rs = y0 + (k >> 1);
+                    // the destination row whose nominal source row rs is (-1: none)
+                    const int yq = (rs < 0 || rs >= H) ? -1
+                                   : (r.gui ? H - 1 - rs : (H == 1 ? 0 : (rs <= H - 2 ? H - 2 - rs : -1)));
+                    in[k] = yq >= 0 && xs >= 0 && xs < W;
+                    const long long q = in[k] ? (long long)yq * W + xs : i;
+                    const uint32_t* gq = r.prev_guides + 8 * q;
+                    qp[k][0] = u2f(gq[0]); qp[k][1] = u2f(gq[1]); qp[k][2] = u2f(gq[2]);
+                    kq[k] = gq[3];
+                    qn[k][0] = u2f(gq[4]); qn[k][1] = u2f(gq[5]); qn[k][2] = u2f(gq[6]);
+                    cq[k] = r.counters[q];
+                    pq[k] = r.pixels[q];
+                    mq[k] = r.m2[q];
+                }
+                float sw = 0.0f, sm = 0.0f, sv = 0.0f, sc = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float bw = ((k & 1) ? tx : 1.0f - tx) * ((k >> 1) ? ty : 1.0f - ty);
+                    const float nf = (float)cq[k];
+                    const float var = div_(mq[k], nf * (nf - 1.0f));
+                    const float dn = rp_dot_(nx, ny, nz, qn[k][0], qn[k][1], qn[k][2]);
+                    const float e = fabs_(rp_dot_(nx, ny, nz, qp[k][0] - Px, qp[k][1] - Py, qp[k][2] - Pz));
+                    const bool ok = in[k] && (kq[k] & 3u) == 1u && cq[k] >= 2u && isfinite_(pq[k]) &&
+                                    isfinite_(var) && dn >= r.normal_min && e <= r.sigma_z;
+                    if (ok) {
+                        const uint32_t cc = cq[k] < r.max_count ? cq[k] : r.max_count;
+                        const float ccf = (float)cc;
+                        const float ve = var * div_(nf, ccf);
+                        sw += bw;
+                        sm += bw * pq[k];
+                        sv += (bw * bw) * ve;
+                        sc += bw * ccf;
+                    }
+                }
+                if (sw != 0.0f) {
+                    mean = div_(sm, sw);
+                    const float var = div_(sv, sw * sw);
+                    const uint32_t cu = (uint32_t)div_(sc, sw);
+                    co = cu < 2u ? 2u : (cu > r.max_count ? r.max_count : cu);
+                    const float nf = (float)co;
+                    m2o = var * (nf * (nf - 1.0f));
+                    reused = true;
+                    disoccluded = false;
+                }
+            }
+        }
+        r.out_pixels[i] = mean;
+        r.out_counters[i] = co;
+        r.out_m2[i] = m2o;
+    }
+    if (r.stats) {
+        const bool cls[3] = {reused, disoccluded, not_surface};
+        for (int k = 0; k < 3; ++k) {
+            const unsigned int c = (unsigned int)__popcll(__ballot(cls[k]));
+            if ((threadIdx.x & 63) == 0 && c) atomicAdd(&r.stats[k], c);
+        }
+    }
+}
+
 // ------------------------------------------------------------------ denoising
 // ipt_guides_device's second half: the FULL preview kernel's per-sample kinds
 // and hits of one pass, [H][W] in source order, into the guide plane in
@@ -1037,6 +1160,27 @@ int denoise_check(ipt_ctx* ctx, const ipt_denoise_params* p, const float* pixels
     const size_t len[6] = {n * 4, n * 4, n * 4, n * sizeof(ipt_guide), n * 4, n * 4};
     if (any_overlap(buf, len, 6, 4))  // every pair with an output in it
         return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_denoise: an output overlaps another buffer");
+    return IPT_OK;
+}
+
+// the argument rules of ipt_reproject / ipt_reproject_device (ipt_capi.h)
+int reproject_check(ipt_ctx* ctx, const ipt_reproject_params* p, const float* pixels, const uint32_t* counters,
+                    const float* m2, const ipt_guide* prev_guides, const ipt_guide* cur_guides, const float* out_pixels,
+                    const uint32_t* out_counters, const float* out_m2, const uint32_t* stats) {
+    if (!ctx) return IPT_E_INVALID;
+    if (!p || !pixels || !counters || !m2 || !prev_guides || !cur_guides || !out_pixels || !out_counters || !out_m2 ||
+        p->width <= 0 || p->height <= 0 || !(p->sigma_z > 0.0f) || p->normal_min != p->normal_min ||
+        p->max_count < 2u || p->max_count > (1u << 24))
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID,
+                                      "ipt_reproject: bad arguments (sigma_z > 0, normal_min no NaN, max_count 2..1<<24)");
+    if ((p->flags & ~(uint32_t)IPT_FLAG_GUI_PLANE) != 0 || (long long)p->width * p->height > (1ll << 31))
+        return ipt_internal::ctx_fail(ctx, IPT_E_UNSUPPORTED,
+                                      "ipt_reproject: IPT_FLAG_GUI_PLANE alone, at most 2^31 pixels");
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    const void* buf[9] = {pixels, counters, m2, prev_guides, cur_guides, out_pixels, out_counters, out_m2, stats};
+    const size_t len[9] = {n * 4, n * 4, n * 4, n * sizeof(ipt_guide), n * sizeof(ipt_guide), n * 4, n * 4, n * 4, 16};
+    if (any_overlap(buf, len, 9, 5))  // every pair with an output in it
+        return ipt_internal::ctx_fail(ctx, IPT_E_INVALID, "ipt_reproject: an output overlaps another buffer");
     return IPT_OK;
 }
 
@@ -1504,6 +1648,66 @@ int ipt_adapt_device(ipt_ctx* ctx, const ipt_adapt_params* p, const float* dev_p
     hipLaunchKernelGGL(adapt_kernel, dim3(blocks_for(n)), dim3(kPostBlock), 0, st, dev_pixels, dev_counters, dev_m2,
                        dev_mask, n, no_source, p->min_count, p->rel_tol, p->abs_tol, dev_stats);
     return post_queued(ctx, st);
+}
+
+int ipt_reproject_device(ipt_ctx* ctx, const ipt_reproject_params* p, const float* dev_prev_pixels,
+                         const uint32_t* dev_prev_counters, const float* dev_prev_m2, const ipt_guide* dev_prev_guides,
+                         const ipt_guide* dev_cur_guides, float* dev_out_pixels, uint32_t* dev_out_counters,
+                         float* dev_out_m2, uint32_t* dev_stats, void* hip_stream) {
+    if (const int rc = reproject_check(ctx, p, dev_prev_pixels, dev_prev_counters, dev_prev_m2, dev_prev_guides,
+                                       dev_cur_guides, dev_out_pixels, dev_out_counters, dev_out_m2, dev_stats))
+        return rc;
+    // (no scratch of its own: the event alone, so that the context's waits cover the call)
+    hipStream_t st;
+    if (const int rc = post_begin(ctx, hip_stream, PostNeeds{}, &st)) return rc;
+    RpArgs a{};
+    a.pixels = dev_prev_pixels;
+    a.counters = dev_prev_counters;
+    a.m2 = dev_prev_m2;
+    a.prev_guides = reinterpret_cast<const uint32_t*>(dev_prev_guides);
+    a.cur_guides = reinterpret_cast<const uint32_t*>(dev_cur_guides);
+    a.out_pixels = dev_out_pixels;
+    a.out_counters = dev_out_counters;
+    a.out_m2 = dev_out_m2;
+    a.stats = dev_stats;
+    for (int k = 0; k < 3; ++k) {
+        a.pos[k] = p->prev_camera.position[k];
+        a.dir[k] = p->prev_camera.direction[k];
+        a.right[k] = p->prev_camera.right[k];
+        a.up[k] = p->prev_camera.up[k];
+    }
+    a.W = p->width;
+    a.H = p->height;
+    a.gui = (p->flags & IPT_FLAG_GUI_PLANE) != 0 ? 1 : 0;
+    a.sigma_z = p->sigma_z;
+    a.normal_min = p->normal_min;
+    a.max_count = p->max_count;
+    a.n = (long long)p->width * p->height;
+    if (dev_stats) POSTCHECK(ctx, hipMemsetAsync(dev_stats, 0, 4 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(reproject_kernel, dim3(blocks_for(a.n)), dim3(kPostBlock), 0, st, a);
+    return post_queued(ctx, st);
+}
+
+int ipt_reproject(ipt_ctx* ctx, const ipt_reproject_params* p, const float* prev_pixels, const uint32_t* prev_counters,
+                  const float* prev_m2, const ipt_guide* prev_guides, const ipt_guide* cur_guides, float* out_pixels,
+                  uint32_t* out_counters, float* out_m2, uint32_t* stats) {
+    if (const int rc = reproject_check(ctx, p, prev_pixels, prev_counters, prev_m2, prev_guides, cur_guides, out_pixels,
+                                       out_counters, out_m2, stats))
+        return rc;
+    const size_t n = (size_t)p->width * p->height;
+    HostStage hs(ctx);
+    const float* dpx = hs.in(prev_pixels, n);
+    const uint32_t* dcnt = hs.in(prev_counters, n);
+    const float* dm2 = hs.in(prev_m2, n);
+    const ipt_guide* dpg = hs.in(prev_guides, n);
+    const ipt_guide* dcg = hs.in(cur_guides, n);
+    float* dopx = hs.out(out_pixels, n);
+    uint32_t* docnt = hs.out(out_counters, n);
+    float* dom2 = hs.out(out_m2, n);
+    uint32_t* dst = hs.out(stats, 4);
+    if (hs.rc) return hs.rc;
+    if (const int rc = ipt_reproject_device(ctx, p, dpx, dcnt, dm2, dpg, dcg, dopx, docnt, dom2, dst, hs.st)) return rc;
+    return hs.finish();
 }
 
 int ipt_denoise_device(ipt_ctx* ctx, const ipt_denoise_params* p, const float* dev_pixels, const uint32_t* dev_counters,

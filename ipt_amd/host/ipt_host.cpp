@@ -472,7 +472,7 @@ void GpuRenderer::render(GridRenderPlane& plane, const RenderParams& p) {
 
 namespace {
 AdaptResult run_adaptive(ipt_ctx* ctx, ipt_image img, size_t W, size_t H, const RenderParams& p, const AdaptParams& a,
-                         uint32_t flags) {
+                         uint32_t flags, const std::vector<float>* m2_in) {
     const ipt_params q = to_params(W, H, p, flags);
     ipt_adapt_params ap{};
     ap.width = (int)W;
@@ -483,7 +483,10 @@ AdaptResult run_adaptive(ipt_ctx* ctx, ipt_image img, size_t W, size_t H, const 
     ap.flags = flags & IPT_FLAG_GUI_PLANE;
     AdaptResult r;
     r.mask.assign(W * H, 0);
-    r.m2.assign(W * H, 0.0f);
+    if (m2_in && m2_in->size() != W * H)
+        throw IptError(IPT_E_INVALID, "render_adaptive: m2_in must hold width*height elements");
+    if (m2_in) r.m2 = *m2_in;
+    else r.m2.assign(W * H, 0.0f);
     uint32_t st[4] = {0, 0, 0, 0};
     check(ctx, ipt_render_adaptive(ctx, &q, &ap, a.round_spp, &img, r.m2.data(), r.mask.data(), st));
     r.active = st[0];
@@ -494,18 +497,21 @@ AdaptResult run_adaptive(ipt_ctx* ctx, ipt_image img, size_t W, size_t H, const 
 }
 }  // namespace
 
-AdaptResult GpuRenderer::render_adaptive(GridRenderPlane& plane, const RenderParams& p, const AdaptParams& a) {
+AdaptResult GpuRenderer::render_adaptive(GridRenderPlane& plane, const RenderParams& p, const AdaptParams& a,
+                                         const std::vector<float>* m2_in) {
     check_plane(plane);
     PlaneIo io(plane, 2 * p.spp);  // (row 0 takes two samples per pass)
-    const AdaptResult r = run_adaptive(ctx_, io.image(plane.pixels), plane.width, plane.height, p, a, 0);
+    const AdaptResult r = run_adaptive(ctx_, io.image(plane.pixels), plane.width, plane.height, p, a, 0, m2_in);
     io.finish(plane);
     return r;
 }
 
-AdaptResult GpuRenderer::render_adaptive(GuiRenderPlane& plane, const RenderParams& p, const AdaptParams& a) {
+AdaptResult GpuRenderer::render_adaptive(GuiRenderPlane& plane, const RenderParams& p, const AdaptParams& a,
+                                         const std::vector<float>* m2_in) {
     check_plane(plane);
     PlaneIo io(plane, p.spp);
-    const AdaptResult r = run_adaptive(ctx_, io.image(plane.pixels), plane.width, plane.height, p, a, IPT_FLAG_GUI_PLANE);
+    const AdaptResult r =
+        run_adaptive(ctx_, io.image(plane.pixels), plane.width, plane.height, p, a, IPT_FLAG_GUI_PLANE, m2_in);
     io.finish(plane);
     return r;
 }
@@ -540,12 +546,73 @@ std::vector<float> run_denoise(ipt_ctx* ctx, const std::vector<float>& pixels, c
 }
 }  // namespace
 
-std::vector<float> GpuRenderer::render_m2(GridRenderPlane& plane, const RenderParams& p) {
-    return render_adaptive(plane, p, one_round(p)).m2;
+std::vector<float> GpuRenderer::render_m2(GridRenderPlane& plane, const RenderParams& p,
+                                          const std::vector<float>* m2_in) {
+    return render_adaptive(plane, p, one_round(p), m2_in).m2;
 }
 
-std::vector<float> GpuRenderer::render_m2(GuiRenderPlane& plane, const RenderParams& p) {
-    return render_adaptive(plane, p, one_round(p)).m2;
+std::vector<float> GpuRenderer::render_m2(GuiRenderPlane& plane, const RenderParams& p,
+                                          const std::vector<float>* m2_in) {
+    return render_adaptive(plane, p, one_round(p), m2_in).m2;
+}
+
+namespace {
+ReprojectResult run_reproject(ipt_ctx* ctx, std::vector<float>& pixels, std::vector<size_t>& counters, size_t W,
+                              size_t H, const std::vector<float>& m2, const std::vector<ipt_guide>& prev_guides,
+                              const std::vector<ipt_guide>& cur_guides, const SimpleCamera& cam,
+                              const ReprojectParams& rp, uint32_t flags) {
+    const size_t n = W * H;
+    if (m2.size() != n || prev_guides.size() != n || cur_guides.size() != n)
+        throw IptError(IPT_E_INVALID, "reproject: m2 and both guide planes must hold width*height elements");
+    std::vector<uint32_t> cnt(n), out_cnt(n);
+    for (size_t i = 0; i < n; ++i) cnt[i] = counters[i] > 0xffffffffull ? 0xffffffffu : (uint32_t)counters[i];
+    ipt_reproject_params q{};
+    q.width = (int32_t)W;
+    q.height = (int32_t)H;
+    q.flags = flags;
+    const vec3f* cs[4] = {&cam.position, &cam.direction, &cam.right, &cam.up};
+    float* cd[4] = {q.prev_camera.position, q.prev_camera.direction, q.prev_camera.right, q.prev_camera.up};
+    for (int k = 0; k < 4; ++k) {
+        cd[k][0] = cs[k]->x;
+        cd[k][1] = cs[k]->y;
+        cd[k][2] = cs[k]->z;
+    }
+    q.sigma_z = rp.sigma_z;
+    q.normal_min = rp.normal_min;
+    q.max_count = rp.max_count;
+    ReprojectResult r;
+    r.m2.assign(n, 0.0f);
+    std::vector<float> out(n);
+    uint32_t st[4] = {0, 0, 0, 0};
+    check(ctx, ipt_reproject(ctx, &q, pixels.data(), cnt.data(), m2.data(), prev_guides.data(), cur_guides.data(),
+                             out.data(), out_cnt.data(), r.m2.data(), st));
+    pixels = std::move(out);
+    for (size_t i = 0; i < n; ++i) counters[i] = out_cnt[i];
+    r.reused = st[0];
+    r.disoccluded = st[1];
+    r.not_surface = st[2];
+    return r;
+}
+}  // namespace
+
+ReprojectResult GpuRenderer::reproject(GridRenderPlane& plane, const std::vector<float>& m2,
+                                       const std::vector<ipt_guide>& prev_guides,
+                                       const std::vector<ipt_guide>& cur_guides, const SimpleCamera& prev_camera,
+                                       const ReprojectParams& rp) {
+    check_plane(plane);
+    ReprojectResult r = run_reproject(ctx_, plane.pixels, plane.pixel_counters, plane.width, plane.height, m2,
+                                      prev_guides, cur_guides, prev_camera, rp, 0);
+    plane.max_value = 0;
+    return r;
+}
+
+ReprojectResult GpuRenderer::reproject(GuiRenderPlane& plane, const std::vector<float>& m2,
+                                       const std::vector<ipt_guide>& prev_guides,
+                                       const std::vector<ipt_guide>& cur_guides, const SimpleCamera& prev_camera,
+                                       const ReprojectParams& rp) {
+    check_plane(plane);
+    return run_reproject(ctx_, plane.pixels, plane.value_counter, plane.width, plane.height, m2, prev_guides, cur_guides,
+                         prev_camera, rp, IPT_FLAG_GUI_PLANE);
 }
 
 std::vector<ipt_guide> GpuRenderer::guides(size_t width, size_t height, const RenderParams& p, bool gui_plane) {

@@ -252,6 +252,20 @@ struct AdaptResult {
     std::vector<float> m2;                      // the second-moment plane
 };
 
+// Temporal reprojection (ipt_reproject): which history a tap may carry over --
+// within sigma_z world units of the new hit's plane, its normal within
+// normal_min of the new one (a dot product), at most max_count samples'
+// weight -- and what the call returns besides the plane.
+struct ReprojectParams {
+    float sigma_z = 0.1f;
+    float normal_min = 0.9f;
+    uint32_t max_count = 64;  // 2 .. 1 << 24
+};
+struct ReprojectResult {
+    uint32_t reused = 0, disoccluded = 0, not_surface = 0;  // ipt_reproject's stats
+    std::vector<float> m2;                                  // the new frame's second-moment plane
+};
+
 class GpuRenderer {
    public:
     explicit GpuRenderer(int device = 0);
@@ -267,8 +281,12 @@ class GpuRenderer {
     // mask on the device, until no pixel is active (ipt_render_adaptive; one
     // device, whole frame: p.n_shards > 1 throws IPT_E_UNSUPPORTED). The plane
     // is continued as render() continues it; the second moments start at zero.
-    AdaptResult render_adaptive(GridRenderPlane& plane, const RenderParams& p, const AdaptParams& a);
-    AdaptResult render_adaptive(GuiRenderPlane& plane, const RenderParams& p, const AdaptParams& a);
+    // m2_in (width*height, e.g. ReprojectResult::m2): the second moments the
+    // plane comes with, continued like the plane.
+    AdaptResult render_adaptive(GridRenderPlane& plane, const RenderParams& p, const AdaptParams& a,
+                                const std::vector<float>* m2_in = nullptr);
+    AdaptResult render_adaptive(GuiRenderPlane& plane, const RenderParams& p, const AdaptParams& a,
+                                const std::vector<float>* m2_in = nullptr);
     // p.spp unmasked passes through the masked entry point, which keeps the
     // second moments the filter below needs (one round of ipt_render_adaptive:
     // round 0 traces every pixel; this layer holds host buffers only and
@@ -276,8 +294,22 @@ class GpuRenderer {
     // masked entry point. It also runs one ipt_adapt_device pass whose mask
     // is dropped). Returns m2; the plane is continued as render() continues
     // it, bit for bit.
-    std::vector<float> render_m2(GridRenderPlane& plane, const RenderParams& p);
-    std::vector<float> render_m2(GuiRenderPlane& plane, const RenderParams& p);
+    std::vector<float> render_m2(GridRenderPlane& plane, const RenderParams& p,
+                                 const std::vector<float>* m2_in = nullptr);
+    std::vector<float> render_m2(GuiRenderPlane& plane, const RenderParams& p,
+                                 const std::vector<float>* m2_in = nullptr);
+    // The plane carried across a camera move (ipt_reproject): on entry the
+    // plane, m2 and prev_guides are the previous camera's, cur_guides the new
+    // camera's (guides() after upload() of the new scene); on return the plane
+    // holds the new frame's starting mean and counters (zeros where nothing
+    // could be reused) and the result its m2, for render_m2 / render_adaptive
+    // to continue. A GridRenderPlane's max_value restarts at 0.
+    ReprojectResult reproject(GridRenderPlane& plane, const std::vector<float>& m2,
+                              const std::vector<ipt_guide>& prev_guides, const std::vector<ipt_guide>& cur_guides,
+                              const SimpleCamera& prev_camera, const ReprojectParams& rp = ReprojectParams());
+    ReprojectResult reproject(GuiRenderPlane& plane, const std::vector<float>& m2,
+                              const std::vector<ipt_guide>& prev_guides, const std::vector<ipt_guide>& cur_guides,
+                              const SimpleCamera& prev_camera, const ReprojectParams& rp = ReprojectParams());
     // the guide plane (ipt_guides): the first hit of pass p.spp_offset's preview
     // sample per destination pixel, [height][width], under the Grid row map or,
     // with gui_plane, the Gui's

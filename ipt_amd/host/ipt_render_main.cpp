@@ -17,7 +17,20 @@
 //              [--histogram hist.txt [--hist-buckets 400]]
 //              [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]
 //              [--denoise K [--denoise-sigma L,N,Z]]
+//              [--reproject-from DX,DY,DZ[:SPP] [--reproject-sigma Z,NMIN,CAP]]
 //
+// --reproject-from DX,DY,DZ[:SPP] carries a frame across a camera move
+// (GpuRenderer::reproject, ipt_capi.h "temporal reprojection"): SPP passes
+// (default --spp) are rendered, with their second moments, from the scene's
+// camera displaced by (DX, DY, DZ), and that camera's guide plane is taken;
+// then the scene's own camera is uploaded, its guide plane taken, the planes
+// reprojected to it, and the render continues with --spp passes from pass SPP
+// on. --reproject-sigma Z,NMIN,CAP sets the plane distance in world units
+// (0.1), the least dot product of the two normals (0.9) and the history cap in
+// samples (64). It composes with --gui-plane, --adaptive, --denoise,
+// --gpu-display, --pgm and every output option; one device, one batch
+// (--passes 1), not with --preview. The JSON line then carries
+// "reproject_reused", "reproject_disoccluded" and "reproject_not_surface".
 // --denoise K filters the rendered plane with K iterations (1..6) of the guided
 // a-trous filter (GpuRenderer::denoise, ipt_capi.h "denoising"; iteration k
 // taps at step 1 << k) before every output stage: --smooth, --glare, --pgm,
@@ -99,7 +112,8 @@ namespace {
                  "                  [--compact]\n"
                  "                  [--histogram hist.txt [--hist-buckets 400]]\n"
                  "                  [--adaptive REL [--adaptive-abs A] [--min-spp N] [--round-spp R]]\n"
-                 "                  [--denoise K [--denoise-sigma L,N,Z]]\n");
+                 "                  [--denoise K [--denoise-sigma L,N,Z]]\n"
+                 "                  [--reproject-from DX,DY,DZ[:SPP] [--reproject-sigma Z,NMIN,CAP]]\n");
     std::exit(2);
 }
 }  // namespace
@@ -113,6 +127,9 @@ int main(int argc, char** argv) {
     double glare = -1.0, adaptive_rel = -1.0, adaptive_abs = 1e-3;
     long min_spp = 8, round_spp = 4, denoise = 0, denoise_pow = 5;
     double denoise_l = 4.0, denoise_z = 0.1;
+    bool reproject = false;
+    double from[3] = {0.0, 0.0, 0.0}, reproject_z = 0.1, reproject_nmin = 0.9;
+    long reproject_spp = 0, reproject_cap = 64;
     long width = 640, height = 640, spp = 16, passes = 1, n_rays = 16, depth = 8, device = 0, tile_rows = 16;
     std::vector<int> devices;
     unsigned long long seed = 20241223ull;
@@ -163,6 +180,14 @@ int main(int argc, char** argv) {
             if (std::sscanf(val(), "%lf,%ld,%lf", &denoise_l, &denoise_pow, &denoise_z) != 3)
                 usage("--denoise-sigma takes L,N,Z");
         }
+        else if (a == "--reproject-from") {
+            const int got = std::sscanf(val(), "%lf,%lf,%lf:%ld", &from[0], &from[1], &from[2], &reproject_spp);
+            if (got < 3 || (got == 4 && reproject_spp <= 0)) usage("--reproject-from takes DX,DY,DZ[:SPP], SPP >= 1");
+            reproject = true;
+        } else if (a == "--reproject-sigma") {
+            if (std::sscanf(val(), "%lf,%lf,%ld", &reproject_z, &reproject_nmin, &reproject_cap) != 3)
+                usage("--reproject-sigma takes Z,NMIN,CAP");
+        }
         else usage(("unknown option " + a).c_str());
     }
     if (width <= 0 || height <= 0 || spp <= 0 || passes <= 0 || n_rays < 0 || depth < 0) usage("bad sizes");
@@ -181,6 +206,12 @@ int main(int argc, char** argv) {
     if (denoise > 0 && (passes != 1 || devices.size() > 1)) usage("--denoise filters one batch on one device");
     if (denoise > 0 && (!(denoise_l > 0.0) || !(denoise_z > 0.0) || denoise_pow < 0 || denoise_pow > 7))
         usage("--denoise-sigma: L > 0, N in 0..7, Z > 0");
+    if (reproject && (passes != 1 || devices.size() > 1)) usage("--reproject-from carries one batch on one device");
+    if (reproject && preview) usage("--reproject-from continues the full estimator's plane; not with --preview");
+    if (reproject && (!(reproject_z > 0.0) || reproject_nmin != reproject_nmin || reproject_cap < 2 ||
+                      reproject_cap > (1l << 24)))
+        usage("--reproject-sigma: Z > 0, NMIN a number, CAP in 2..16777216");
+    if (reproject && reproject_spp == 0) reproject_spp = spp;
     try {
         const ipt::Scene scene = ipt::make_scene_by_name(scene_name);
         if (devices.empty()) devices.push_back((int)device);
@@ -206,19 +237,47 @@ int main(int argc, char** argv) {
         std::vector<float> m2;
         double kernel_ms = 0.0;
         ipt::AdaptResult ar;
+        ipt::ReprojectResult rr;
         const auto t0 = std::chrono::steady_clock::now();
+        if (reproject) {
+            // the history: reproject_spp passes from the displaced camera, and its guides
+            const auto cam = std::dynamic_pointer_cast<const ipt::SimpleCamera>(scene.camera);
+            if (!cam) throw ipt::IptError(IPT_E_UNSUPPORTED, "--reproject-from needs a SimpleCamera");
+            const auto moved = std::make_shared<ipt::SimpleCamera>(*cam);
+            moved->position = ipt::vec3f{cam->position.x + (float)from[0], cam->position.y + (float)from[1],
+                                         cam->position.z + (float)from[2]};
+            ipt::Scene prev_scene = scene;
+            prev_scene.camera = moved;
+            gpus.upload(prev_scene);
+            ipt::RenderParams hp = p;
+            hp.spp = (int)reproject_spp;
+            m2 = gui_plane ? gpu.render_m2(gui, hp) : gpu.render_m2(plane, hp);
+            const std::vector<ipt_guide> prev_guides = gpu.guides((size_t)width, (size_t)height, hp, gui_plane);
+            // the new camera: its guides, the planes resampled to it, and the render goes on from pass reproject_spp
+            gpus.upload(scene);
+            const std::vector<ipt_guide> cur_guides = gpu.guides((size_t)width, (size_t)height, hp, gui_plane);
+            ipt::ReprojectParams rp;
+            rp.sigma_z = (float)reproject_z;
+            rp.normal_min = (float)reproject_nmin;
+            rp.max_count = (uint32_t)reproject_cap;
+            rr = gui_plane ? gpu.reproject(gui, m2, prev_guides, cur_guides, *moved, rp)
+                           : gpu.reproject(plane, m2, prev_guides, cur_guides, *moved, rp);
+            m2 = rr.m2;
+            p.spp_offset = (int)reproject_spp;
+        }
+        const std::vector<float>* m2_in = reproject ? &m2 : nullptr;
         if (adaptive) {
             ipt::AdaptParams ad;
             ad.rel_tol = (float)adaptive_rel;
             ad.abs_tol = (float)adaptive_abs;
             ad.min_count = (int)min_spp;
             ad.round_spp = (int)round_spp;
-            ar = gui_plane ? gpu.render_adaptive(gui, p, ad) : gpu.render_adaptive(plane, p, ad);
+            ar = gui_plane ? gpu.render_adaptive(gui, p, ad, m2_in) : gpu.render_adaptive(plane, p, ad, m2_in);
             m2 = ar.m2;
-        } else if (denoise > 0) {
-            m2 = gui_plane ? gpu.render_m2(gui, p) : gpu.render_m2(plane, p);
+        } else if (denoise > 0 || reproject) {
+            m2 = gui_plane ? gpu.render_m2(gui, p, m2_in) : gpu.render_m2(plane, p, m2_in);
         }
-        for (long pass = 0; pass < passes && !adaptive && denoise == 0; ++pass) {  // progressive: each batch continues the RNG stream
+        for (long pass = 0; pass < passes && !adaptive && denoise == 0 && !reproject; ++pass) {  // progressive: each batch continues the RNG stream
             p.spp_offset = (int)(pass * spp);
             if (gui_plane) gpus.render(gui, p);
             else gpus.render(plane, p);
@@ -283,6 +342,9 @@ int main(int argc, char** argv) {
             paths / secs / 1e6, kernel_ms > 0 ? paths / (kernel_ms * 1e-3) / 1e6 : 0.0, (unsigned long long)h2d,
             (unsigned long long)d2h, gui_plane ? "gui" : "grid");
         if (adaptive) std::printf(", \"adaptive_passes\": %d, \"adaptive_active\": %u", ar.passes, ar.active);
+        if (reproject)
+            std::printf(", \"reproject_reused\": %u, \"reproject_disoccluded\": %u, \"reproject_not_surface\": %u",
+                        rr.reused, rr.disoccluded, rr.not_surface);
         std::printf("}\n");
     } catch (const ipt::IptError& e) {
         std::fprintf(stderr, "ipt_render: error %d: %s\n", e.code, e.what());
