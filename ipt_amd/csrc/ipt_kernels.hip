@@ -920,6 +920,13 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
     // conditional expressions on kK at each use: the other instances keep
     // their code, and their register assignment, as it was)
     constexpr int kTreeRays = 1 << kK, kTreeMetaShift = kTreeRays > 255 ? 16 : 8;
+    // the product FIXED = K instances also take a fact of the scene's lights as
+    // the launch's (kp.no_fallthrough, checked by select_path4; DESIGN.md
+    // 4.19): no draw word falls through the pick (cdf[nl] >= 1),
+    // so a pick is a light or the surface and every pick word stands for three
+    // draws. The counting instances keep the general code, and so do the
+    // lattices with global records (no_fallthrough_mode, ipt_kparams.h).
+    constexpr bool kFactPick = kK > 0 && !COUNT && no_fallthrough_mode(LMODE);
     constexpr int kRange = GEOM == IPT_GEOM_SPHERE_IN_BOX ? (BOXIN ? kRangeIn : kRangeGeneric) : kRangeRuntime;
     // the generic box instances keep the full-form trace (small, rarely run)
     constexpr bool kNearest = box_nearest(GEOM) && kRange != kRangeGeneric;
@@ -1337,7 +1344,10 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             const uint32_t rw = kPreSkip && j >= 4u ? (j & 1u ? w.b1 : w.b0) : sel4(j & 3u, w.a0, w.a1, w.a2, w.a3);
             const float r = u01(rw);
             // the single light's pick on the raw word: r < cdf[c] as w < pk_u (host-exact)
+            // (kFactPick: no word falls through and pk_u0 < 2^32, select_path4:
+            // one 32-bit compare)
             auto pick_w = [&](uint32_t wd) {
+                if constexpr (kFactPick) return wd < (uint32_t)kp.pk_u0 ? 0 : 1;
                 return (unsigned long long)wd < kp.pk_u0 ? 0 : ((unsigned long long)wd < kp.pk_u1 ? 1 : 2);
             };
             constexpr bool kPickInt = one_light(LMODE);
@@ -1384,13 +1394,16 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             auto pick_p2w = [&](uint32_t wd) {
                 const uint32_t g = wd >> 8;
                 const int ce = min((int)(g >> (24 - kp.cdf_p2e)), nl);
+                // (kFactPick: g < cdf_end_t = 2^24 always, no fall-through)
                 if (kp.cdf_p2 == 2) {
                     // every light's threshold is exactly (i+1) 2^(24-e)
                     // (host-checked): the first i with g < T[i] is ce itself
+                    if constexpr (kFactPick) return ce;  // (clamped to nl above)
                     return ce < nl ? ce : (g < kp.cdf_end_t ? nl : nl + 1);
                 }
                 const uint32_t fa = __float_as_uint(LS.cdf(max(ce - 1, 0))), fb = __float_as_uint(LS.cdf(ce));
                 int c = (ce >= 1 && g < fa) ? ce - 1 : (g < fb ? ce : ce + 1);
+                if constexpr (kFactPick) return min(c, nl);
                 if (c >= nl) c = g < kp.cdf_end_t ? nl : nl + 1;
                 return c;
             };
@@ -1438,7 +1451,9 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 }
             }
             pick = c;
-            if (c <= nl) {
+            // (kFactPick: c <= nl always -- the scan's last entry cdf[nl] >= 1
+            // exceeds every draw)
+            if (kFactPick || c <= nl) {
                 // words jj+1, jj+2 (jj <= 4 in the skip-ahead instances, <= 5
                 // with kPreSkip, else <= 3)
                 uint32_t r1, r2;
@@ -1465,7 +1480,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                     // below nl has g < T[pick] <= T[nl] on the non-decreasing cdf
                     // that cdf_p2 requires; without cdf_p2 the leaf rule is off,
                     // the whole pick_word here measured -0.9 % on C5)
-                    if constexpr (kK > 0 && !COUNT)
+                    if constexpr (kK > 0 && !COUNT && !kFactPick)
                         pre_ft = kPickIntCdf ? (pre_w >> 8) >= kp.cdf_end_t : pick_word(pre_w) > nl;
                 } else {
                     const bool hi = kSkipAhead && jj >= 4u;
@@ -1617,6 +1632,9 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
         // one is selected (a mixed wave runs both anyway), so the CosineDdf
         // gathers have an unconditional consumer and stay unconditional loads
         vec3 dir_bf = v3(0, 0, 0);
+        // kFactPick, one light: the light sample returned the zero vector (a
+        // certain skip; dir_bf then holds the unused direction)
+        bool lskip = false;
         // (the lattice instances measured 3 % slower this way: their light sample
         // reads the picked light's record, and both directions cost more there)
         constexpr bool kDirBf = one_light(LMODE);
@@ -1634,8 +1652,16 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                 const vec3 ldir = LMODE == kLightsOneA10
                                       ? light_sample_dir_ax_ok<1, 0, true>(LS.one, tpos, u1, u2, &lok)
                                       : light_sample_dir_ax_ok<0, 1, true>(LS.one, tpos, u1, u2, &lok);
+                if constexpr (kFactPick) {
+                    // the pick is a light or the surface: one select per
+                    // component; the light sample's zero vector (!lok) is the
+                    // skip flag below, not a third value
+                    dir_bf = pick < nl ? ldir : cdir;
+                    lskip = pick < nl && !lok;
+                } else {
                 const vec3 other = pick == nl ? cdir : zero;
                 dir_bf = pick < nl && lok ? ldir : other;
+                }
             } else {
                 const vec3 ldir = lsample(LS.one, tpos, u1, u2);
                 dir_bf = pick < nl ? ldir : (pick == nl ? cdir : zero);
@@ -1668,7 +1694,7 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
             }
             ++ti;
             if (COUNT) ++c_iter;
-            if (is_zero(dir)) {
+            if (lskip || is_zero(dir)) {
                 if (COUNT) ++c_skip;
             } else {
                 rd = dir;
@@ -2119,6 +2145,10 @@ __global__ __launch_bounds__(block_of(LMODE, GEOM), waves_per_simd(GEOM, LMODE))
                               (kK > 0 && !COUNT ? lpick || leaf : lpick);
             ti += take ? 1 : 0;
             // (a light pick is not the fall-through: pre_ft is true only on a leaf's take)
+            // (kFactPick: no fall-through, every pick word stands for three draws)
+            if constexpr (kFactPick)
+                k += take ? 3u : 0u;
+            else
             k += take ? (kK > 0 && !COUNT ? (pre_ft ? 1u : 3u) : 3u) : 0u;
             if (COUNT) {
                 c_iter += take ? 1u : 0u;

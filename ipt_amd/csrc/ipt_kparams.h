@@ -113,8 +113,11 @@ struct KParams {
     float cdf_p2s, cdf_end;               // (unread)
     int cdf_p2e;
     uint32_t cdf_end_t;
-    // (unread)
-    int lpf_calc, lc_shift;
+    // no_fallthrough: word_threshold(cdf[nl]) == 2^32, no draw word falls
+    // through the pick (set by plan_scene, read by the selector alone: no kernel
+    // reads it; it sits in an unread field's place, so the layout is the same);
+    // lc_shift on: (unread)
+    int no_fallthrough, lc_shift;
     float lc_x0, lc_y0, lc_dx, lc_dy, lc_ax, lc_ay;
     int ltr_calc, lg_ident;
     float lc_ix, lc_iy, lc_area, lc_spow;
@@ -222,6 +225,22 @@ __host__ __device__ constexpr bool step_fixed_mode(int lm) {
 // one compiled K: n_rays 16, every configuration of bench.py but C3)
 constexpr int kFixedPow2 = -1;
 constexpr int kTreeK = 4;
+// KParams::no_fallthrough, the scene fact that gates the FIXED = kTreeK product
+// instances besides the tree shape (select_path4):
+// word_threshold(cdf[nl]) == 2^32, so every draw word picks a light or the
+// surface and UnionDdf's fall-through (one draw, a zero direction) cannot
+// occur -- what those instances' pick, pre-skip and direction select are
+// compiled for.
+// The instances compiled for it (no_fallthrough_mode): the axis-aligned single
+// light and the lattices with their records in LDS (bench.py's C2, C4 and C5).
+// The lattices with global records keep the general pick in their FIXED =
+// kTreeK instances, and the selector does not ask them for the fact: they are
+// what a lattice too large for the LDS takes, and such a lattice's hundreds of
+// weights rarely sum to 1 (the 17 x 18 census lattices leave 48 of the 2^24
+// draw values past cdf[nl]).
+__host__ __device__ constexpr bool no_fallthrough_mode(int lm) {
+    return lm == kLightsOneA10 || lm == kLightsOneA01 || lm == kLightsGridA10L || lm == kLightsGridA01L;
+}
 __host__ __device__ constexpr bool lax_in_lds(int lm) { return lm == kLightsGridA10L || lm == kLightsGridA01L; }
 __host__ __device__ constexpr bool global_lights(int lm) { return lm == kLightsGlobal || grid_lights(lm); }
 // kLightsOneA10 / A01: the single light is an axis-aligned AreaLight

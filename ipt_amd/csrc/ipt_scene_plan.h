@@ -297,6 +297,9 @@ inline int plan_scene(const ipt_scene* s, const PlanSettings& set, ScenePlan& ou
         }
         k.sa_u = word_threshold(sa_cl);
     }
+    // the product FIXED = kTreeK instances' fact (select_path4): no draw word
+    // falls through the pick
+    k.no_fallthrough = word_threshold(cdf[nl]) == 1ull << 32 ? 1 : 0;
     // every ray origin (camera, surface points within B) inside 2^39: the box
     // planes may use the range-free division (box_plane_t<true>)
     const float lim = 549755813888.0f;  // 2^39

@@ -35,7 +35,8 @@ size_t path_lds_bytes(const KParams& kp) {
 // What the selector reads: the launch's KParams (the scene's fields with
 // n_rays and depth_max), its stack depth (needed_susp) and counting flag, the
 // scene's facts that are no kernel parameter (ScenePlan, ipt_scene_plan.h) and
-// the context's creation-time settings.
+// the context's creation-time settings. (The FIXED = kTreeK instances'
+// scene fact rides in kp.no_fallthrough, a field no kernel reads.)
 struct SelectIn {
     const KParams& kp;
     int susp;
@@ -70,9 +71,14 @@ int select_path4(const SelectIn& in, F&& f) {
                 const uint32_t nr = (uint32_t)kp.n_rays;
                 if (kp.sa_on && nr != 0u && (nr & (nr - 1u)) == 0u) {
                     // the tree shape as well: n_rays == 2^K and depth_max > K + 1 (then
-                    // the stack has K levels: the 4-level instances)
+                    // the stack has K levels: the 4-level instances), and, in the
+                    // instances compiled for it, no fall-through pick
+                    // (kp.no_fallthrough, from plan_scene; one light: its pick
+                    // threshold a 32-bit word as well, i.e. cdf[0] < 1)
                     if constexpr (MAXSUSP == kTreeK)
-                        if (nr == (1u << kTreeK) && kp.depth_max > kTreeK + 1)
+                        if (nr == (1u << kTreeK) && kp.depth_max > kTreeK + 1 &&
+                            (!no_fallthrough_mode(LMODE) ||
+                             (kp.no_fallthrough != 0 && (!one_light(LMODE) || (kp.pk_u0 >> 32) == 0ull))))
                             return f(ms, cnt, lm, g, bool_c<true>{}, int_c<kTreeK>{});
                     return f(ms, cnt, lm, g, bool_c<true>{}, int_c<kFixedPow2>{});
                 }
