@@ -867,7 +867,12 @@ int ipt_denoise_pass_ms(ipt_ctx* ctx, float ms[7]);
         mean = sm / sw;  var = sv / (sw * sw);  cf = sc / sw
         c' = (uint32)cf clamped to [2, max_count];  nf' = (float)c'
         out_pixels = mean;  out_counters = c';  out_m2 = var * (nf' * (nf' - 1.0f))
-      class "reused".
+      class "reused". mean and out_m2 are produced as computed, with no
+      test of their own: finite inputs that pass step 3 with an m2 near
+      FLT_MAX can give out_m2 = +inf (var * (nf' * (nf' - 1.0f)) overflows
+      where a tap with a small counter is blended with one that lifts c').
+      The next ipt_adapt_device and ipt_reproject_device treat such a pixel
+      as any pixel whose variance is not finite.
    5. dev_stats (4 uint32, may be NULL) = {reused, disoccluded, not_surface, 0}:
       integer sums, deterministic; the call zeroes them itself, in stream order.
    The three classes sum to W * H. Under the Grid map row H-1 of the new frame

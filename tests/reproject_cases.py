@@ -2,9 +2,13 @@
 operation for operation as include/ipt_capi.h states it, with the wrong
 variants the CPU tests must tell apart, a camera helper and the case builders
 (rendered planes and guides at two cameras, synthetic guides, poisoned planes).
-Shared by tests/test_reproject_cpu.py (the restatement alone) and the GPU
-tests (the same cases through the kernel). Imports from the other case
-modules and changes nothing there."""
+For the definition's exact comparisons: a dyadic lattice on which they land on
+equality, the same lattice a few ulp off, cameras at the ends of step 2, a
+census of how often each comparison is met with equality, the slips that show
+only there (WRONG_EDGES), and the definition a second time, pixel by pixel
+(reproject_scalar). Shared by tests/test_reproject_cpu.py and
+tests/test_reproject_edges_cpu.py (the restatement alone) and the GPU tests
+(the same cases through the kernel). Imports from the other case modules."""
 import functools
 
 import numpy as np
@@ -20,6 +24,23 @@ GRID, GUI = ac.GRID, ac.GUI
 DEFAULTS = capi.REPROJECT_DEFAULTS
 WRONG = ("dx_outer", "unsquared_var", "nearest", "no_half", "unit_direction", "grid_as_gui", "source_index",
          "no_cap", "signed_counter")
+# One device-side slip each, on the definition's exact comparisons; the lattice
+# cases below are where they show (tests/test_reproject_edges_cpu.py pins where).
+WRONG_EDGES = ("trunc_floor", "contracted", "strict_sigma", "strict_normal", "cap_strict", "round_counter",
+               "grid_last_row", "reused_if_any_tap", "daz")
+# Slips that no input can show, so no test can ask for them:
+# fx == -1 has tx == 0 and its one column inside the frame weighs 0, so sw == 0
+# either way; fx == W has both columns outside; t == 0 makes a / t infinite or
+# NaN, which the window rejects; and sc >= 2 sw in float32 because every
+# cc >= 2 and rounding is monotone, so (uint32)cf is never below 2.
+SAME_RESULT = ("open_left", "closed_right", "t_nonneg", "no_floor_two")
+# what census() counts, in the order DESIGN.md 4.18 lists them
+EVENTS = ("t == 0", "t not finite", "fx == -1", "fy == -1", "fx == W", "fy == H", "tx == 0", "ty == 0",
+          "x0 == -1", "y0 == -1", "x0 == W-1", "tap on Grid source row H-1", "e == sigma_z",
+          "n.n_q == normal_min", "c_q == max_count", "c_q > max_count", "c_q >= 2^24", "used tap with bw == 0",
+          "a tap passed yet sw == 0", "denormal sv term", "cf within an ulp of an integer", "c' == 2",
+          "c' == max_count", "out_m2 not finite", "denormal out_m2")
+GRID_ONLY_EVENTS = ("tap on Grid source row H-1",)
 REUSED, DISOCCLUDED, NOT_SURFACE = 0, 1, 2
 
 
@@ -55,10 +76,6 @@ def box_prev_camera(move):
 
 
 # ---------------------------------------------------------------- the restatement
-def _dot(a, b):
-    return ((a[0] * b[0]).astype(F) + (a[1] * b[1]).astype(F)).astype(F) + (a[2] * b[2]).astype(F)
-
-
 def _vec(x):
     return [F(v) for v in x]
 
@@ -76,12 +93,23 @@ def source_rows_to_dest(rs, H, plane):
     return np.where(inside, yq, -1)
 
 
+def _ops(daz):
+    """(mul, div) in float32; daz: denormal operands and results flushed to a
+    signed zero, as denoise_cases has it."""
+    if not daz:
+        return (lambda a, b: (a * b).astype(F)), (lambda a, b: (a / b).astype(F))
+    z = dn.daz
+    return (lambda a, b: z((z(a) * z(b)).astype(F))), (lambda a, b: z((z(a) / z(b)).astype(F)))
+
+
 def reproject(pixels, counters, m2, prev_guides, cur_guides, W, H, prev_camera, plane=GRID,
               sigma_z=DEFAULTS["sigma_z"], normal_min=DEFAULTS["normal_min"], max_count=DEFAULTS["max_count"],
-              wrong=None):
+              wrong=None, census=None):
     """(out_pixels f32, out_counters u32, out_m2 f32, stats u32[4], class per
-    pixel) of ipt_reproject_device. wrong: one of WRONG."""
-    assert wrong is None or wrong in WRONG
+    pixel) of ipt_reproject_device. wrong: one of WRONG, WRONG_EDGES or
+    SAME_RESULT. census: a dict that takes the event counts (EVENTS, summed
+    onto what it holds); it changes no result."""
+    assert wrong is None or wrong in WRONG + WRONG_EDGES + SAME_RESULT
     n = W * H
     px = np.asarray(pixels, F).reshape(-1)
     cn = np.asarray(counters, np.uint32).reshape(-1)
@@ -93,21 +121,59 @@ def reproject(pixels, counters, m2, prev_guides, cur_guides, W, H, prev_camera, 
     N = [cg["normal"][:, k].astype(F) for k in range(3)]
     pos, dirn, right, up = (_vec(prev_camera[k]) for k in ("position", "direction", "right", "up"))
     sz, nmin = F(sigma_z), F(normal_min)
+    mul, div = _ops(wrong == "daz")
+
+    def dot(a, b):
+        return ((mul(a[0], b[0]) + mul(a[1], b[1])).astype(F) + mul(a[2], b[2])).astype(F)
+
+    ev = dict.fromkeys(EVENTS, 0) if census is not None else None
+
+    def count(name, mask):
+        if ev is not None:
+            ev[name] += int(np.count_nonzero(mask))
+
     with np.errstate(all="ignore"):
         surface = ((cg["kind"] & 3) == 1) & np.isfinite(P[0]) & np.isfinite(P[1]) & np.isfinite(P[2])
         v = [(P[k] - pos[k]).astype(F) for k in range(3)]
-        a, b, c = _dot(v, right), _dot(v, up), _dot(v, dirn)
-        dd = F(F(F(dirn[0] * dirn[0]) + F(dirn[1] * dirn[1])) + F(dirn[2] * dirn[2]))
-        t = c if wrong == "unit_direction" else (c / dd).astype(F)
+        a, b, c = dot(v, right), dot(v, up), dot(v, dirn)
+        dd = F(dot(dirn, dirn))
+        t = c if wrong == "unit_direction" else div(c, dd)
         half = F(0.0) if wrong == "no_half" else F(0.5)
-        fx = ((((a / t).astype(F) + F(0.5)).astype(F) * F(W)).astype(F) - half).astype(F)
-        fy = ((((b / t).astype(F) + F(0.5)).astype(F) * F(H)).astype(F) - half).astype(F)
-        live = surface & (t > 0) & (fx >= F(-1.0)) & (fx < F(W)) & (fy >= F(-1.0)) & (fy < F(H))
+        s_x, s_y = (div(a, t) + F(0.5)).astype(F), (div(b, t) + F(0.5)).astype(F)
+        if wrong == "contracted":  # one fused multiply-add: the product is exact in float64
+            fx = (s_x.astype(np.float64) * W - 0.5).astype(F)
+            fy = (s_y.astype(np.float64) * H - 0.5).astype(F)
+        else:
+            fx, fy = (mul(s_x, F(W)) - half).astype(F), (mul(s_y, F(H)) - half).astype(F)
+        ahead = (t >= 0) if wrong == "t_nonneg" else (t > 0)
+        if wrong == "open_left":
+            window = (fx > F(-1.0)) & (fx < F(W)) & (fy > F(-1.0)) & (fy < F(H))
+        elif wrong == "closed_right":
+            window = (fx >= F(-1.0)) & (fx <= F(W)) & (fy >= F(-1.0)) & (fy <= F(H))
+        else:
+            window = (fx >= F(-1.0)) & (fx < F(W)) & (fy >= F(-1.0)) & (fy < F(H))
+        live = surface & ahead & window
+        count("t == 0", surface & (t == 0))
+        count("t not finite", surface & ~np.isfinite(t))
+        front = surface & (t > 0)
+        count("fx == -1", front & (fx == F(-1.0)))
+        count("fy == -1", front & (fy == F(-1.0)))
+        count("fx == W", front & (fx == F(W)))
+        count("fy == H", front & (fy == F(H)))
         fx, fy = np.where(live, fx, F(0.0)).astype(F), np.where(live, fy, F(0.0)).astype(F)
-        x0f, y0f = np.floor(fx).astype(F), np.floor(fy).astype(F)
+        if wrong == "trunc_floor":
+            x0f, y0f = np.trunc(fx).astype(F), np.trunc(fy).astype(F)
+        else:
+            x0f, y0f = np.floor(fx).astype(F), np.floor(fy).astype(F)
         tx, ty = (fx - x0f).astype(F), (fy - y0f).astype(F)
         x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+        count("tx == 0", live & (tx == 0))
+        count("ty == 0", live & (ty == 0))
+        count("x0 == -1", live & (x0 == -1))
+        count("y0 == -1", live & (y0 == -1))
+        count("x0 == W-1", live & (x0 == W - 1))
         sw, sm, sv, sc = (np.zeros(n, F) for _ in range(4))
+        passed = np.zeros(n, bool)
         taps = [(j, i) for j in (0, 1) for i in (0, 1)]
         if wrong == "dx_outer":
             taps = [(j, i) for i in (0, 1) for j in (0, 1)]
@@ -115,37 +181,70 @@ def reproject(pixels, counters, m2, prev_guides, cur_guides, W, H, prev_camera, 
         for j, i in taps:
             xs, rs = x0 + i, y0 + j
             yq = source_rows_to_dest(rs, H, GUI if wrong == "grid_as_gui" else plane)
+            if plane == GRID and H > 1:
+                count("tap on Grid source row H-1", live & (rs == H - 1) & (xs >= 0) & (xs < W))
+                if wrong == "grid_last_row":  # the row map clamped: row H-1 read as row H-2's pixel
+                    yq = np.where(rs == H - 1, 0, yq)
             ok = live & (yq >= 0) & (xs >= 0) & (xs < W)
             q = np.where(ok, (rs if wrong == "source_index" else yq) * W + xs, 0)
-            bw = ((tx if i else (one - tx).astype(F)) * (ty if j else (one - ty).astype(F))).astype(F)
+            bw = mul(tx if i else (one - tx).astype(F), ty if j else (one - ty).astype(F))
             if wrong == "nearest":
                 ok &= ((tx >= F(0.5)) == bool(i)) & ((ty >= F(0.5)) == bool(j))
                 bw = np.ones(n, F)
             cq, pq = cn[q], px[q]
             nf = cq.astype(F)
-            var = (mm[q] / (nf * (nf - one)).astype(F)).astype(F)
+            var = div(mm[q], mul(nf, (nf - one).astype(F)))
             Pq = [pg["pos"][q, k].astype(F) for k in range(3)]
             Nq = [pg["normal"][q, k].astype(F) for k in range(3)]
-            dn_ = _dot(N, Nq)
-            e = np.abs(_dot(N, [(Pq[k] - P[k]).astype(F) for k in range(3)]))
+            dn_ = dot(N, Nq)
+            e = np.abs(dot(N, [(Pq[k] - P[k]).astype(F) for k in range(3)]))
             ok &= ((pg["kind"][q] & 3) == 1) & (cq >= 2) & np.isfinite(pq) & np.isfinite(var)
-            ok &= (dn_ >= nmin) & (e <= sz)
-            cc = cq if wrong == "no_cap" else np.minimum(cq, max_count)
+            flat, near = (dn_ >= nmin), (e <= sz)
+            count("e == sigma_z", ok & flat & (e == sz))
+            count("n.n_q == normal_min", ok & near & (dn_ == nmin))
+            if wrong == "strict_normal":
+                flat = dn_ > nmin
+            if wrong == "strict_sigma":
+                near = e < sz
+            ok &= flat & near
+            if wrong == "cap_strict":
+                cc = np.where(cq < max_count, cq, max_count - 1)
+            else:
+                cc = cq if wrong == "no_cap" else np.minimum(cq, max_count)
             ccf = cc.astype(F)
-            ve = (var * (nf / ccf).astype(F)).astype(F)
-            bw2 = bw if wrong == "unsquared_var" else (bw * bw).astype(F)
+            ve = mul(var, div(nf, ccf))
+            bw2 = bw if wrong == "unsquared_var" else mul(bw, bw)
+            term = mul(bw2, ve)
+            count("c_q == max_count", ok & (cq == max_count))
+            count("c_q > max_count", ok & (cq > max_count))
+            count("c_q >= 2^24", ok & (cq >= 2 ** 24))
+            count("used tap with bw == 0", ok & (bw == 0))
+            count("denormal sv term", ok & dn.denormal(term))
+            passed |= ok
             sw = np.where(ok, sw + bw, sw).astype(F)
-            sm = np.where(ok, sm + (bw * pq).astype(F), sm).astype(F)
-            sv = np.where(ok, sv + (bw2 * ve).astype(F), sv).astype(F)
-            sc = np.where(ok, sc + (bw * ccf).astype(F), sc).astype(F)
-        reused = live & (sw != 0)
-        mean = (sm / sw).astype(F)
-        var = (sv / (sw * sw).astype(F)).astype(F)
-        cf = np.where(reused, (sc / sw).astype(F), F(0.0))
+            sm = np.where(ok, sm + mul(bw, pq), sm).astype(F)
+            sv = np.where(ok, sv + term, sv).astype(F)
+            sc = np.where(ok, sc + mul(bw, ccf), sc).astype(F)
+        reused = live & (passed if wrong == "reused_if_any_tap" else (sw != 0))
+        count("a tap passed yet sw == 0", live & passed & (sw == 0))
+        mean = div(sm, sw)
+        var = div(sv, mul(sw, sw))
+        cf = np.where(reused, div(sc, sw), F(0.0)).astype(F)
         top = 0xffffffff if wrong == "no_cap" else max_count
-        co = np.clip(cf.astype(np.int64), 2, top).astype(np.uint32)
+        whole = np.rint(cf) if wrong == "round_counter" else cf
+        if wrong == "reused_if_any_tap":  # (it alone makes 0 / 0)
+            whole = np.where(np.isfinite(whole), whole, F(0.0))
+        co = np.clip(whole.astype(np.int64), 0 if wrong == "no_floor_two" else 2, top).astype(np.uint32)
         nf = co.astype(F)
-        om2 = (var * (nf * (nf - one)).astype(F)).astype(F)
+        om2 = mul(var, mul(nf, (nf - one).astype(F)))
+        count("cf within an ulp of an integer", reused & (np.abs(cf - np.rint(cf)) <= np.spacing(cf)))
+        count("c' == 2", reused & (co == 2))
+        count("c' == max_count", reused & (co == max_count))
+        count("out_m2 not finite", reused & ~np.isfinite(om2))
+        count("denormal out_m2", reused & dn.denormal(om2))
+    if census is not None:
+        for k, x in ev.items():
+            census[k] = census.get(k, 0) + x
     cls = np.where(reused, REUSED, np.where(surface, DISOCCLUDED, NOT_SURFACE)).astype(np.uint8)
     stats = np.array([(cls == k).sum() for k in range(3)] + [0], np.uint32)
     return (np.where(reused, mean, F(0.0)).astype(F), np.where(reused, co, 0).astype(np.uint32),
@@ -263,3 +362,240 @@ def poisoned(case, W, H, seed=11):
         for field, k, bits in POISON_GUIDE:
             g[field][spots(), k] = np.uint32(bits).view(F)
     return px, cn, m2, pg.reshape(H, W), cg.reshape(H, W), cam
+
+
+# ---------------------------------------------------------------- the dyadic lattice
+# A plane at z = 0 under a camera straight above it, every quantity a small
+# dyadic number: on a power-of-two frame a / t, sx and fx are exact, and the
+# definition's comparisons land on equality.
+LATTICE = dict(sigma_z=2.0 ** -5, normal_min=0.5, max_count=16)
+LATTICE_MAX_COUNTS = (2, 16, 1 << 24)
+LATTICE_FRAMES = ((32, 16), (64, 32))
+NEAR_FRAMES = ((32, 16), (37, 23), (131, 67))
+TINY_LATTICE_FRAMES = ((1, 1), (2, 1), (1, 2), (2, 2), (4, 2), (1, 8))
+# name: (aW, b, cH, d), the camera shift (a W + b, c H + d) in pixels. The
+# pixel of source row ys and column x lands on fx = x - sx, fy = ys - sy.
+LATTICE_SHIFTS = (
+    ("none", (0, 0, 0, 0)),
+    ("quarter_x", (0, 0.25, 0, 0)), ("quarter_y", (0, 0, 0, 0.25)), ("quarter_xy", (0, 0.25, 0, 0.25)),
+    ("half_x", (0, 0.5, 0, 0)), ("half_y", (0, 0, 0, 0.5)), ("half_xy", (0, 0.5, 0, 0.5)),
+    ("minus_half_xy", (0, -0.5, 0, -0.5)),
+    ("one_x", (0, 1, 0, 0)), ("minus_one_x", (0, -1, 0, 0)), ("one_y", (0, 0, 0, 1)), ("minus_one_y", (0, 0, 0, -1)),
+    ("whole_xy", (0, 3, 0, -2)),
+    ("w_minus_half", (1, -0.5, 0, 0)), ("minus_w_plus_half", (-1, -0.5, 0, 0)), ("minus_w_minus_half", (-1, 0.5, 0, 0)),
+    ("h_plus_half", (0, 0, 1, 0.5)), ("minus_h_minus_half", (0, 0, -1, 0.5)), ("h_minus_three_halves", (0, 0, 1, -1.5)),
+    ("half_frame", (0.5, 0.25, 0.5, 0.75)),
+    ("tiny", (0, 2.0 ** -20, 0, -2.0 ** -20)),
+)
+
+
+def lattice_counters(mc):
+    return 0, 1, 2, 3, mc - 1, mc, mc + 1, 2 ** 24 - 1, 2 ** 24, 2 ** 24 + 1, 2 ** 31, 2 ** 32 - 1
+
+
+LATTICE_M2 = (0.0, 2.0 ** -149, 2.0 ** -130, 2.0 ** -100, 1e-3, 0.2, 3e38)
+HALF_PLUS_4ULP = float(np.uint32(0x3f000004).view(F))
+LATTICE_NORMALS = (0.25, 0.5, HALF_PLUS_4ULP, 1.0)
+
+
+def lattice_shift(name, W, H):
+    aw, b, ch, d = dict(LATTICE_SHIFTS)[name]
+    return aw * W + b, ch * H + d
+
+
+def lattice_camera(W, H, shift=(0.0, 0.0), dlen=2.0, pitch=2.0 ** -4):
+    """Straight above the lattice, shifted by `shift` pixels: right = +x,
+    up = +y, direction.direction = dlen^2 exactly."""
+    return scenes.simple_camera((shift[0] * pitch, shift[1] * pitch * W / H, W * pitch * dlen), (0.0, 0.0, -dlen),
+                                up_hint=(0.0, 1.0, 0.0))
+
+
+def lattice_guides(W, H, plane, pitch=2.0 ** -4):
+    """The plane z = 0 with normal +z in destination order under the plane's
+    row map; a row without a nominal source as ipt_guides_device leaves it."""
+    g = np.zeros((H, W), capi.GuideRecord)
+    g["kind"] = 0xff
+    src = dn.guide_rows(H, plane)
+    ok = src >= 0
+    g["kind"][ok] = 1 | 4
+    g["pos"][ok, :, 0] = ((np.arange(W) + 0.5 - W / 2) * pitch).astype(F)[None, :]
+    g["pos"][ok, :, 1] = ((src[ok] + 0.5 - H / 2) * pitch * W / H).astype(F)[:, None]
+    g["normal"][ok, :, 2] = F(1.0)
+    return g
+
+
+def lattice_case(W, H, shift, plane, dlen=2.0, pitch=2.0 ** -4, max_count=LATTICE["max_count"], seed=7,
+                 benign=False):
+    """(pixels, counters, m2, prev_guides, cur_guides, prev_camera) on the
+    lattice; shift: a name of LATTICE_SHIFTS or (sx, sy) in pixels. The
+    previous guides' heights are k 2^-6, k in -3..3 (e = 0, sigma_z / 2,
+    sigma_z, 3 sigma_z / 2 at sigma_z = 2^-5), their normals' z one of
+    LATTICE_NORMALS (n.n_q below, at and above normal_min = 0.5); counters and
+    m2 are drawn from lattice_counters(max_count) and LATTICE_M2. benign:
+    every pixel's own history passes every test (heights within sigma_z,
+    normals >= 0.5, counters 2..max_count). Exact on power-of-two frames."""
+    if isinstance(shift, str):
+        shift = lattice_shift(shift, W, H)
+    rng = np.random.default_rng([W, H, seed, int(plane == GUI)])
+    n = W * H
+    cg = lattice_guides(W, H, plane, pitch)
+    pg = cg.copy()
+    surface = pg["kind"] == (1 | 4)
+    k = rng.integers(-2, 3, (H, W)) if benign else rng.integers(-3, 4, (H, W))
+    nz = rng.choice(np.array(LATTICE_NORMALS[1:] if benign else LATTICE_NORMALS, F), (H, W))
+    pg["pos"][..., 2] = np.where(surface, (k * 2.0 ** -6).astype(F), F(0.0))
+    pg["normal"][..., 2] = np.where(surface, nz, F(0.0))
+    px = rng.random(n, dtype=F)
+    if benign:
+        cn = rng.integers(2, max_count + 1, n).astype(np.uint32)
+    else:
+        cn = rng.choice(np.array(lattice_counters(max_count), np.uint32), n)
+    m2 = rng.choice(np.array(LATTICE_M2, F), n)
+    return px, cn, m2, pg, cg, lattice_camera(W, H, shift, dlen, pitch)
+
+
+def constant_lattice_case(W, H, shift, plane, dlen=2.0, pitch=2.0 ** -4):
+    """The lattice with nothing drawn: the previous guides are the current
+    ones, every counter is 4, every m2 is 0.25 and pixel q holds (q + 1) / 16,
+    so every tap inside the frame that the row map gives a pixel is used and
+    the border and the map alone decide what is reused."""
+    if isinstance(shift, str):
+        shift = lattice_shift(shift, W, H)
+    n = W * H
+    g = lattice_guides(W, H, plane, pitch)
+    px = ((np.arange(n) + 1) / 16).astype(F)
+    return px, np.full(n, 4, np.uint32), np.full(n, 0.25, F), g.copy(), g, lattice_camera(W, H, shift, dlen, pitch)
+
+
+def near_lattice_case(W, H, shift, plane, seed=13, **kw):
+    """A lattice case whose current positions are moved, per component, by -2,
+    -1, +1 and +2 ulp on seeded quarters of the pixels: fx and fy straddle -1,
+    the integers and W by the smallest steps there are. Any frame size."""
+    px, cn, m2, pg, cg, cam = lattice_case(W, H, shift, plane, **kw)
+    cg = cg.copy()
+    rng = np.random.default_rng([W, H, seed, int(plane == GUI)])
+    surface = cg["kind"] == (1 | 4)
+    for k in range(3):
+        steps = np.array((-2, -1, 1, 2))[rng.integers(0, 4, (H, W))]
+        p = cg["pos"][..., k].copy()
+        for r in range(2):
+            go = (np.abs(steps) > r) & surface
+            p = np.where(go, np.nextafter(p, np.where(steps > 0, F(np.inf), F(-np.inf)).astype(F)), p).astype(F)
+        cg["pos"][..., k] = p
+    return px, cn, m2, pg, cg, cam
+
+
+def camera_edge_cases(W, H, dlen=2.0, pitch=2.0 ** -4):
+    """Previous cameras at the ends of the contract's step 2, by name; each is
+    used on lattice guides, and each has a defined result."""
+    z = W * pitch * dlen
+
+    def cam(position=(0.0, 0.0, z), direction=(0.0, 0.0, -dlen), right=(1.0, 0.0, 0.0), up=(0.0, 1.0, 0.0)):
+        return {k: [float(F(x)) for x in v] for k, v in (("position", position), ("direction", direction),
+                                                         ("right", right), ("up", up))}
+
+    return {
+        "zero_direction": cam(direction=(0.0, 0.0, 0.0)),               # c = 0, dd = 0: t is NaN
+        "denormal_direction": cam(direction=(0.0, 0.0, -2.0 ** -140)),  # dd underflows to 0: t = +inf
+        "direction_2p60": cam(position=(0.0, 0.0, W * pitch * 2.0 ** 60), direction=(0.0, 0.0, -2.0 ** 60)),
+        "direction_2m60": cam(position=(0.0, 0.0, W * pitch * 2.0 ** -60), direction=(0.0, 0.0, -2.0 ** -60)),
+        "position_3e38": cam(position=(3e38, 3e38, 3e38)),              # c overflows: t = +inf
+        "nan_right": cam(right=(float("nan"), 0.0, 0.0)),
+        "inf_position": cam(position=(float("inf"), 0.0, z)),
+        "zero_up_right": cam(right=(0.0, 0.0, 0.0), up=(0.0, 0.0, 0.0)),  # every pixel lands on the frame's centre
+        "in_plane": cam(position=(0.0, 0.0, 0.0)),                      # c = 0 and t = 0 on every pixel
+    }
+
+
+def census(case, W, H, plane, **params):
+    """The counts of EVENTS (without the Grid map's own under the Gui map) of
+    one case, from reproject's own intermediate values."""
+    c = {}
+    reproject(*case[:5], W, H, case[5], plane, census=c, **params)
+    return {k: v for k, v in c.items() if plane == GRID or k not in GRID_ONLY_EVENTS}
+
+
+# ---------------------------------------------------------------- the definition again, pixel by pixel
+def reproject_scalar(pixels, counters, m2, prev_guides, cur_guides, W, H, prev_camera, plane=GRID,
+                     sigma_z=DEFAULTS["sigma_z"], normal_min=DEFAULTS["normal_min"], max_count=DEFAULTS["max_count"]):
+    """reproject's tuple from include/ipt_capi.h's steps 1 to 5 read one pixel
+    at a time: np.float32 scalars, plain ifs, no masked lane, no helper of
+    reproject's. Slow: for frames of at most about 2500 pixels."""
+    px, cn, mm = (np.asarray(a, t).reshape(-1) for a, t in ((pixels, F), (counters, np.uint32), (m2, F)))
+    pg, cg = np.asarray(prev_guides).reshape(-1), np.asarray(cur_guides).reshape(-1)
+    position, direction, right, up = ([F(x) for x in prev_camera[k]] for k in ("position", "direction", "right", "up"))
+    sz, nmin, one, halff = F(sigma_z), F(normal_min), F(1.0), F(0.5)
+    out_px, out_cn, out_m2 = np.zeros(W * H, F), np.zeros(W * H, np.uint32), np.zeros(W * H, F)
+    cls = np.zeros(W * H, np.uint8)
+
+    def dot3(a, b):
+        return F(F(F(a[0] * b[0]) + F(a[1] * b[1])) + F(a[2] * b[2]))
+
+    with np.errstate(all="ignore"):
+        dd = dot3(direction, direction)
+        for d in range(W * H):
+            g = cg[d]
+            P, nrm = [F(x) for x in g["pos"]], [F(x) for x in g["normal"]]
+            if (int(g["kind"]) & 3) != 1 or not all(np.isfinite(x) for x in P):
+                cls[d] = NOT_SURFACE
+                continue
+            cls[d] = DISOCCLUDED
+            v = [F(P[k] - position[k]) for k in range(3)]
+            a, b, c = dot3(v, right), dot3(v, up), dot3(v, direction)
+            t = F(c / dd)
+            if not t > 0:
+                continue
+            fx = F(F(F(F(a / t) + halff) * F(W)) - halff)
+            fy = F(F(F(F(b / t) + halff) * F(H)) - halff)
+            if not (fx >= F(-1.0) and fx < F(W)) or not (fy >= F(-1.0) and fy < F(H)):
+                continue
+            x0, y0 = np.floor(fx), np.floor(fy)
+            tx, ty = F(fx - x0), F(fy - y0)
+            sw = sm = sv = sc = F(0.0)
+            for j in (0, 1):
+                for i in (0, 1):
+                    xs, r = int(x0) + i, int(y0) + j
+                    bw = F((tx if i else F(one - tx)) * (ty if j else F(one - ty)))
+                    if xs < 0 or xs >= W or r < 0 or r >= H:
+                        continue
+                    if plane == GUI:
+                        row = H - 1 - r
+                    elif H == 1:
+                        row = 0
+                    elif r <= H - 2:
+                        row = H - 2 - r
+                    else:
+                        continue  # the Grid map's source row H-1 is no pixel's nominal source
+                    q = row * W + xs
+                    if (int(pg[q]["kind"]) & 3) != 1:
+                        continue
+                    c_q = int(cn[q])
+                    if not c_q >= 2:
+                        continue
+                    if not np.isfinite(px[q]):
+                        continue
+                    nf = F(c_q)
+                    var_q = F(mm[q] / F(nf * F(nf - one)))
+                    if not np.isfinite(var_q):
+                        continue
+                    if not dot3(nrm, [F(x) for x in pg[q]["normal"]]) >= nmin:
+                        continue
+                    if not abs(dot3(nrm, [F(F(pg[q]["pos"][k]) - P[k]) for k in range(3)])) <= sz:
+                        continue
+                    cc = min(c_q, max_count)
+                    ve = F(var_q * F(F(c_q) / F(cc)))
+                    sw = F(sw + bw)
+                    sm = F(sm + F(bw * px[q]))
+                    sv = F(sv + F(F(bw * bw) * ve))
+                    sc = F(sc + F(bw * F(cc)))
+            if sw == 0:
+                continue
+            cf = F(sc / sw)
+            c_new = min(max(int(cf), 2), max_count)
+            nf = F(c_new)
+            out_px[d] = F(sm / sw)
+            out_cn[d] = c_new
+            out_m2[d] = F(F(sv / F(sw * sw)) * F(nf * F(nf - one)))
+            cls[d] = REUSED
+    stats = np.array([int((cls == k).sum()) for k in range(3)] + [0], np.uint32)
+    return out_px, out_cn, out_m2, stats, cls
